@@ -9,6 +9,15 @@ one batch of 32 synthetic 640x640 frames that are already resident in HBM, per G
 weights; there is no data-path collective - results are gathered once, after the
 timed region, to show the exchange step).  Prints ONE JSON line on rank 0.
 
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, the configuration).  `--full` adds every
+side measurement listed under "Extra objects" below, each in runs of its own after the timed steps.
+
+`--dump-outputs DIR` writes what the last timed step computed - the probability map `prob` and the binarized map `bitmap`
+of ocr_det_forward_device - as DIR/<name>.npy in float32, at most 60 MB in all: an output too large for its share is written
+as a fixed, seeded sample of its frames (the result line's `outputs` names them).  Frames and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
+
 `python bench.py --gpus N` is a complete command for any N: when it is not already running
 under torch.distributed.run (no RANK in the environment) and N > 1, this process only LAUNCHES -
 before it has made any GPU call it starts N child ranks of itself (subprocess, one per GPU, RANK /
@@ -16,7 +25,7 @@ LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set), relays rank 
 exits non-zero if any rank failed.  Under `python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...` the ranks exist already and it just runs as one of them.
 
-Extra objects in that line:
+Extra objects in that line (--full only):
   roofline      dominant kernel (largest summed time), measured live with HIP events
                 on the launch stream: the MFMA FLOPs its launches EXECUTE / their time,
                 against the dense MFMA peak of the instruction it issues - 157.3 TF/s for the f32 forms,
@@ -74,7 +83,15 @@ def parse(argv=None):
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
                     help="f32 = the reference's arithmetic (BASELINE configs[1], the headline); bf16 = the opt-in "
                          "OCR_PRECISION_BF16 detector (configs[4]), reported as its own line")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (roofline, other precisions, host-memory and post-processing rates, "
+                         "end-to-end paths, the N > 1 exchange, the CPU baseline); off: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # --------------------------------------------------------------------------------------------------
@@ -414,6 +431,33 @@ def c_abi_exchange(capi, dist, torch, polys, scores, gathered, world, rank, loca
     return out
 
 
+DUMP_SHARES = (("prob", 52_500_000), ("bitmap", 7_500_000))   # bytes per output in --dump-outputs: 60 MB in all
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """--dump-outputs: every output as out_dir/<name>.npy in float32.  One that exceeds its share of DUMP_SHARES is cut to a
+    sample of whole frames (axis 0) drawn with a fixed seed - the same frames for the same arguments - or, when even one frame
+    exceeds it, to a seeded sample of its elements.  Returns what was written, per name, for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for seed, (name, share) in enumerate(DUMP_SHARES):
+        a = arrays[name]
+        frame = a[0].size * 4
+        written = "all"
+        if a.size * 4 > share:
+            rng = np.random.default_rng(seed)
+            if frame <= share:
+                idx = np.sort(rng.choice(a.shape[0], share // frame, replace=False))
+                a, written = a[idx], idx.tolist()
+            else:
+                a = a.reshape(-1)[np.sort(rng.choice(a.size, share // 4, replace=False))]
+                written = f"{a.size} elements, numpy default_rng({seed}) without replacement, sorted"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        info[name] = {"shape": list(arrays[name].shape), "frames": written}
+    return info
+
+
 _RESULT_FD = None
 
 
@@ -527,10 +571,18 @@ def main():
         elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(elapsed)
 
+    # ---- the last timed step's outputs, before any side measurement below reuses prob / bitmap
+    dumped = None
+    if rank == 0 and a.dump_outputs:
+        dumped = dump_outputs(a.dump_outputs, {"prob": prob.cpu().numpy(), "bitmap": bitmap.cpu().numpy()})
+
+    # ---- everything below up to the result line is a side measurement: --full only
+    extras_on = a.full and not a.no_extras
+
     # ---- roofline of the dominant kernel: HIP events around every launch, on the launch stream
     roof = None
     executed_gflop = None
-    if rank == 0:
+    if rank == 0 and a.full:
         agg = {}
         reps = 3
         for _ in range(reps):
@@ -598,7 +650,7 @@ def main():
     # ---- the same step with every conv on the exact-f32 matrix instructions (option mfma=f32): what the split-bf16
     # kernels buy, measured beside the headline in the same process
     strict = {}
-    if rank == 0 and a.dtype == "f32" and not a.no_extras:
+    if rank == 0 and a.dtype == "f32" and extras_on:
         try:
             d32 = capi.Detector(W.pack_blob(det_w), local, options="mfma=f32;" + det_opts)
             d32.set_stream(stream.cuda_stream)
@@ -618,11 +670,11 @@ def main():
         except Exception as e:
             strict["f32_mfma_only_error"] = f"{type(e).__name__}: {e}"
 
-    # ---- the opt-in bf16 precision of configs[4], measured in EVERY default run (never the headline): the same detector handle
+    # ---- the opt-in bf16 precision of configs[4], measured in every --full run (never the headline): the same detector handle
     # switched to precision=bf16 for ten steps, its dominant kernel from per-launch HIP events, and the whole hot path
     # (detect -> polygons -> crops -> classify) further down (`bf16.e2e_pages_per_s`)
     bf16 = {}
-    if rank == 0 and a.dtype == "f32" and not a.no_extras:
+    if rank == 0 and a.dtype == "f32" and extras_on:
         try:
             det.set_precision(capi.PRECISION_BF16)
             k = 10
@@ -657,7 +709,7 @@ def main():
     # ---- frames in HOST memory (the reference's call sites hand CPU tensors): PCIe inside the timed region.  Blocking forward
     # over pipelined pieces (ocr_det_forward / _u8, MEM_HOST) from pinned and from pageable memory.
     host = {}
-    if rank == 0 and not a.no_extras and a.dtype == "f32":
+    if rank == 0 and extras_on and a.dtype == "f32":
         try:
             xf = x.cpu().numpy()
             xb = np.clip(np.rint(xf), 0, 255).astype(np.uint8)
@@ -692,31 +744,32 @@ def main():
     # RCCL over xGMI when the backend is nccl (ocr-rs_amd/parallel.py)
     post = {}
     polys = scores = pm = adj = params = gathered = None
-    try:
-        params = capi.default_params(skip_degenerate=True)
-        maps = FX.text_like_maps(n, s, seed=rank)
-        pm = torch.from_numpy(maps).to(x.device)
-        adj = np.ones((n, 2))
-        torch.cuda.synchronize()
-        polys, scores = det.postprocess(pm, n, s, s, adj, capi.MEM_DEVICE, params)
-        reps = 5
-        t1 = time.perf_counter()
-        for _ in range(reps):   # the library call (ocr_det_postprocess), not the conversion of its CSR block to Python lists
-            det.postprocess_counts(pm, n, s, s, adj, capi.MEM_DEVICE, params)
-        post = {"postprocess_images_per_s": round(n * reps / (time.perf_counter() - t1), 1),
-                "postprocess_polygons_per_image": round(sum(len(p) for p in polys) / n, 2)}
-        if rank == 0 and not a.no_extras:
-            dm = torch.from_numpy(FX.dense_text_maps(n, s, 5)).to(x.device)
-            npoly, _ = det.postprocess_counts(dm, n, s, s, adj, capi.MEM_DEVICE, params)
+    if a.full:
+        try:
+            params = capi.default_params(skip_degenerate=True)
+            maps = FX.text_like_maps(n, s, seed=rank)
+            pm = torch.from_numpy(maps).to(x.device)
+            adj = np.ones((n, 2))
+            torch.cuda.synchronize()
+            polys, scores = det.postprocess(pm, n, s, s, adj, capi.MEM_DEVICE, params)
+            reps = 5
             t1 = time.perf_counter()
-            for _ in range(reps):
-                det.postprocess_counts(dm, n, s, s, adj, capi.MEM_DEVICE, params)
-            post["postprocess_dense_images_per_s"] = round(n * reps / (time.perf_counter() - t1), 1)
-            post["postprocess_dense_polygons_per_image"] = round(npoly / n, 2)
-    except Exception as e:  # side numbers never hide the headline
-        post["postprocess_error"] = f"{type(e).__name__}: {e}"
-        polys = None
-    if dist is not None:
+            for _ in range(reps):   # the library call (ocr_det_postprocess), not the conversion of its CSR block to Python lists
+                det.postprocess_counts(pm, n, s, s, adj, capi.MEM_DEVICE, params)
+            post = {"postprocess_images_per_s": round(n * reps / (time.perf_counter() - t1), 1),
+                    "postprocess_polygons_per_image": round(sum(len(p) for p in polys) / n, 2)}
+            if rank == 0 and extras_on:
+                dm = torch.from_numpy(FX.dense_text_maps(n, s, 5)).to(x.device)
+                npoly, _ = det.postprocess_counts(dm, n, s, s, adj, capi.MEM_DEVICE, params)
+                t1 = time.perf_counter()
+                for _ in range(reps):
+                    det.postprocess_counts(dm, n, s, s, adj, capi.MEM_DEVICE, params)
+                post["postprocess_dense_images_per_s"] = round(n * reps / (time.perf_counter() - t1), 1)
+                post["postprocess_dense_polygons_per_image"] = round(npoly / n, 2)
+        except Exception as e:  # side numbers never hide the headline
+            post["postprocess_error"] = f"{type(e).__name__}: {e}"
+            polys = None
+    if dist is not None and a.full:
         # the collective section runs only when EVERY rank has results (a rank that failed above must not leave
         # the others waiting in an all-gather)
         ok = torch.tensor([0.0 if polys is None else 1.0], dtype=torch.float64, device=comm_dev)
@@ -752,7 +805,7 @@ def main():
     # ---- configs[3] end to end at its best: every rank runs the library's pipelined detect (forward of batch k+1 under the
     # post-processing of batch k) on synthetic pages with text-following weights, and the polygon lists of the batch that just
     # came back are all-gathered each step.  Set-up may fail on a rank; the collective loop runs only if it worked on all.
-    if dist is not None and gathered is not None and not a.no_extras:
+    if dist is not None and gathered is not None and extras_on:
         dt = xp = None
         try:
             dt = capi.Detector(W.pack_blob(W.make_det_weights_text()), local, options=det_opts)
@@ -793,7 +846,7 @@ def main():
     # pipelined inside the library (ocr_det_detect_pipelined).  Random weights give noise maps, so this leg runs the
     # text-following synthetic weights on synthetic pages (weights.make_det_weights_text / synth_text_pages): same graph,
     # same kernels, maps with ~20 word polygons per page.
-    if rank == 0 and not a.no_extras and a.dtype == "f32":
+    if rank == 0 and extras_on and a.dtype == "f32":
         try:
             dt = capi.Detector(W.pack_blob(W.make_det_weights_text()), local, options=det_opts)
             dt.set_stream(stream.cuda_stream)
@@ -850,7 +903,7 @@ def main():
     # ---- configs[4] / the whole hot path on one GPU: pages -> detect (pipelined with its post-processing) -> crops of every
     # polygon -> classify, in this run's precision; 128 synthetic pages in four batches of 32
     e2e = {}
-    if rank == 0 and not a.no_extras:
+    if rank == 0 and extras_on:
         def e2e_pages(dtype):
             de = capi.Detector(W.pack_blob(W.make_det_weights_text()), local, options=det_opts)
             if dtype == "bf16":
@@ -908,7 +961,7 @@ def main():
     # from device-resident frames and from pinned host memory with the handle's pool at 1, 2, 4 and 16 threads, on text-like
     # pages (18 words) and dense ones (about 65 words per page), in both precisions
     sweep = {}
-    if rank == 0 and not a.no_extras and a.dtype == "f32":
+    if rank == 0 and extras_on and a.dtype == "f32":
         try:
             params = capi.default_params(skip_degenerate=True)
             adj1 = np.ones((n, 2))
@@ -968,7 +1021,7 @@ def main():
 
     extras = {}
     rec_w = W.make_rec_weights(0)
-    if rank == 0 and not a.no_extras:
+    if rank == 0 and extras_on:
         try:
             rec = capi.Recognizer(W.pack_blob(rec_w), local)
             rec.set_stream(stream.cuda_stream)
@@ -1080,37 +1133,40 @@ def main():
         line["post_threads"] = min(16, cores_per_rank)
         line["cores_per_rank"] = cores_per_rank
         line["rank_cpus"] = PINNED_CPUS   # N > 1: the CPUs this rank pinned itself to before any GPU call (nearest its GPU's NUMA node); None = unpinned
-        if not a.no_cpu_baseline:   # every N: each line of a scaling sweep stands alone (the other ranks wait in the barrier below)
+        if a.full and not a.no_cpu_baseline:   # every N: each line of a scaling sweep stands alone (the other ranks wait in the barrier below)
             try:
                 line["cpu_baseline"] = cpu_baseline(det_w, rec_w, s, a.cpu_seconds)
             except Exception as e:
                 line["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
         if dist is not None and try_c_abi and gathered is not None:
             line.update(c_abi_exchange(capi, dist, torch, polys, scores, gathered, world, rank, local, line))
-        # the last ~1 500 characters of the line are what a stored record keeps: the numbers a reader needs, once more, at the very end
-        cb = line.get("cpu_baseline") or {}
-        b16 = line.get("bf16") or {}
-        sw = (line.get("post_threads_sweep") or {}).get("2") or {}
-        line["summary"] = {
-            "ms_per_step": line["ms_per_step"], "images_per_s": line["value"], "n_gpus": world, "dtype": a.dtype,
-            "roofline": {"kernel": roof.get("kernel"), "frac": roof.get("frac"), "achieved_tflops": roof.get("achieved"), "peak_tflops": roof.get("peak"),
-                         "avg_launch_ms": roof.get("avg_launch_ms"), "avg_launch_ms_in_schedule": roof.get("avg_launch_ms_in_schedule"), "traffic_bytes": roof.get("traffic"), "mfma_busy": roof.get("mfma_busy")},
-            "f32_mfma_only_ms": (line.get("f32_mfma_only") or {}).get("ms_per_step"),
-            "bf16": {k2: b16.get(k2) for k2 in ("ms_per_step", "images_per_s", "e2e_pages_per_s")} if b16 else None,
-            "e2e_pages_per_s": line.get("e2e_pages_per_s"),
-            "detect_postprocess_pipelined_images_per_s": line.get("detect_postprocess_pipelined_images_per_s"),
-            "postprocess_images_per_s": {"text": line.get("postprocess_images_per_s"), "dense": line.get("postprocess_dense_images_per_s")},
-            "post_threads_2": {k2: v2.get("detect_postprocess_pipelined_images_per_s") for k2, v2 in sw.items() if isinstance(v2, dict) and "detect_postprocess_pipelined_images_per_s" in v2} if sw else None,
-            "post_threads_16_device_chain": {k2: v2.get("detect_postprocess_pipelined_images_per_s") for k2, v2 in ((line.get("post_threads_sweep") or {}).get("16_device_chain") or {}).items()
-                                             if isinstance(v2, dict) and "detect_postprocess_pipelined_images_per_s" in v2} or None,
-            "extension": line.get("extension"),
-            "rec_crops_per_s": {"b256": line.get("rec_crops_per_s_b256"), "b65536": line.get("rec_crops_per_s_b65536")},
-            "cpu_baseline": {"images_per_s": cb.get("value"), "cores": cb.get("cores"), "kind": cb.get("kind"),
-                             "one_thread": (cb.get("one_thread") or {}).get("value"),
-                             "rec_crops_per_s": (cb.get("recognition") or {}).get("value"),
-                             "postprocess_images_per_s": (cb.get("postprocess") or {}).get("value")},
-            "exchange_ok": line.get("exchange_ok"),
-        }
+        if dumped is not None:
+            line["outputs"] = {"dir": a.dump_outputs, **dumped}
+        if a.full:
+            # the last ~1 500 characters of the line are what a stored record keeps: the numbers a reader needs, once more, at the very end
+            cb = line.get("cpu_baseline") or {}
+            b16 = line.get("bf16") or {}
+            sw = (line.get("post_threads_sweep") or {}).get("2") or {}
+            line["summary"] = {
+                "ms_per_step": line["ms_per_step"], "images_per_s": line["value"], "n_gpus": world, "dtype": a.dtype,
+                "roofline": {"kernel": roof.get("kernel"), "frac": roof.get("frac"), "achieved_tflops": roof.get("achieved"), "peak_tflops": roof.get("peak"),
+                             "avg_launch_ms": roof.get("avg_launch_ms"), "avg_launch_ms_in_schedule": roof.get("avg_launch_ms_in_schedule"), "traffic_bytes": roof.get("traffic"), "mfma_busy": roof.get("mfma_busy")},
+                "f32_mfma_only_ms": (line.get("f32_mfma_only") or {}).get("ms_per_step"),
+                "bf16": {k2: b16.get(k2) for k2 in ("ms_per_step", "images_per_s", "e2e_pages_per_s")} if b16 else None,
+                "e2e_pages_per_s": line.get("e2e_pages_per_s"),
+                "detect_postprocess_pipelined_images_per_s": line.get("detect_postprocess_pipelined_images_per_s"),
+                "postprocess_images_per_s": {"text": line.get("postprocess_images_per_s"), "dense": line.get("postprocess_dense_images_per_s")},
+                "post_threads_2": {k2: v2.get("detect_postprocess_pipelined_images_per_s") for k2, v2 in sw.items() if isinstance(v2, dict) and "detect_postprocess_pipelined_images_per_s" in v2} if sw else None,
+                "post_threads_16_device_chain": {k2: v2.get("detect_postprocess_pipelined_images_per_s") for k2, v2 in ((line.get("post_threads_sweep") or {}).get("16_device_chain") or {}).items()
+                                                 if isinstance(v2, dict) and "detect_postprocess_pipelined_images_per_s" in v2} or None,
+                "extension": line.get("extension"),
+                "rec_crops_per_s": {"b256": line.get("rec_crops_per_s_b256"), "b65536": line.get("rec_crops_per_s_b65536")},
+                "cpu_baseline": {"images_per_s": cb.get("value"), "cores": cb.get("cores"), "kind": cb.get("kind"),
+                                 "one_thread": (cb.get("one_thread") or {}).get("value"),
+                                 "rec_crops_per_s": (cb.get("recognition") or {}).get("value"),
+                                 "postprocess_images_per_s": (cb.get("postprocess") or {}).get("value")},
+                "exchange_ok": line.get("exchange_ok"),
+            }
         emit(line)
         if line.get("exchange_ok") is False and backend == "nccl":
             exit_code = 4   # the line is out, with the error in it; a failed exchange over RCCL must not read as a clean run

@@ -126,3 +126,36 @@ def test_committed_counter_extract_belongs_to_the_committed_kernels():
     k, src, stale = bench.pmc_extract("f32", 32, 640)
     assert stale is False and "winograd43_fused<c64>" in k
     assert bench.in_schedule_ms("winograd43_fused<c64>") > 0.15
+
+
+def test_plain_run_is_the_default_and_steps_are_checked():
+    """A plain command runs the headline steps only; --full opts into the side measurements; --steps sets the timed steps."""
+    import pytest
+    sys.path.insert(0, os.path.dirname(BENCH))
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_fit_the_cap_and_sample_fixed_frames(tmp_path):
+    """--dump-outputs at the default batch (32 x 640 x 640): float32 files, 64 MB at most in all, the probability map whole and
+    the binarized map as a seeded sample of frames - the same frames on every run."""
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(BENCH))
+    import bench
+    prob = np.random.default_rng(3).random((32, 1, 640, 640), dtype=np.float32)
+    outs = {"prob": prob, "bitmap": (prob > 0.6).astype(np.uint8)}
+    info = [bench.dump_outputs(str(tmp_path / d), outs) for d in ("a", "b")]
+    assert info[0] == info[1] and info[0]["prob"]["frames"] == "all"
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64e6
+    p, bm = np.load(tmp_path / "a" / "prob.npy"), np.load(tmp_path / "a" / "bitmap.npy")
+    assert p.dtype == bm.dtype == np.float32
+    assert np.array_equal(p, prob)
+    frames = info[0]["bitmap"]["frames"]
+    assert 0 < len(frames) < 32 and np.array_equal(bm, outs["bitmap"][frames])
+    assert np.array_equal(bm, np.load(tmp_path / "b" / "bitmap.npy"))
