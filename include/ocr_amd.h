@@ -360,6 +360,23 @@ const char* ocr_rec_alphabet(void);
  * GPU and stream; blocking; mem_kind says where the three buffers live.  Exact integers: oracle/ctc_oracle.py. */
 int ocr_ctc_greedy_decode(ocr_rec_t* rec, const float* logits, int n, int t, int c, int blank, int mem_kind, int32_t* labels,
                           int32_t* lengths);
+/* EXTENSION - no counterpart in the reference (see above): CTC prefix beam search returning the beam_width (B) most probable label
+ * sequences of every crop with their log-probabilities.  logits N x T x C f32 (raw logits or log-probabilities: each column goes
+ * through log-softmax first), blank in [0, C).  All arithmetic after the load is f64, with a (+) b = M + log1p(exp(m - M)) for
+ * M = max, m = min (-inf (+) x = x).  Per column: lp = log-softmax; every beam (a distinct prefix l without blanks, lb / lnb = log P
+ * of l ending on a blank / a non-blank, e = its last label or -1, tot = lb (+) lnb; at the start only the empty prefix, lb = 0,
+ * lnb = -inf) offers its stay (lb' = tot + lp[blank], lnb' = lnb + lp[e] when e >= 0 else -inf) and, for every class c != blank, its
+ * extension l + c (lnb' = (c == e ? lb : tot) + lp[c], lb' = -inf).  An extension whose prefix is already a beam is added ((+)) to
+ * that beam's stay lnb' instead of standing on its own.  The first B candidates by score lb' (+) lnb' descending, ties by (beam
+ * rank, class) ascending with a stay as class -1, are the next column's beams in that order.  Without pruning each score is the
+ * exact CTC log P(l | x).  Out, in rank order: labels N x B x T int32 (row: lengths[] classes, then -1), lengths N x B, scores N x B
+ * f64 (tot); slots beyond the distinct prefixes have length -1, score -inf, labels -1.  Limits 1 <= B <= 32, 1 <= T <= 1024,
+ * 1 <= C <= 256; N = 0 does nothing.  OCR_ERR_INVALID for anything outside them, a null pointer, a mem_kind other than
+ * OCR_MEM_HOST / OCR_MEM_DEVICE, and any NaN or +-inf logit (the message names the first such crop; the outputs are then unspecified,
+ * the handle stays usable).  One 256-thread workgroup per crop on the handle's GPU and stream; blocking.  Oracle:
+ * tests/ctc_beam_oracle.py. */
+int ocr_ctc_beam_decode(ocr_rec_t* rec, const float* logits, int n, int t, int c, int blank, int beam_width, int mem_kind,
+                        int32_t* labels, int32_t* lengths, double* scores);
 
 /* ---------------------------------------------------------------------------
  * Multi-GPU exchange.  Frames and crops are independent (eval-mode batch norm), so a batch shards over the GPUs of

@@ -30,6 +30,7 @@ EXPORTS = [
     "ocr_extract_crops", "ocr_evaluate_image", "ocr_combine_results",
     "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_set_stream", "ocr_rec_set_options", "ocr_rec_synchronize",
     "ocr_rec_forward", "ocr_rec_classify_async", "ocr_rec_classify_profile", "ocr_rec_classify", "ocr_rec_alphabet", "ocr_ctc_greedy_decode",
+    "ocr_ctc_beam_decode",
     "ocr_comm_unique_id", "ocr_comm_rccl_version", "ocr_comm_create", "ocr_comm_destroy",
     "ocr_comm_all_gather_polygons", "ocr_comm_all_gather_labels",
 ]
@@ -130,6 +131,8 @@ def lib() -> C.CDLL:
         L.ocr_postproc_default_params.restype = None
         L.ocr_det_post_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.ocr_ctc_greedy_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.ocr_ctc_beam_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
         L.ocr_det_postprocess.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_double), C.POINTER(PostprocParams),
                                           C.POINTER(C.POINTER(Polygons))]
@@ -660,6 +663,23 @@ class Recognizer:
 
     def ctc_greedy_decode_device(self, logits_ptr: int, n: int, t: int, c: int, blank: int, labels_ptr: int, lengths_ptr: int) -> None:
         check(lib().ocr_ctc_greedy_decode(self._h, C.c_void_p(logits_ptr), n, t, c, int(blank), MEM_DEVICE, C.c_void_p(labels_ptr), C.c_void_p(lengths_ptr)))
+
+    def ctc_beam_decode(self, logits: np.ndarray, blank: int, beam_width: int):
+        """EXTENSION (no reference counterpart): CTC prefix beam search over N x T x C f32 logits in host memory -> (labels N x B x T
+        int32 padded with -1, lengths N x B (-1: no such hypothesis), scores N x B f64 log-probabilities), hypotheses in rank order."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        n, t, c = x.shape
+        b = int(beam_width)
+        labels = np.empty((n, max(b, 0), t), np.int32)
+        lengths = np.empty((n, max(b, 0)), np.int32)
+        scores = np.empty((n, max(b, 0)), np.float64)
+        check(lib().ocr_ctc_beam_decode(self._h, _ptr(x), n, t, c, int(blank), b, MEM_HOST, _ptr(labels), _ptr(lengths), _ptr(scores)))
+        return labels, lengths, scores
+
+    def ctc_beam_decode_device(self, logits_ptr: int, n: int, t: int, c: int, blank: int, beam_width: int, labels_ptr: int, lengths_ptr: int,
+                               scores_ptr: int, mem_kind: int = MEM_DEVICE) -> None:
+        check(lib().ocr_ctc_beam_decode(self._h, C.c_void_p(logits_ptr), n, t, c, int(blank), int(beam_width), int(mem_kind),
+                                        C.c_void_p(labels_ptr), C.c_void_p(lengths_ptr), C.c_void_p(scores_ptr)))
 
     def classify_profile(self, crops_ptr: int, n: int, labels_ptr: int = 0, probs_ptr: int = 0):
         """[(kernel, ms, executed flops, bytes)] of one classify pass (device pointers)."""

@@ -47,6 +47,16 @@ class Net:
             out.append("".join(VALUES[int(k)] if 0 <= int(k) < VALUES_COUNT else "?" for k in row[:int(n)]))
         return out
 
+    def ctc_beam_decode(self, logits: np.ndarray, beam_width: int = 8, blank: int = VALUES_COUNT) -> List[List[Tuple[str, float]]]:
+        """EXTENSION (no reference counterpart): CTC prefix beam search of N x T x C logits over the reference's alphabet (classes 0..61 =
+        VALUES, blank default class 62) -> per crop the hypotheses in rank order as (string, log-probability); unused slots left out."""
+        labels, lengths, scores = self._rec.ctc_beam_decode(np.ascontiguousarray(logits, dtype=np.float32), blank, beam_width)
+        out = []
+        for rows, ns, ss in zip(labels, lengths, scores):
+            out.append([("".join(VALUES[int(k)] if 0 <= int(k) < VALUES_COUNT else "?" for k in row[:int(n)]), float(sc))
+                        for row, n, sc in zip(rows, ns, ss) if int(n) >= 0])
+        return out
+
     def close(self):
         self._rec.close()
 

@@ -930,6 +930,46 @@ int ocr_ctc_greedy_decode(ocr_rec_t* rec, const float* logits, int n, int t, int
     OCR_HIP(hipStreamSynchronize(s));
   });
 }
+int ocr_ctc_beam_decode(ocr_rec_t* rec, const float* logits, int n, int t, int c, int blank, int beam_width, int mem_kind, int32_t* labels,
+                        int32_t* lengths, double* scores) {
+  return guard([&] {
+    using namespace ocr;
+    if (!rec || !logits || !labels || !lengths || !scores) fail(OCR_ERR_INVALID, "ctc_beam_decode: null argument");
+    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "ctc_beam_decode: mem_kind %d", mem_kind);
+    if (n < 0 || t < 1 || t > 1024 || c < 1 || c > 256 || blank < 0 || blank >= c || beam_width < 1 || beam_width > 32)
+      fail(OCR_ERR_INVALID, "ctc_beam_decode: N=%d T=%d C=%d blank=%d beam_width=%d (limits: T 1..1024, C 1..256, beam_width 1..32)", n, t, c,
+           blank, beam_width);
+    if (n == 0) return;
+    OCR_HIP(hipSetDevice(rec->impl.device()));
+    hipStream_t s = rec->impl.stream();
+    if (!rec->ctc_bad_crop) OCR_HIP(hipMalloc(reinterpret_cast<void**>(&rec->ctc_bad_crop), sizeof(int32_t)));
+    constexpr int32_t kNone = 0x7F7F7F7F;   // what the byte memset leaves: above every crop index
+    OCR_HIP(hipMemsetAsync(rec->ctc_bad_crop, 0x7F, sizeof(int32_t), s));
+    int32_t bad = kNone;
+    if (mem_kind == OCR_MEM_DEVICE) {   // enqueued on the handle's stream and awaited (the flag decides the return code)
+      launch_ctc_beam(logits, n, t, c, blank, beam_width, labels, lengths, scores, rec->ctc_bad_crop, s);
+      OCR_HIP(hipMemcpyAsync(&bad, rec->ctc_bad_crop, sizeof(bad), hipMemcpyDeviceToHost, s));
+      OCR_HIP(hipStreamSynchronize(s));
+    } else {
+      const size_t in_b = (size_t)n * t * c * 4, lab_b = (size_t)n * beam_width * t * 4, len_b = (size_t)n * beam_width * 4,
+                   sc_b = (size_t)n * beam_width * 8;
+      char* d = nullptr;
+      OCR_HIP(hipMalloc(reinterpret_cast<void**>(&d), align256(in_b) + align256(lab_b) + align256(len_b) + align256(sc_b)));
+      struct Free { char* p; ~Free() { (void)hipFree(p); } } free_d{d};
+      int32_t* d_lab = reinterpret_cast<int32_t*>(d + align256(in_b));
+      int32_t* d_len = reinterpret_cast<int32_t*>(d + align256(in_b) + align256(lab_b));
+      double* d_sc = reinterpret_cast<double*>(d + align256(in_b) + align256(lab_b) + align256(len_b));
+      OCR_HIP(hipMemcpyAsync(d, logits, in_b, hipMemcpyHostToDevice, s));
+      launch_ctc_beam(reinterpret_cast<const float*>(d), n, t, c, blank, beam_width, d_lab, d_len, d_sc, rec->ctc_bad_crop, s);
+      OCR_HIP(hipMemcpyAsync(&bad, rec->ctc_bad_crop, sizeof(bad), hipMemcpyDeviceToHost, s));
+      OCR_HIP(hipMemcpyAsync(labels, d_lab, lab_b, hipMemcpyDeviceToHost, s));
+      OCR_HIP(hipMemcpyAsync(lengths, d_len, len_b, hipMemcpyDeviceToHost, s));
+      OCR_HIP(hipMemcpyAsync(scores, d_sc, sc_b, hipMemcpyDeviceToHost, s));
+      OCR_HIP(hipStreamSynchronize(s));
+    }
+    if (bad != kNone) fail(OCR_ERR_INVALID, "ctc_beam_decode: non-finite logit in crop %d", bad);
+  });
+}
 const char* ocr_rec_alphabet(void) { return "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789"; }
 
 /* ---- multi-GPU exchange (comm.hip) */

@@ -14,7 +14,11 @@ struct ocr_det {
 };
 struct ocr_rec {
   ocr::Recognizer impl;
+  int32_t* ctc_bad_crop = nullptr;   // device int of ocr_ctc_beam_decode: the lowest crop with a non-finite logit (allocated on first use)
   ocr_rec(const void* b, size_t n, int d) : impl(b, n, d) {}
+  ~ocr_rec() {
+    if (ctc_bad_crop) (void)hipFree(ctc_bad_crop);
+  }
 };
 
 namespace ocr {
@@ -44,6 +48,12 @@ int guard(F&& f) {
 }
 
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+// ctc_beam.hip (extension, no reference counterpart): CTC prefix beam search, one workgroup per crop; logits [n][t][c] f32 ->
+// labels [n][beam][t] (-1 padded), lengths [n][beam] (-1: unused slot), scores [n][beam] f64.  *bad_crop_dev is lowered (atomicMin) to
+// the index of every crop holding a non-finite logit; the caller presets it.
+void launch_ctc_beam(const float* logits_dev, int n, int t, int c, int blank, int beam_width, int32_t* labels_dev, int32_t* lengths_dev,
+                     double* scores_dev, int32_t* bad_crop_dev, hipStream_t s);
 
 // the library-owned storage behind an ocr_polygons_t* (released by ocr_polygons_free)
 struct PolygonsOwned {

@@ -1,0 +1,339 @@
+"""CTC prefix beam search - an EXTENSION without a reference counterpart, like the greedy decoder of test_ctc.py.  The oracle
+(tests/ctc_beam_oracle.py, f64 numpy, every extension a candidate) is pinned to exact CTC probabilities: by enumerating every
+alignment of small inputs, and by torch's forward algorithm (ctc_loss).  The kernel (ocr-rs_amd/csrc/ctc_beam.hip, one workgroup
+per crop, pre-selected extensions) is held to the oracle through the C ABI: labels and lengths bit for bit, scores to 1e-9."""
+import math
+
+import numpy as np
+import pytest
+
+from tests import ctc_beam_oracle as O
+
+
+def _torch_logp(lab, x, blank):
+    """-ctc_loss of each hypothesis lab[i] (label tuple) against crop x (T x C) in f64."""
+    import torch
+    T, C = x.shape
+    lp = torch.log_softmax(torch.from_numpy(np.asarray(x, np.float64)), -1)
+    n = len(lab)
+    lp = lp[:, None, :].expand(T, n, C)
+    tg = torch.tensor([k for p in lab for k in p], dtype=torch.long)
+    tl = torch.tensor([len(p) for p in lab], dtype=torch.long)
+    il = torch.full((n,), T, dtype=torch.long)
+    loss = torch.nn.functional.ctc_loss(lp, tg, il, tl, blank=blank, reduction="none", zero_infinity=False)
+    return (-loss).numpy()
+
+
+def _close(a, b, tol):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    with np.errstate(invalid="ignore"):   # -inf - -inf: equal, caught by a == b
+        return bool(np.all((a == b) | (np.abs(a - b) <= tol * np.maximum(1.0, np.abs(b)))))
+
+
+# ---------------------------------------------------------------- the oracle (CPU)
+
+@pytest.mark.parametrize("T,C,blank,seed", [(1, 4, 0, 0), (3, 2, 1, 1), (4, 3, 0, 2), (5, 3, 2, 3), (6, 4, 0, 4), (6, 4, 3, 5), (6, 2, 0, 6)])
+def test_oracle_equals_brute_force(T, C, blank, seed):
+    x = np.random.default_rng(seed).standard_normal((T, C)).astype(np.float32) * 1.5
+    exact = O.brute_force(x, blank)
+    hyps, _ = O.decode_one(x, blank, 10 ** 6)            # wide enough that nothing is pruned
+    got = {p: s for p, s in hyps if s > -math.inf}
+    assert set(got) == set(exact)
+    assert all(abs(got[p] - exact[p]) <= 1e-12 for p in exact)
+    assert len({p for p, _ in hyps}) == len(hyps)        # distinct prefixes
+    s = [v for _, v in hyps]
+    assert s == sorted(s, reverse=True)
+
+
+def _two_label_crop():
+    """T = 32, C = 63: every column peaked (30 against N(0, 1)); columns 9 and 20 hold labels with the blank a close second, so the
+    top four hypotheses (the empty one among them) carry all their mass on alignments a width-16 beam never prunes."""
+    x = np.random.default_rng(7).standard_normal((32, 63)).astype(np.float32)
+    x[:, 62] = 30.0
+    x[9, 62], x[9, 5] = 29.0, 30.0
+    x[20, 62], x[20, 8] = 29.5, 30.0
+    return x
+
+
+def _assert_against_ctc_loss(hyps, scores, x, blank, exact):
+    """scores of the hypotheses hyps vs -ctc_loss: equal (1e-9) for the first `exact`, never above it (a beam sums a subset of the
+    alignments; pruning only loses mass)."""
+    want = _torch_logp(hyps, x, blank)
+    s = np.asarray(scores, np.float64)
+    assert _close(s[:exact], want[:exact], 1e-9), (s[:exact], want[:exact])
+    with np.errstate(invalid="ignore"):
+        assert np.all((s == want) | (s <= want + 1e-9 * np.maximum(1.0, np.abs(want))))
+
+
+def test_oracle_equals_torch_ctc_loss():
+    # nothing pruned (C = 2: at most 17 prefixes at T = 32, B = 32): every hypothesis exact, the empty one included
+    for seed in range(3):
+        for blank in (0, 1):
+            x = np.random.default_rng(seed).standard_normal((32, 2)).astype(np.float32) * 2
+            hyps, _ = O.decode_one(x, blank, 32)
+            assert any(len(p) == 0 for p, _ in hyps)
+            _assert_against_ctc_loss([p for p, _ in hyps], [v for _, v in hyps], x, blank, len(hyps))
+    # T = 32, C = 63, B = 16
+    x = _two_label_crop()
+    hyps, _ = O.decode_one(x, 62, 16)
+    assert [p for p, _ in hyps[:4]] == [(5, 8), (5,), (8,), ()]
+    _assert_against_ctc_loss([p for p, _ in hyps], [v for _, v in hyps], x, 62, 4)
+    rng = np.random.default_rng(7)
+    for _ in range(3):
+        x = rng.standard_normal((32, 63)).astype(np.float32)
+        x[:, 62] += 1.5
+        hyps, _ = O.decode_one(x, 62, 16)
+        _assert_against_ctc_loss([p for p, _ in hyps], [v for _, v in hyps], x, 62, 0)
+
+
+def _peaked(seq, c, hi=6.0, lo=-3.0):
+    x = np.full((len(seq), c), lo, np.float32)
+    for t, k in enumerate(seq):
+        x[t, k] = hi
+    return x
+
+
+def test_oracle_hand_vectors():
+    # "a _ a" decodes to "aa", "a a a" to "a" (blank 0, a = 1)
+    hyps, _ = O.decode_one(_peaked([1, 0, 1], 3), 0, 4)
+    assert hyps[0][0] == (1, 1)
+    hyps, _ = O.decode_one(_peaked([1, 1, 1], 3), 0, 4)
+    assert hyps[0][0] == (1,)
+    # a repeat merges into the stay: T = 2, P("a") = p(aa) + p(a_) + p(_a) exactly
+    x = np.random.default_rng(11).standard_normal((2, 2)).astype(np.float32)
+    lp = np.stack([O.log_softmax(x[t]) for t in range(2)])
+    want = math.log(math.exp(lp[0, 1] + lp[1, 1]) + math.exp(lp[0, 1] + lp[1, 0]) + math.exp(lp[0, 0] + lp[1, 1]))
+    got = dict(O.decode_one(x, 0, 8)[0])
+    assert abs(got[(1,)] - want) <= 1e-14
+    assert got[(1, 1)] == -math.inf                      # "aa" needs a blank between: reachable as a prefix, probability 0
+    # the tie rule: classes 1 and 2 carry identical logits in every column -> identical scores, the lower class first
+    x = np.random.default_rng(12).standard_normal((3, 4)).astype(np.float32)
+    x[:, 2] = x[:, 1]
+    x[:, 1:3] += 2.0
+    hyps, margin = O.decode_one(x, 0, 6)
+    assert margin == 0.0
+    pairs = {p: s for p, s in hyps}
+    for p, s in hyps:
+        q = tuple(2 if k == 1 else 1 if k == 2 else k for k in p)
+        assert pairs.get(q, s) == s                      # the mirror image scores the same ...
+    ranks = {p: i for i, (p, _) in enumerate(hyps)}
+    assert ranks[(1,)] < ranks[(2,)]                     # ... and ranks after its lower-class twin
+    # a parent pruned and re-created in another slot: its child must still absorb the extension (merge by content, not by slot)
+    x = np.random.default_rng(29).standard_normal((8, 3)).astype(np.float32) * 2
+    hyps, _, steps = O.decode_one(x, 0, 3, trace=True)
+    assert (1, 2, 1, 2) in steps[4] and (1, 2, 1) not in steps[4]
+    assert (1, 2, 1) in steps[5] and (1, 2, 1, 2) in steps[5]
+    assert steps[5].index((1, 2, 1)) != steps[3].index((1, 2, 1)) if (1, 2, 1) in steps[3] else True
+    assert all(len(set(s)) == len(s) for s in steps)
+    # C = 1: only the empty prefix, probability 1
+    hyps, _ = O.decode_one(np.zeros((5, 1), np.float32), 0, 4)
+    assert hyps == [((), 0.0)]
+    # T = 1: the blank and every class, scores = the log-softmax
+    x = np.random.default_rng(13).standard_normal((1, 5)).astype(np.float32)
+    hyps, _ = O.decode_one(x, 4, 8)
+    lp = O.log_softmax(x[0])
+    assert sorted(hyps, key=lambda h: (len(h[0]), h[0])) == [((), lp[4])] + [((k,), lp[k]) for k in range(4)]
+    # both blank ends against the exact enumeration
+    for blank in (0, 3):
+        x = np.random.default_rng(14 + blank).standard_normal((4, 4)).astype(np.float32)
+        exact = O.brute_force(x, blank)
+        got = {p: s for p, s in O.decode_one(x, blank, 200)[0] if s > -math.inf}
+        assert set(got) == set(exact) and all(abs(got[p] - exact[p]) <= 1e-12 for p in exact)
+
+
+# ---------------------------------------------------------------- the kernel (GPU)
+
+def _rec():
+    import ocr_rs_amd  # noqa: F401
+    from ocr_rs_amd import capi
+    from ocr_rs_amd import weights as W
+    return capi.Recognizer(W.pack_blob(W.make_rec_weights(0)), 0)
+
+
+def _check(got, want, name, exact_ties=False, min_margin=1e-6):
+    """got: (labels, lengths, scores) of the kernel; want: the oracle's (labels, lengths, scores, margins)."""
+    gl, gn, gs = got
+    wl, wn, ws, wm = want
+    ok = np.ones(len(wm), bool) if exact_ties else wm > min_margin
+    assert ok.mean() >= 0.8, (name, "too many near ties", int((~ok).sum()))
+    assert np.array_equal(gn[ok], wn[ok]), name
+    assert np.array_equal(gl[ok], wl[ok]), name
+    assert _close(gs[ok], ws[ok], 1e-9), (name, float(np.nanmax(np.abs(gs[ok] - ws[ok]))))
+    return ok
+
+
+def _random_cases():
+    rng = np.random.default_rng(2024)
+    x = rng.standard_normal((256, 32, 63)).astype(np.float32)
+    x[:128, :, 62] += 1.5                                # a blank-heavy head
+    yield "256x32x63", x, 62, (1, 2, 8, 16, 32)
+    yield "T=1", rng.standard_normal((64, 1, 63)).astype(np.float32), 62, (1, 8, 32)
+    yield "T=65", rng.standard_normal((16, 65, 20)).astype(np.float32), 19, (4, 16)
+    yield "T=1024", rng.standard_normal((2, 1024, 40)).astype(np.float32) * 2, 0, (8,)
+    yield "C=256", rng.standard_normal((16, 24, 256)).astype(np.float32), 255, (8, 32)
+    yield "blank 0", rng.standard_normal((64, 32, 63)).astype(np.float32), 0, (16,)
+    yield "small C", rng.standard_normal((64, 12, 3)).astype(np.float32), 1, (2, 32)
+
+
+@pytest.mark.gpu
+def test_device_ctc_beam_decode_equals_the_oracle():
+    rec = _rec()
+    for name, x, blank, widths in _random_cases():
+        for b in widths:
+            _check(rec.ctc_beam_decode(x, blank, b), O.ctc_beam_decode(x, blank, b), f"{name} B={b}")
+    # exact ties, decided by the key on both sides: all-equal columns, twin classes, C = 1, the re-created parent
+    eq = np.zeros((3, 6, 5), np.float32)
+    for b in (1, 4, 32):
+        _check(rec.ctc_beam_decode(eq, 0, b), O.ctc_beam_decode(eq, 0, b), f"all-equal B={b}", exact_ties=True)
+        _check(rec.ctc_beam_decode(eq, 4, b), O.ctc_beam_decode(eq, 4, b), f"all-equal blank=C-1 B={b}", exact_ties=True)
+    eq = np.zeros((2, 5, 256), np.float32)                # ties across the whole class range: the tie group runs past the B-th
+    _check(rec.ctc_beam_decode(eq, 7, 32), O.ctc_beam_decode(eq, 7, 32), "all-equal C=256", exact_ties=True)
+    tw = np.random.default_rng(5).standard_normal((8, 10, 6)).astype(np.float32)
+    tw[:, :, 3] = tw[:, :, 2]
+    _check(rec.ctc_beam_decode(tw, 0, 8), O.ctc_beam_decode(tw, 0, 8), "twin classes", exact_ties=True)
+    one = np.random.default_rng(6).standard_normal((4, 9, 1)).astype(np.float32)
+    got = rec.ctc_beam_decode(one, 0, 4)
+    _check(got, O.ctc_beam_decode(one, 0, 4), "C=1", exact_ties=True)
+    assert (got[1][:, 0] == 0).all() and (got[1][:, 1:] == -1).all() and (got[2][:, 1:] == -math.inf).all()
+    rc = (np.random.default_rng(29).standard_normal((8, 3)).astype(np.float32) * 2)[None]
+    _check(rec.ctc_beam_decode(rc, 0, 3), O.ctc_beam_decode(rc, 0, 3), "re-created parent")
+    rec.close()
+
+
+@pytest.mark.gpu
+def test_device_scores_equal_torch_ctc_loss():
+    rec = _rec()
+
+    def hyps_of(labels, lengths, i):
+        return [tuple(labels[i, k, : lengths[i, k]].tolist()) for k in range(labels.shape[1]) if lengths[i, k] >= 0]
+
+    x = np.stack([np.random.default_rng(s).standard_normal((32, 2)).astype(np.float32) * 2 for s in range(4)])
+    for blank in (0, 1):
+        labels, lengths, scores = rec.ctc_beam_decode(x, blank, 32)
+        for i in range(x.shape[0]):
+            h = hyps_of(labels, lengths, i)
+            _assert_against_ctc_loss(h, scores[i, : len(h)], x[i], blank, len(h))
+    x = _two_label_crop()[None]
+    labels, lengths, scores = rec.ctc_beam_decode(x, 62, 16)
+    _assert_against_ctc_loss(hyps_of(labels, lengths, 0), scores[0], x[0], 62, 4)
+    x = np.random.default_rng(8).standard_normal((16, 32, 63)).astype(np.float32)
+    x[:, :, 62] += 1.5
+    labels, lengths, scores = rec.ctc_beam_decode(x, 62, 16)
+    for i in range(x.shape[0]):
+        _assert_against_ctc_loss(hyps_of(labels, lengths, i), scores[i], x[i], 62, 0)
+    rec.close()
+
+
+@pytest.mark.gpu
+def test_device_input_forms():
+    import torch
+    rec = _rec()
+    x = np.random.default_rng(9).standard_normal((256, 32, 63)).astype(np.float32)
+    x[:, :, 62] += 1.5
+    want = O.ctc_beam_decode(x, 62, 8)
+    host = rec.ctc_beam_decode(x, 62, 8)
+    ok = _check(host, want, "host")
+    # log-probabilities in: the same hypotheses
+    lsm = torch.log_softmax(torch.from_numpy(x), -1).numpy()
+    got = rec.ctc_beam_decode(lsm, 62, 8)
+    assert np.array_equal(got[0][ok], host[0][ok]) and np.array_equal(got[1][ok], host[1][ok])
+    assert _close(got[2][ok], host[2][ok], 1e-6)
+    # device memory: the same bits as the host path
+    xd = torch.from_numpy(x).cuda()
+    lab = torch.empty((256, 8, 32), dtype=torch.int32, device="cuda")
+    ln = torch.empty((256, 8), dtype=torch.int32, device="cuda")
+    sc = torch.empty((256, 8), dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    rec.ctc_beam_decode_device(xd.data_ptr(), 256, 32, 63, 62, 8, lab.data_ptr(), ln.data_ptr(), sc.data_ptr())
+    assert np.array_equal(lab.cpu().numpy(), host[0]) and np.array_equal(ln.cpu().numpy(), host[1])
+    assert np.array_equal(sc.cpu().numpy(), host[2])
+    # a handle on a caller-set stream
+    st = torch.cuda.Stream()
+    rec.set_stream(st.cuda_stream)
+    got = rec.ctc_beam_decode(x, 62, 8)
+    assert all(np.array_equal(a, b) for a, b in zip(got, host))
+    rec.set_stream(None)
+    rec.close()
+
+
+@pytest.mark.gpu
+def test_device_peaked_top_hypothesis_equals_greedy():
+    rec = _rec()
+    rng = np.random.default_rng(10)
+    x = rng.standard_normal((128, 32, 63)).astype(np.float32)
+    peak = np.where(rng.random((128, 32)) < 0.4, 62, rng.integers(0, 62, (128, 32)))   # a blank-heavy best path
+    np.put_along_axis(x, peak[:, :, None], 30.0, axis=2)                                   # every column peaked far above the rest
+    gl, gn = rec.ctc_greedy_decode(x, 62)
+    bl, bn, _ = rec.ctc_beam_decode(x, 62, 4)
+    assert np.array_equal(bn[:, 0], gn)
+    assert np.array_equal(bl[:, 0, :], gl)
+    rec.close()
+
+
+@pytest.mark.gpu
+def test_device_invalid_arguments():
+    import ocr_rs_amd  # noqa: F401
+    from ocr_rs_amd import capi
+    rec = _rec()
+    x = np.random.default_rng(11).standard_normal((4, 8, 10)).astype(np.float32)
+    want = O.ctc_beam_decode(x, 9, 4)
+
+    def still_works():
+        _check(rec.ctc_beam_decode(x, 9, 4), want, "after an error")
+
+    bad_calls = [
+        lambda: rec.ctc_beam_decode(x, 9, 0),
+        lambda: rec.ctc_beam_decode(x, 9, 33),
+        lambda: rec.ctc_beam_decode(np.zeros((1, 1025, 4), np.float32), 0, 2),
+        lambda: rec.ctc_beam_decode(np.zeros((1, 4, 257), np.float32), 0, 2),
+        lambda: rec.ctc_beam_decode(x, 10, 4),
+        lambda: rec.ctc_beam_decode(x, -1, 4),
+    ]
+    for call in bad_calls:
+        with pytest.raises(capi.OcrError) as e:
+            call()
+        assert e.value.code == 1
+        still_works()
+    # mem_kind 2
+    lab = np.empty((4, 4, 8), np.int32)
+    ln = np.empty((4, 4), np.int32)
+    sc = np.empty((4, 4), np.float64)
+    code = capi.lib().ocr_ctc_beam_decode(rec._h, x.ctypes.data, 4, 8, 10, 9, 4, 2, lab.ctypes.data, ln.ctypes.data, sc.ctypes.data)
+    assert code == 1
+    still_works()
+    # a NaN and an inf logit: the message names the first such crop
+    for crop, v in ((2, np.nan), (1, np.inf), (3, -np.inf)):
+        y = x.copy()
+        y[crop, 5, 3] = v
+        if crop == 1:
+            y[3, 0, 0] = np.nan
+        with pytest.raises(capi.OcrError) as e:
+            rec.ctc_beam_decode(y, 9, 4)
+        assert e.value.code == 1 and f"crop {crop}" in str(e.value)
+        still_works()
+    # N = 0 is a no-op
+    got = rec.ctc_beam_decode(np.zeros((0, 8, 10), np.float32), 9, 4)
+    assert got[0].shape == (0, 4, 8)
+    rec.close()
+
+
+@pytest.mark.gpu
+def test_reference_named_mirror_returns_ranked_strings():
+    import ocr_rs_amd  # noqa: F401
+    from ocr_rs_amd import char_recognition as cr
+    from ocr_rs_amd import weights as W
+    net = cr.Net(W.pack_blob(W.make_rec_weights(0)), 0)
+    word = [7, 7, 62, 30, 62, 37, 37, 62, 37, 40, 62, 62, 52, 53]        # H e l l o 0 1 with repeats and blanks
+    x = np.full((2, len(word), 63), -2.0, np.float32)
+    for t, k in enumerate(word):
+        x[0, t, k] = 3.0
+    x[1, :, 62] = 1.0                                                     # mostly blank
+    out = net.ctc_beam_decode(x, beam_width=5)
+    assert len(out) == 2 and all(len(o) == 5 for o in out)
+    assert out[0][0][0] == "Hello01" and out[1][0][0] == ""
+    for hyps in out:
+        s = [v for _, v in hyps]
+        assert s == sorted(s, reverse=True) and all(v <= 0.0 for v in s)
+        assert all(ch in cr.VALUES for h, _ in hyps for ch in h)
+    assert len({h for h, _ in out[0]}) == 5
+    net.close()
