@@ -292,6 +292,57 @@ int ocr_det_detect_pipelined_host(ocr_det_t* det, const void* x_host, int x_elem
 int ocr_extract_crops(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind,
                       const ocr_polygons_t* polys, const double* adj_xy, float* crops);
 
+/* Glyph segmentation: detected words -> glyph boxes -> 28 x 28 glyph crops for the single-glyph recogniser (BUILD-DEFINED: the
+ * reference's "Character Segmentation" step, README.md:20-26, was never built).  For every polygon of `polys` (a word), in polygon order:
+ *  1. word box: the ocr_extract_crops box (f32 frame coordinates x0, y0, x1, y1) -> X0 = floor(x0), X1 = ceil(x1), Y0 = floor(y0),
+ *     Y1 = ceil(y1), clamped to the frame, half-open; a box of more than 2^22 pixels is OCR_ERR_INVALID;
+ *  2. q = (int)min(max(v, 0), 255), truncated toward zero, NaN -> 0, of the raw 0..255 f32 frame value v;
+ *  3. Otsu over the 256-bin histogram of q in the box: for t in 0..254 class 0 is q <= t (count W0, int64 sum S0), class 1 the rest
+ *     (W1, S1); t is valid when both classes are non-empty and scores d*d / ((double)W0 * (double)W1), d = (double)(S1*W0 - S0*W1)
+ *     (the product is exact in int64); the highest score wins, ties to the smaller t.  No valid t (a flat box): t = -1, no glyphs;
+ *  4. polarity 0 (auto): ink is the smaller class, dark ink on a tie; 1 forces dark ink (q <= t), 2 light ink (q > t);
+ *  5. mu0 = (float)((double)S0 / W0), mu1 = (float)((double)S1 / W1); bg = the non-ink class's mean, ink = the ink class's mean
+ *     (they differ: mu0 <= t < mu1);
+ *  6. cnt[x] = ink pixels of column x over [Y0, Y1); a column is ink when cnt[x] >= min_col_ink; every maximal run of ink columns is a
+ *     glyph span, left to right; a span with fewer than min_glyph_pixels ink pixels is dropped;
+ *  7. a glyph box is [xs, xe) x [first ink row of the span, last ink row + 1);
+ *  8. at most max_glyphs spans per word are kept; a word that had more is flagged truncated.
+ * Glyph crop (ocr_extract_glyph_crops), 28 x 28 f32, aspect-preserving and centred (as MNIST / EMNIST): s = (float)max(gw, gh) /
+ * (float)glyph_box, cx = (float)(x0 + x1) * 0.5f, sx = (cx + (((float)j + 0.5f) - 14.0f) * s) - 0.5f, sy likewise with row i;
+ * bilinear taps at floor(sx), floor(sy) in ocr_extract_crops's operation order; a tap reads r = (v - bg) / (ink - bg) as
+ * g = r > 0 ? min(r, 1) : 0 (NaN -> 0) inside the glyph box and 0 outside it; ink_high = 0 writes 1 - o.  f32, separately rounded.
+ * Out of scope: touching or kerned glyphs (they stay one glyph), rotated or curved words (the box is axis-aligned and pixels are not
+ * masked by the polygon), lexicons, spaces inside a polygon.  Oracle: tests/glyph_oracle.py; kernels: csrc/glyphs.hip.
+ * Both calls are blocking and run behind everything queued on the detector's stream; no overlap with a pending pipelined forward
+ * (ocr_det_detect_pipelined*) is promised.  frames: N x 1 x H x W f32 in mem_kind memory; polys, adj_xy, params and the glyph block
+ * are host memory; crops (n_glyphs x 784 f32) lives in the same mem_kind as frames.  OCR_ERR_INVALID for a null pointer, a bad mem_kind,
+ * polys->n_images != n, a parameter out of range, a word box over 2^22 pixels, and (crops) a glyph block that does not fit the frames;
+ * the handle stays usable. */
+typedef struct ocr_segment_params {
+  int32_t polarity;          /* 0 auto (default), 1 dark ink, 2 light ink        */
+  int32_t min_col_ink;       /* >= 1, default 1                                   */
+  int32_t min_glyph_pixels;  /* >= 0, default 4                                   */
+  int32_t max_glyphs;        /* 1..256, default 32 (per word)                     */
+  int32_t glyph_box;         /* 1..28, default 20: the glyph's longer side in the crop */
+  int32_t ink_high;          /* 1 (default): ink = 1, background = 0; 0: inverted */
+} ocr_segment_params_t;
+typedef struct ocr_glyphs {
+  int32_t n_images, n_words, n_glyphs;
+  const int32_t* img_offsets;   /* [n_images+1] word range per image (= the polygons')                          */
+  const int32_t* word_offsets;  /* [n_words+1]  glyph range per word                                            */
+  const int32_t* word_info;     /* [4*n_words]  frame, t (-1 flat), polarity used (0 none), truncated (0 / 1)    */
+  const float* word_levels;     /* [2*n_words]  bg, ink (0, 0 for a flat word)                                  */
+  const int32_t* boxes;         /* [4*n_glyphs] x0, y0, x1, y1 frame pixels, half-open                          */
+} ocr_glyphs_t;
+void ocr_segment_default_params(ocr_segment_params_t* p);
+/* params == NULL -> defaults.  *out must be released with ocr_glyphs_free. */
+int ocr_segment_glyphs(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
+                       const double* adj_xy, const ocr_segment_params_t* params, ocr_glyphs_t** out);
+/* glyph_box and ink_high of params (NULL -> defaults) shape the crops; the other fields are checked only. */
+int ocr_extract_glyph_crops(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_glyphs_t* glyphs,
+                            const ocr_segment_params_t* params, float* crops);
+void ocr_glyphs_free(ocr_glyphs_t* g);
+
 /* ---------------------------------------------------------------------------
  * Detection quality metrics (host code; consumers of the polygon lists).  Replaces
  *   evaluate_image(gt, ignore_flags, pred) -> Result<MetricsItem>      metrics.rs:255-380

@@ -27,7 +27,8 @@ EXPORTS = [
     "ocr_det_forward_u8", "ocr_host_alloc", "ocr_host_free", "ocr_det_detect_pipelined_host",
     "ocr_det_forward_async", "ocr_det_synchronize", "ocr_det_forward_profile",
     "ocr_preprocess_image", "ocr_postproc_default_params", "ocr_det_postprocess", "ocr_det_post_stats", "ocr_det_detect_pipelined", "ocr_polygons_free",
-    "ocr_extract_crops", "ocr_evaluate_image", "ocr_combine_results",
+    "ocr_extract_crops", "ocr_segment_default_params", "ocr_segment_glyphs", "ocr_extract_glyph_crops", "ocr_glyphs_free",
+    "ocr_evaluate_image", "ocr_combine_results",
     "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_set_stream", "ocr_rec_set_options", "ocr_rec_synchronize",
     "ocr_rec_forward", "ocr_rec_classify_async", "ocr_rec_classify_profile", "ocr_rec_classify", "ocr_rec_alphabet", "ocr_ctc_greedy_decode",
     "ocr_ctc_beam_decode",
@@ -56,6 +57,17 @@ class Polygons(C.Structure):
     _fields_ = [("n_images", C.c_int32), ("n_polygons", C.c_int32), ("n_vertices", C.c_int32),
                 ("img_offsets", C.POINTER(C.c_int32)), ("poly_offsets", C.POINTER(C.c_int32)),
                 ("xy", C.POINTER(C.c_uint32)), ("scores", C.POINTER(C.c_double))]
+
+
+class SegmentParams(C.Structure):
+    _fields_ = [("polarity", C.c_int32), ("min_col_ink", C.c_int32), ("min_glyph_pixels", C.c_int32), ("max_glyphs", C.c_int32),
+                ("glyph_box", C.c_int32), ("ink_high", C.c_int32)]
+
+
+class Glyphs(C.Structure):
+    _fields_ = [("n_images", C.c_int32), ("n_words", C.c_int32), ("n_glyphs", C.c_int32),
+                ("img_offsets", C.POINTER(C.c_int32)), ("word_offsets", C.POINTER(C.c_int32)), ("word_info", C.POINTER(C.c_int32)),
+                ("word_levels", C.POINTER(C.c_float)), ("boxes", C.POINTER(C.c_int32))]
 
 
 _lib = None
@@ -147,6 +159,14 @@ def lib() -> C.CDLL:
                                           C.POINTER(C.c_double)]
         L.ocr_extract_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Polygons),
                                         C.POINTER(C.c_double), C.c_void_p]
+        L.ocr_segment_default_params.argtypes = [C.POINTER(SegmentParams)]
+        L.ocr_segment_default_params.restype = None
+        L.ocr_segment_glyphs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Polygons),
+                                         C.POINTER(C.c_double), C.POINTER(SegmentParams), C.POINTER(C.POINTER(Glyphs))]
+        L.ocr_extract_glyph_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Glyphs),
+                                              C.POINTER(SegmentParams), C.c_void_p]
+        L.ocr_glyphs_free.argtypes = [C.POINTER(Glyphs)]
+        L.ocr_glyphs_free.restype = None
         L.ocr_rec_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_rec_destroy.argtypes = [C.c_void_p]
         L.ocr_rec_destroy.restype = None
@@ -266,6 +286,65 @@ def default_params(skip_degenerate: bool = False) -> PostprocParams:
     return p
 
 
+def segment_params(**fields) -> SegmentParams:
+    """ocr_segment_default_params with the given fields overridden (polarity, min_col_ink, min_glyph_pixels, max_glyphs, glyph_box,
+    ink_high)."""
+    p = SegmentParams()
+    lib().ocr_segment_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k not in dict(SegmentParams._fields_):
+            raise TypeError(f"unknown segment parameter {k!r}")
+        setattr(p, k, int(v))
+    return p
+
+
+def _as_segment_params(params) -> Optional[SegmentParams]:
+    if params is None or isinstance(params, SegmentParams):
+        return params
+    return segment_params(**params)
+
+
+class GlyphSet:
+    """The arrays of an ocr_glyphs_t, copied into numpy: img_offsets [n_images+1], word_offsets [n_words+1], word_info n_words x 4
+    (frame, t, polarity used, truncated), word_levels n_words x 2 f32 (bg, ink), boxes n_glyphs x 4 (x0, y0, x1, y1, half-open)."""
+
+    def __init__(self, img_offsets, word_offsets, word_info, word_levels, boxes):
+        self.img_offsets = np.ascontiguousarray(img_offsets, dtype=np.int32)
+        self.word_offsets = np.ascontiguousarray(word_offsets, dtype=np.int32)
+        self.word_info = np.ascontiguousarray(word_info, dtype=np.int32).reshape(-1, 4)
+        self.word_levels = np.ascontiguousarray(word_levels, dtype=np.float32).reshape(-1, 2)
+        self.boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+
+    @property
+    def n_images(self) -> int:
+        return len(self.img_offsets) - 1
+
+    @property
+    def n_words(self) -> int:
+        return len(self.word_offsets) - 1
+
+    @property
+    def n_glyphs(self) -> int:
+        return int(self.word_offsets[-1])
+
+    @staticmethod
+    def from_block(gp) -> "GlyphSet":
+        g = gp.contents
+        ni, nw, ng = g.n_images, g.n_words, g.n_glyphs
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return GlyphSet(arr(g.img_offsets, ni + 1, np.int32), arr(g.word_offsets, nw + 1, np.int32), arr(g.word_info, 4 * nw, np.int32),
+                        arr(g.word_levels, 2 * nw, np.float32), arr(g.boxes, 4 * ng, np.int32))
+
+    def block(self) -> Glyphs:
+        """An ocr_glyphs_t viewing these arrays (valid while this object lives)."""
+        def p(a, t):
+            return a.ctypes.data_as(C.POINTER(t))
+        return Glyphs(self.n_images, self.n_words, self.n_glyphs, p(self.img_offsets, C.c_int32), p(self.word_offsets, C.c_int32),
+                      p(self.word_info, C.c_int32), p(self.word_levels, C.c_float), p(self.boxes, C.c_int32))
+
+
 class HostBuffer:
     """Pinned host memory from ocr_host_alloc, viewed as a numpy array (frames / maps of the host-memory entry points)."""
 
@@ -299,6 +378,7 @@ class Detector:
         """options: "key=value;..." engine options of ocr_det_create_with_options (None = defaults)."""
         self._h = C.c_void_p()
         self._blob = weights_blob
+        self.device = device
         if varstore_path is not None:   # `vs.load(file)`: the library reads the tch archive itself
             check(lib().ocr_det_create_from_varstore(os.fsencode(varstore_path), device, C.byref(self._h)))
         else:
@@ -423,6 +503,47 @@ class Detector:
             return polys, scores, npoly
         finally:
             lib().ocr_polygons_free(out)
+
+    def _segment(self, frames_ptr, n: int, h: int, w: int, mem_kind: int, polys, adjust_values, params) -> GlyphSet:
+        st, keep = python_to_polygons(polys, [[0.0] * len(p) for p in polys]) if not isinstance(polys, Polygons) else (polys, None)
+        adj = np.ascontiguousarray(adjust_values, dtype=np.float64).reshape(-1, 2)
+        prm = _as_segment_params(params)
+        out = C.POINTER(Glyphs)()
+        check(lib().ocr_segment_glyphs(self._h, frames_ptr, n, h, w, mem_kind, C.byref(st), adj.ctypes.data_as(C.POINTER(C.c_double)),
+                                       C.byref(prm) if prm is not None else None, C.byref(out)))
+        try:
+            return GlyphSet.from_block(out)
+        finally:
+            lib().ocr_glyphs_free(out)
+
+    def segment_glyphs(self, frames: np.ndarray, polys, adjust_values, params=None) -> GlyphSet:
+        """Glyph segmentation of the words `polys` (per image the polygons in original-image pixels, as postprocess returns them, or a
+        Polygons block) on host frames N x 1 x H x W f32.  params: SegmentParams, a dict of its fields, or None (defaults)."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        n, _, h, w = frames.shape
+        return self._segment(_ptr(frames), n, h, w, MEM_HOST, polys, adjust_values, params)
+
+    def segment_glyphs_device(self, frames_ptr: int, n: int, h: int, w: int, polys, adjust_values, params=None) -> GlyphSet:
+        """The same on device-resident frames (a device pointer to N x 1 x H x W f32)."""
+        return self._segment(C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, polys, adjust_values, params)
+
+    def extract_glyph_crops(self, frames: np.ndarray, glyphs: GlyphSet, params=None) -> np.ndarray:
+        """The 28 x 28 crop of every glyph (host frames) -> n_glyphs x 784 f32."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        n, _, h, w = frames.shape
+        crops = np.empty((glyphs.n_glyphs, 784), np.float32)
+        blk = glyphs.block()
+        prm = _as_segment_params(params)
+        check(lib().ocr_extract_glyph_crops(self._h, _ptr(frames), n, h, w, MEM_HOST, C.byref(blk), C.byref(prm) if prm is not None else None,
+                                            _ptr(crops)))
+        return crops
+
+    def extract_glyph_crops_device(self, frames_ptr: int, n: int, h: int, w: int, glyphs: GlyphSet, crops_ptr: int, params=None) -> None:
+        """The same on device memory: crops_ptr points at n_glyphs x 784 f32."""
+        blk = glyphs.block()
+        prm = _as_segment_params(params)
+        check(lib().ocr_extract_glyph_crops(self._h, C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, C.byref(blk),
+                                            C.byref(prm) if prm is not None else None, C.c_void_p(crops_ptr)))
 
     def debug_stage(self, stage_id: int, shape_nhwc) -> np.ndarray:
         """Test hook: NHWC intermediate of the last forward, returned as NCHW."""
@@ -609,6 +730,7 @@ class Recognizer:
     def __init__(self, weights_blob: Optional[bytes], device: int = 0, varstore_path: Optional[str] = None,
                  options: Optional[str] = None):
         self._h = C.c_void_p()
+        self.device = device
         if varstore_path is not None:
             check(lib().ocr_rec_create_from_varstore(os.fsencode(varstore_path), device, C.byref(self._h)))
         else:

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
@@ -614,6 +615,27 @@ int ocr_preprocess_image(ocr_det_t* det, const uint8_t* rgba, int w, int h, int 
   });
 }
 
+// the box of every polygon in frame coordinates (oracle/crop_oracle.py crop_boxes), shared by the crop and glyph entry points
+static std::vector<ocr::CropBox> crop_boxes(const ocr_polygons_t* polys, const double* adj_xy, int n, int h, int w) {
+  std::vector<ocr::CropBox> boxes;
+  boxes.reserve(polys->n_polygons);
+  for (int b = 0; b < n; ++b) {
+    const double ax = adj_xy[2 * b], ay = adj_xy[2 * b + 1];
+    for (int k = polys->img_offsets[b]; k < polys->img_offsets[b + 1]; ++k) {
+      double mnx = 1e300, mxx = -1e300, mny = 1e300, mxy = -1e300;
+      for (int v = polys->poly_offsets[k]; v < polys->poly_offsets[k + 1]; ++v) {
+        const double x = polys->xy[2 * v] * ax, y = polys->xy[2 * v + 1] * ay;  // back to frame coordinates
+        mnx = std::min(mnx, x); mxx = std::max(mxx, x);
+        mny = std::min(mny, y); mxy = std::max(mxy, y);
+      }
+      const double x0 = std::min(std::max(mnx, 0.0), w - 1.0), x1 = std::min(std::max(mxx + 1.0, x0 + 1.0), (double)w);
+      const double y0 = std::min(std::max(mny, 0.0), h - 1.0), y1 = std::min(std::max(mxy + 1.0, y0 + 1.0), (double)h);
+      boxes.push_back({b, (float)x0, (float)y0, (float)x1, (float)y1});
+    }
+  }
+  return boxes;
+}
+
 int ocr_extract_crops(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
                       const double* adj_xy, float* crops) {
   return guard([&] {
@@ -623,22 +645,7 @@ int ocr_extract_crops(ocr_det_t* det, const float* frames, int n, int h, int w, 
     if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "mem_kind %d", mem_kind);
     const int np = polys->n_polygons;
     if (np == 0) return;
-    std::vector<CropBox> boxes;
-    boxes.reserve(np);
-    for (int b = 0; b < n; ++b) {
-      const double ax = adj_xy[2 * b], ay = adj_xy[2 * b + 1];
-      for (int k = polys->img_offsets[b]; k < polys->img_offsets[b + 1]; ++k) {
-        double mnx = 1e300, mxx = -1e300, mny = 1e300, mxy = -1e300;
-        for (int v = polys->poly_offsets[k]; v < polys->poly_offsets[k + 1]; ++v) {
-          const double x = polys->xy[2 * v] * ax, y = polys->xy[2 * v + 1] * ay;  // back to frame coordinates
-          mnx = std::min(mnx, x); mxx = std::max(mxx, x);
-          mny = std::min(mny, y); mxy = std::max(mxy, y);
-        }
-        const double x0 = std::min(std::max(mnx, 0.0), w - 1.0), x1 = std::min(std::max(mxx + 1.0, x0 + 1.0), (double)w);
-        const double y0 = std::min(std::max(mny, 0.0), h - 1.0), y1 = std::min(std::max(mxy + 1.0, y0 + 1.0), (double)h);
-        boxes.push_back({b, (float)x0, (float)y0, (float)x1, (float)y1});
-      }
-    }
+    const std::vector<CropBox> boxes = crop_boxes(polys, adj_xy, n, h, w);
     OCR_HIP(hipSetDevice(det->impl.device()));
     // while a pipelined forward is in flight on the handle's stream the crops of the batch that just came back are cut on
     // the post-processing stream, beside it: ordered behind everything that was queued on the handle's stream BEFORE that
@@ -665,6 +672,157 @@ int ocr_extract_crops(ocr_det_t* det, const float* frames, int n, int h, int w, 
       OCR_HIP(hipStreamSynchronize(s));
     }
   });
+}
+
+// ---- glyph segmentation (glyphs.hip; rule in include/ocr_amd.h, oracle tests/glyph_oracle.py)
+struct GlyphsOwned {   // the library-owned storage behind an ocr_glyphs_t* (released by ocr_glyphs_free)
+  ocr_glyphs_t view;
+  std::vector<int32_t> img_offsets, word_offsets, word_info, boxes;
+  std::vector<float> word_levels;
+  void finish() {
+    view.n_images = (int32_t)img_offsets.size() - 1;
+    view.n_words = (int32_t)word_offsets.size() - 1;
+    view.n_glyphs = (int32_t)(boxes.size() / 4);
+    view.img_offsets = img_offsets.data();
+    view.word_offsets = word_offsets.data();
+    view.word_info = word_info.data();
+    view.word_levels = word_levels.data();
+    view.boxes = boxes.data();
+  }
+};
+
+static ocr_segment_params_t segment_params(const ocr_segment_params_t* params, const char* who) {
+  ocr_segment_params_t p;
+  ocr_segment_default_params(&p);
+  if (params) p = *params;
+  if (p.polarity < 0 || p.polarity > 2 || p.min_col_ink < 1 || p.min_glyph_pixels < 0 || p.max_glyphs < 1 || p.max_glyphs > 256 ||
+      p.glyph_box < 1 || p.glyph_box > 28 || (p.ink_high != 0 && p.ink_high != 1))
+    ocr::fail(OCR_ERR_INVALID,
+              "%s: params polarity=%d min_col_ink=%d min_glyph_pixels=%d max_glyphs=%d glyph_box=%d ink_high=%d (limits: polarity 0..2, "
+              "min_col_ink >= 1, min_glyph_pixels >= 0, max_glyphs 1..256, glyph_box 1..28, ink_high 0..1)",
+              who, p.polarity, p.min_col_ink, p.min_glyph_pixels, p.max_glyphs, p.glyph_box, p.ink_high);
+  return p;
+}
+
+void ocr_segment_default_params(ocr_segment_params_t* p) {
+  if (!p) return;
+  p->polarity = 0;
+  p->min_col_ink = 1;
+  p->min_glyph_pixels = 4;
+  p->max_glyphs = 32;
+  p->glyph_box = 20;
+  p->ink_high = 1;
+}
+
+int ocr_segment_glyphs(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
+                       const double* adj_xy, const ocr_segment_params_t* params, ocr_glyphs_t** out) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !frames || !polys || !adj_xy || !out) fail(OCR_ERR_INVALID, "segment_glyphs: null argument");
+    *out = nullptr;
+    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "segment_glyphs: mem_kind %d", mem_kind);
+    if (n < 0 || h < 1 || w < 1) fail(OCR_ERR_INVALID, "segment_glyphs: N=%d H=%d W=%d", n, h, w);
+    if (polys->n_images != n) fail(OCR_ERR_INVALID, "segment_glyphs: polygon block holds %d images, frames %d", polys->n_images, n);
+    const ocr_segment_params_t p = segment_params(params, "segment_glyphs");
+    std::vector<WordBox> words;
+    words.reserve(polys->n_polygons);
+    for (const CropBox& c : crop_boxes(polys, adj_xy, n, h, w)) {
+      const int x0 = std::min(std::max((int)std::floor(c.x0), 0), w), x1 = std::min(std::max((int)std::ceil(c.x1), 0), w);
+      const int y0 = std::min(std::max((int)std::floor(c.y0), 0), h), y1 = std::min(std::max((int)std::ceil(c.y1), 0), h);
+      if ((int64_t)(x1 - x0) * (y1 - y0) > (int64_t(1) << 22))
+        fail(OCR_ERR_INVALID, "segment_glyphs: word %zu box of %lld pixels (limit 2^22)", words.size(), (long long)(x1 - x0) * (y1 - y0));
+      words.push_back({c.frame, x0, y0, x1, y1});
+    }
+    std::unique_ptr<GlyphsOwned> g(new GlyphsOwned());
+    g->img_offsets.assign(polys->img_offsets, polys->img_offsets + n + 1);
+    g->word_offsets.push_back(0);
+    const int nw = (int)words.size();
+    if (nw > 0) {
+      const int R = glyph_record_ints(p.max_glyphs);
+      std::vector<int32_t> rec((size_t)nw * R);
+      OCR_HIP(hipSetDevice(det->impl.device()));
+      hipStream_t s = det->impl.stream();
+      const size_t wd_bytes = words.size() * sizeof(WordBox), rec_bytes = rec.size() * 4, fr_bytes = (size_t)n * h * w * 4;
+      char* sc = static_cast<char*>(det->impl.scratch(1, align256(wd_bytes) + align256(rec_bytes)));
+      int32_t* d_rec = reinterpret_cast<int32_t*>(sc + align256(wd_bytes));
+      const float* d_fr = frames;
+      if (mem_kind == OCR_MEM_HOST) {
+        float* f = static_cast<float*>(det->impl.scratch(0, fr_bytes));
+        OCR_HIP(hipMemcpyAsync(f, frames, fr_bytes, hipMemcpyHostToDevice, s));
+        d_fr = f;
+      }
+      OCR_HIP(hipMemcpyAsync(sc, words.data(), wd_bytes, hipMemcpyHostToDevice, s));
+      const GlyphSegParams gp{p.polarity, p.min_col_ink, p.min_glyph_pixels, p.max_glyphs};
+      launch_segment(d_fr, h, w, reinterpret_cast<const WordBox*>(sc), nw, gp, d_rec, s);
+      OCR_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s));
+      OCR_HIP(hipStreamSynchronize(s));
+      g->word_info.resize((size_t)4 * nw);
+      g->word_levels.resize((size_t)2 * nw);
+      for (int i = 0; i < nw; ++i) {   // the per-word records -> CSR
+        const int32_t* r = &rec[(size_t)i * R];
+        std::copy(r, r + 4, &g->word_info[(size_t)4 * i]);
+        std::memcpy(&g->word_levels[(size_t)2 * i], r + 4, 8);
+        if (r[6] < 0 || r[6] > p.max_glyphs) fail(OCR_ERR_INTERNAL, "segment_glyphs: word %d reports %d glyphs", i, r[6]);
+        g->boxes.insert(g->boxes.end(), r + 8, r + 8 + 4 * r[6]);
+        g->word_offsets.push_back((int32_t)(g->boxes.size() / 4));
+      }
+    }
+    g->finish();
+    *out = &g.release()->view;
+  });
+}
+
+int ocr_extract_glyph_crops(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_glyphs_t* glyphs,
+                            const ocr_segment_params_t* params, float* crops) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !frames || !glyphs || (!crops && glyphs->n_glyphs > 0)) fail(OCR_ERR_INVALID, "extract_glyph_crops: null argument");
+    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "extract_glyph_crops: mem_kind %d", mem_kind);
+    if (n < 0 || h < 1 || w < 1) fail(OCR_ERR_INVALID, "extract_glyph_crops: N=%d H=%d W=%d", n, h, w);
+    if (glyphs->n_images != n) fail(OCR_ERR_INVALID, "extract_glyph_crops: glyph block holds %d images, frames %d", glyphs->n_images, n);
+    const ocr_segment_params_t p = segment_params(params, "extract_glyph_crops");
+    const int nw = glyphs->n_words, ng = glyphs->n_glyphs;
+    if (nw < 0 || ng < 0) fail(OCR_ERR_INVALID, "extract_glyph_crops: %d words, %d glyphs", nw, ng);
+    if (ng == 0) return;
+    if (!glyphs->word_offsets || !glyphs->word_info || !glyphs->word_levels || !glyphs->boxes)
+      fail(OCR_ERR_INVALID, "extract_glyph_crops: null array in the glyph block");
+    if (glyphs->word_offsets[0] != 0 || glyphs->word_offsets[nw] != ng) fail(OCR_ERR_INVALID, "extract_glyph_crops: word offsets do not span the glyphs");
+    std::vector<GlyphJob> jobs;
+    jobs.reserve(ng);
+    for (int i = 0; i < nw; ++i) {   // every box is checked against the frames: the kernel reads inside them only
+      const int fr = glyphs->word_info[4 * i];
+      const int k0 = glyphs->word_offsets[i], k1 = glyphs->word_offsets[i + 1];
+      if (k1 < k0 || k1 > ng) fail(OCR_ERR_INVALID, "extract_glyph_crops: word %d glyph range [%d, %d)", i, k0, k1);
+      if (k1 > k0 && (fr < 0 || fr >= n)) fail(OCR_ERR_INVALID, "extract_glyph_crops: word %d on frame %d of %d", i, fr, n);
+      for (int k = k0; k < k1; ++k) {
+        const int32_t* b = glyphs->boxes + 4 * (size_t)k;
+        if (b[0] < 0 || b[1] < 0 || b[2] > w || b[3] > h || b[0] >= b[2] || b[1] >= b[3])
+          fail(OCR_ERR_INVALID, "extract_glyph_crops: glyph %d box (%d, %d, %d, %d) outside the %d x %d frame", k, b[0], b[1], b[2], b[3], w, h);
+        jobs.push_back({fr, b[0], b[1], b[2], b[3], glyphs->word_levels[2 * i], glyphs->word_levels[2 * i + 1]});
+      }
+    }
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    const size_t jb_bytes = jobs.size() * sizeof(GlyphJob), fr_bytes = (size_t)n * h * w * 4, cr_bytes = (size_t)ng * 784 * 4;
+    char* sc = static_cast<char*>(det->impl.scratch(1, align256(jb_bytes)));
+    OCR_HIP(hipMemcpyAsync(sc, jobs.data(), jb_bytes, hipMemcpyHostToDevice, s));
+    if (mem_kind == OCR_MEM_DEVICE) {
+      launch_glyph_crops(frames, h, w, reinterpret_cast<const GlyphJob*>(sc), ng, p.glyph_box, p.ink_high, crops, s);
+      OCR_HIP(hipStreamSynchronize(s));
+    } else {
+      char* fc = static_cast<char*>(det->impl.scratch(0, align256(fr_bytes) + align256(cr_bytes)));
+      OCR_HIP(hipMemcpyAsync(fc, frames, fr_bytes, hipMemcpyHostToDevice, s));
+      float* d_cr = reinterpret_cast<float*>(fc + align256(fr_bytes));
+      launch_glyph_crops(reinterpret_cast<const float*>(fc), h, w, reinterpret_cast<const GlyphJob*>(sc), ng, p.glyph_box, p.ink_high, d_cr, s);
+      OCR_HIP(hipMemcpyAsync(crops, d_cr, cr_bytes, hipMemcpyDeviceToHost, s));
+      OCR_HIP(hipStreamSynchronize(s));
+    }
+  });
+}
+
+void ocr_glyphs_free(ocr_glyphs_t* g) {
+  if (!g) return;
+  delete reinterpret_cast<GlyphsOwned*>(reinterpret_cast<char*>(g) - offsetof(GlyphsOwned, view));
 }
 
 static std::vector<std::vector<ocr::geom::Pt>> csr_polys(const uint32_t* xy, const int32_t* offsets, int n) {

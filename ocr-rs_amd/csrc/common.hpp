@@ -185,6 +185,25 @@ struct CropBox {
 };
 void launch_crops(const float* frames_dev, int H, int W, const CropBox* boxes_dev, int n_boxes, float* crops_dev, hipStream_t s);
 
+// glyph segmentation (glyphs.hip; rule: include/ocr_amd.h ocr_segment_glyphs, tests/glyph_oracle.py).  A word box is integer, half-open
+// and inside the frame; a word's result record is glyph_record_ints(max_glyphs) int32: [0] frame, [1] t, [2] polarity used,
+// [3] truncated, [4] bg and [5] ink (f32 bits), [6] glyph count, [7] unused, then max_glyphs boxes x0, y0, x1, y1.
+struct WordBox {
+  int frame, x0, y0, x1, y1;
+};
+struct GlyphSegParams {
+  int polarity, min_col_ink, min_glyph_pixels, max_glyphs;
+};
+struct GlyphJob {
+  int frame, x0, y0, x1, y1;
+  float bg, ink;
+};
+__host__ __device__ inline int glyph_record_ints(int max_glyphs) { return 8 + 4 * max_glyphs; }
+void launch_segment(const float* frames_dev, int H, int W, const WordBox* words_dev, int n_words, const GlyphSegParams& p,
+                    int32_t* records_dev, hipStream_t s);
+void launch_glyph_crops(const float* frames_dev, int H, int W, const GlyphJob* jobs_dev, int n_glyphs, int glyph_box, int ink_high,
+                        float* crops_dev, hipStream_t s);
+
 // recognition net (rec_net.hip): conv1 + pool + conv2 + pool on the matrix cores -> feat [n][1024]; fc1 runs as a
 // conv_igemm 1x1 GEMM over the whole batch; fc2 + softmax(f64) + top-1 in one kernel
 struct RecWeights {

@@ -6,7 +6,9 @@
 //   text_detection::resnet18(..) -> FuncT, FuncT::forward_t      model.rs:154-156, mod.rs:52-54
 //   text_detection::metrics::get_boxes_and_box_scores            metrics.rs:37-56
 //   char_recognition::Net::{new_, forward_t}, utils::topk        model.rs:13-39, utils.rs:28-43
+//   read_words: detected words -> glyphs -> text, the pipeline's segmentation step (README.md:20-26), which the reference never built
 #pragma once
+#include <array>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -119,10 +121,74 @@ class Net {
     for (int i = 0; i < n; ++i) out.emplace_back(utils::VALUES()[labels[i]], probs[i]);
     return out;
   }
+  ocr_rec_t* handle() const { return h_; }
 
  private:
   ocr_rec_t* h_ = nullptr;
 };
 }  // namespace char_recognition
+
+// One detected word read glyph by glyph: its text (VALUES), the probability of every character, the glyph boxes (x0, y0, x1, y1
+// frame pixels, half-open).
+struct WordReading {
+  std::string text;
+  std::vector<double> probs;
+  std::vector<std::array<int32_t, 4>> boxes;
+};
+// ocr_segment_glyphs -> ocr_extract_glyph_crops -> ocr_rec_classify over host memory: per image, per polygon of `ps`.  frames are the
+// detector's input (N x 1 x H x W, raw 0..255), adjust_values N x 2 as given to get_boxes_and_box_scores; params == nullptr: defaults.
+inline std::vector<std::vector<WordReading>> read_words(const text_detection::FuncT& det_net, const char_recognition::Net& rec_net,
+                                                        const Tensor& frames, const text_detection::metrics::PolygonScores& ps,
+                                                        const std::vector<double>& adjust_values,
+                                                        const ocr_segment_params_t* params = nullptr) {
+  if (frames.c != 1) throw Error(OCR_ERR_INVALID, "expected N x 1 x H x W");
+  if ((int)ps.polygons.size() != frames.n || (int)adjust_values.size() != 2 * frames.n)
+    throw Error(OCR_ERR_INVALID, "polygons / adjust_values do not match the frames");
+  std::vector<int32_t> img_off{0}, poly_off{0};
+  std::vector<uint32_t> xy;
+  std::vector<double> scores;
+  for (const auto& mp : ps.polygons) {
+    for (const auto& p : mp) {
+      for (const auto& v : p) {
+        xy.push_back(v.first);
+        xy.push_back(v.second);
+      }
+      poly_off.push_back((int32_t)(xy.size() / 2));
+      scores.push_back(0.0);
+    }
+    img_off.push_back((int32_t)scores.size());
+  }
+  const ocr_polygons_t polys{frames.n, (int32_t)scores.size(), (int32_t)(xy.size() / 2), img_off.data(), poly_off.data(), xy.data(),
+                             scores.data()};
+  ocr_glyphs_t* g = nullptr;
+  check(ocr_segment_glyphs(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, &polys,
+                           adjust_values.data(), params, &g));
+  struct Free {
+    ocr_glyphs_t* g;
+    ~Free() { ocr_glyphs_free(g); }
+  } free_g{g};
+  const int ng = g->n_glyphs;
+  std::vector<float> crops((size_t)ng * 784);
+  std::vector<int32_t> labels(ng);
+  std::vector<double> probs(ng);
+  if (ng > 0) {
+    check(ocr_extract_glyph_crops(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, g, params,
+                                  crops.data()));
+    check(ocr_rec_classify(rec_net.handle(), crops.data(), ng, labels.data(), probs.data(), OCR_MEM_HOST));
+  }
+  std::vector<std::vector<WordReading>> out(frames.n);
+  for (int b = 0; b < frames.n; ++b) {
+    for (int k = g->img_offsets[b]; k < g->img_offsets[b + 1]; ++k) {
+      WordReading r;
+      for (int j = g->word_offsets[k]; j < g->word_offsets[k + 1]; ++j) {
+        r.text.push_back(utils::VALUES()[labels[j]]);
+        r.probs.push_back(probs[j]);
+        r.boxes.push_back({g->boxes[4 * j], g->boxes[4 * j + 1], g->boxes[4 * j + 2], g->boxes[4 * j + 3]});
+      }
+      out[b].push_back(std::move(r));
+    }
+  }
+  return out;
+}
 
 }  // namespace ocr_rs
