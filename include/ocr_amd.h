@@ -343,6 +343,65 @@ int ocr_extract_glyph_crops(ocr_det_t* det, const float* frames, int n, int h, i
                             const ocr_segment_params_t* params, float* crops);
 void ocr_glyphs_free(ocr_glyphs_t* g);
 
+/* Word strips: every detected word (a polygon, possibly rotated) warped into an upright strip of strip_height rows, all strips of a
+ * batch side by side in one atlas (BUILD-DEFINED, like ocr_segment_glyphs).  Frame coordinates are continuous: frame pixel p spans
+ * [p, p + 1), and a vertex (x, y) is the point (x * adj_x, y * adj_y).
+ * Geometry (ocr_plan_word_strips, host C++, f64, every operation separately rounded, no FMA), for every polygon in polygon order:
+ *  1. hull: the convex hull of the u32 vertices, exact in int64 (Andrew's monotone chain): repeated vertices merged, collinear points
+ *     dropped, counter-clockwise in the x-right / y-up sense (cross((b - a), (c - a)) > 0 at every vertex), starting at the smallest
+ *     (x, y).  A coordinate >= 2^24 or a polygon without vertices is OCR_ERR_INVALID.  m = the hull's vertex count.  Then every hull
+ *     vertex P is mapped to the frame: (x * adj_x, y * adj_y).  m < 3 (one point, repeated copies of one point, two points, all points
+ *     collinear) flags the word degenerate;
+ *  2. rectangle: for every hull edge i (m >= 3: i = 0..m-1, from P_i to P_(i+1) mod m; m = 2: edge 0 only; m = 1: e = (1, 0) from
+ *     P_0), e = P_(i+1) - P_i, ee = ex*ex + ey*ey; for every hull vertex Q, d = Q - P_i, a = dx*ex + dy*ey, b = dy*ex - dx*ey; with the
+ *     ranges [a0, a1], [b0, b1] over Q, area_i = ((a1 - a0) * (b1 - b0)) / ee.  The smallest area wins, ties to the smaller i.  Corner
+ *     (a, b) = (P_ix + (a*ex - b*ey) / ee, P_iy + (a*ey + b*ex) / ee); R0 = (a0, b0), R1 = (a1, b0), R2 = (a1, b1), R3 = (a0, b1);
+ *  3. reading direction u: of +e, -e, +e' = (-ey, ex), -e' the one with the largest x component, ties to the smaller y component (at
+ *     exactly 45 degrees the direction pointing up wins); v = (-u_y, u_x) points down the strip.  TL, TR, BR, BL = R0..R3 rotated
+ *     cyclically: +e: R0 R1 R2 R3; +e': R1 R2 R3 R0; -e: R2 R3 R0 R1; -e': R3 R0 R1 R2.  So words within 45 degrees of horizontal come
+ *     out upright, steeper words come out turned by 90 degrees, and upside-down text reads upside down (none of it is detected);
+ *  4. U = TR - TL, |U| = sqrt(Ux*Ux + Uy*Uy) (IEEE sqrt), likewise V = BL - TL.  |U| < 1: h = (1 - |U|) * 0.5, s = sqrt(ux*ux + uy*uy),
+ *     dx = h * (ux / s), dy = h * (uy / s); TL and BL move by -(dx, dy), TR and BR by +(dx, dy); U, V and their lengths are taken from
+ *     the corners again.  Then the same for |V| < 1 with v (TL, TR by -, BL, BR by +);
+ *  5. Ws = floor((Hs * |U|) / |V| + 0.5) with Hs = strip_height, clamped to [1, max_width]; above max_width flags the word squeezed;
+ *  6. map, each value rounded once from f64 to f32: (ox, oy) = TL, (ux, uy) = U / Ws, (vx, vy) = V / Hs.
+ * Sampling (ocr_extract_word_strips, csrc/strips.hip, f32, separately rounded): word k owns atlas columns [col_offsets[k],
+ * col_offsets[k+1]); atlas pixel (i, j) of word k with c = j - col_offsets[k] samples frame word_info[2k] at
+ * sx = ((ox + ((float)c + 0.5f) * ux) + ((float)i + 0.5f) * vx) - 0.5f, sy likewise with (oy, uy, vy), clamped as fminf(fmaxf(s, 0),
+ * W - 1 or H - 1) (NaN -> 0), bilinear taps in ocr_extract_crops's operation order, the raw 0..255 value (no / 255): the atlas is a valid
+ * frame for ocr_segment_glyphs, with the rectangles of ocr_word_strip_polygons and adj = (1, 1).
+ * Out of scope: curved words, pixels inside the rectangle but outside the polygon (not masked), upside-down or vertical text detection.
+ * Oracle: tests/strip_oracle.py.  ocr_plan_word_strips needs no GPU (det is not taken).  ocr_extract_word_strips is blocking and runs
+ * behind everything queued on the detector's stream, like the glyph calls; frames (N x 1 x H x W f32) and atlas (height x total_width
+ * f32, row-major) live in mem_kind memory, the strips block in host memory.  An empty polygon list gives total_width = 0 and launches
+ * nothing.  OCR_ERR_INVALID for a null pointer, a bad mem_kind, polys->n_images != n (or strips->n_images != n), a bad shape, params out
+ * of range or nonzero reserved fields, an adjust value that is not finite and > 0, a strips block whose offsets or frame indices do not
+ * fit, and an atlas of more than 2^31 elements; the handle stays usable. */
+typedef struct ocr_strip_params {
+  int32_t strip_height;  /* 8..128, default 32 */
+  int32_t max_width;     /* 1..8192, default 1024 (per word) */
+  int32_t reserved[2];   /* must be 0 */
+} ocr_strip_params_t;
+typedef struct ocr_word_strips {
+  int32_t n_images, n_words, height, total_width;
+  const int32_t* img_offsets;  /* [n_images+1] word range per image (= the polygons')        */
+  const int32_t* col_offsets;  /* [n_words+1]  atlas columns per word                       */
+  const int32_t* word_info;    /* [2*n_words]  frame, flags (1 squeezed, 2 degenerate)      */
+  const double* quads;         /* [8*n_words]  TL, TR, BR, BL (x, y) in frame coordinates   */
+  const float* maps;           /* [6*n_words]  ox, oy, ux, uy, vx, vy as the kernel uses them */
+  const double* scores;        /* [n_words]    the source polygons' scores                  */
+} ocr_word_strips_t;
+void ocr_strip_default_params(ocr_strip_params_t* p);
+/* params == NULL -> defaults; h and w are checked only (the rectangle is not clipped to the frame).  *out: ocr_word_strips_free. */
+int ocr_plan_word_strips(const ocr_polygons_t* polys, const double* adj_xy, int n, int h, int w, const ocr_strip_params_t* params,
+                         ocr_word_strips_t** out);
+int ocr_extract_word_strips(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_word_strips_t* strips,
+                            float* atlas);
+/* One image, n_words rectangles (c0, 0), (c1 - 1, 0), (c1 - 1, Hs - 1), (c0, Hs - 1) of the atlas with the source scores: with
+ * adj = (1, 1) the crop box of rectangle k is exactly word k's columns.  *out: ocr_polygons_free. */
+int ocr_word_strip_polygons(const ocr_word_strips_t* strips, ocr_polygons_t** out);
+void ocr_word_strips_free(ocr_word_strips_t* s);
+
 /* ---------------------------------------------------------------------------
  * Detection quality metrics (host code; consumers of the polygon lists).  Replaces
  *   evaluate_image(gt, ignore_flags, pred) -> Result<MetricsItem>      metrics.rs:255-380

@@ -7,6 +7,7 @@ and a gfx950 device and raises OcrError otherwise.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import List, Optional, Sequence, Tuple
@@ -28,6 +29,7 @@ EXPORTS = [
     "ocr_det_forward_async", "ocr_det_synchronize", "ocr_det_forward_profile",
     "ocr_preprocess_image", "ocr_postproc_default_params", "ocr_det_postprocess", "ocr_det_post_stats", "ocr_det_detect_pipelined", "ocr_polygons_free",
     "ocr_extract_crops", "ocr_segment_default_params", "ocr_segment_glyphs", "ocr_extract_glyph_crops", "ocr_glyphs_free",
+    "ocr_strip_default_params", "ocr_plan_word_strips", "ocr_extract_word_strips", "ocr_word_strip_polygons", "ocr_word_strips_free",
     "ocr_evaluate_image", "ocr_combine_results",
     "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_set_stream", "ocr_rec_set_options", "ocr_rec_synchronize",
     "ocr_rec_forward", "ocr_rec_classify_async", "ocr_rec_classify_profile", "ocr_rec_classify", "ocr_rec_alphabet", "ocr_ctc_greedy_decode",
@@ -68,6 +70,16 @@ class Glyphs(C.Structure):
     _fields_ = [("n_images", C.c_int32), ("n_words", C.c_int32), ("n_glyphs", C.c_int32),
                 ("img_offsets", C.POINTER(C.c_int32)), ("word_offsets", C.POINTER(C.c_int32)), ("word_info", C.POINTER(C.c_int32)),
                 ("word_levels", C.POINTER(C.c_float)), ("boxes", C.POINTER(C.c_int32))]
+
+
+class StripParams(C.Structure):
+    _fields_ = [("strip_height", C.c_int32), ("max_width", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class Strips(C.Structure):
+    _fields_ = [("n_images", C.c_int32), ("n_words", C.c_int32), ("height", C.c_int32), ("total_width", C.c_int32),
+                ("img_offsets", C.POINTER(C.c_int32)), ("col_offsets", C.POINTER(C.c_int32)), ("word_info", C.POINTER(C.c_int32)),
+                ("quads", C.POINTER(C.c_double)), ("maps", C.POINTER(C.c_float)), ("scores", C.POINTER(C.c_double))]
 
 
 _lib = None
@@ -167,6 +179,14 @@ def lib() -> C.CDLL:
                                               C.POINTER(SegmentParams), C.c_void_p]
         L.ocr_glyphs_free.argtypes = [C.POINTER(Glyphs)]
         L.ocr_glyphs_free.restype = None
+        L.ocr_strip_default_params.argtypes = [C.POINTER(StripParams)]
+        L.ocr_strip_default_params.restype = None
+        L.ocr_plan_word_strips.argtypes = [C.POINTER(Polygons), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(StripParams),
+                                           C.POINTER(C.POINTER(Strips))]
+        L.ocr_extract_word_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Strips), C.c_void_p]
+        L.ocr_word_strip_polygons.argtypes = [C.POINTER(Strips), C.POINTER(C.POINTER(Polygons))]
+        L.ocr_word_strips_free.argtypes = [C.POINTER(Strips)]
+        L.ocr_word_strips_free.restype = None
         L.ocr_rec_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_rec_destroy.argtypes = [C.c_void_p]
         L.ocr_rec_destroy.restype = None
@@ -343,6 +363,107 @@ class GlyphSet:
             return a.ctypes.data_as(C.POINTER(t))
         return Glyphs(self.n_images, self.n_words, self.n_glyphs, p(self.img_offsets, C.c_int32), p(self.word_offsets, C.c_int32),
                       p(self.word_info, C.c_int32), p(self.word_levels, C.c_float), p(self.boxes, C.c_int32))
+
+
+def strip_params(**fields) -> StripParams:
+    """ocr_strip_default_params with the given fields overridden (strip_height, max_width)."""
+    p = StripParams()
+    lib().ocr_strip_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k == "reserved":
+            p.reserved[0], p.reserved[1] = (int(x) for x in v)
+        elif k in dict(StripParams._fields_):
+            setattr(p, k, int(v))
+        else:
+            raise TypeError(f"unknown strip parameter {k!r}")
+    return p
+
+
+def _as_strip_params(params) -> Optional[StripParams]:
+    if params is None or isinstance(params, StripParams):
+        return params
+    return strip_params(**params)
+
+
+class WordStrips:
+    """The arrays of an ocr_word_strips_t, copied into numpy: img_offsets [n_images+1], col_offsets [n_words+1], word_info n_words x 2
+    (frame, flags: 1 squeezed, 2 degenerate), quads n_words x 8 f64 (TL, TR, BR, BL in frame coordinates), maps n_words x 6 f32 (ox, oy,
+    ux, uy, vx, vy), scores [n_words] f64; height and total_width of the atlas."""
+
+    def __init__(self, img_offsets, col_offsets, word_info, quads, maps, scores, height: int):
+        self.img_offsets = np.ascontiguousarray(img_offsets, dtype=np.int32)
+        self.col_offsets = np.ascontiguousarray(col_offsets, dtype=np.int32)
+        self.word_info = np.ascontiguousarray(word_info, dtype=np.int32).reshape(-1, 2)
+        self.quads = np.ascontiguousarray(quads, dtype=np.float64).reshape(-1, 8)
+        self.maps = np.ascontiguousarray(maps, dtype=np.float32).reshape(-1, 6)
+        self.scores = np.ascontiguousarray(scores, dtype=np.float64)
+        self.height = int(height)
+
+    @property
+    def n_images(self) -> int:
+        return len(self.img_offsets) - 1
+
+    @property
+    def n_words(self) -> int:
+        return len(self.col_offsets) - 1
+
+    @property
+    def total_width(self) -> int:
+        return int(self.col_offsets[-1])
+
+    @staticmethod
+    def from_block(sp) -> "WordStrips":
+        s = sp.contents
+        ni, nw = s.n_images, s.n_words
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return WordStrips(arr(s.img_offsets, ni + 1, np.int32), arr(s.col_offsets, nw + 1, np.int32), arr(s.word_info, 2 * nw, np.int32),
+                          arr(s.quads, 8 * nw, np.float64), arr(s.maps, 6 * nw, np.float32), arr(s.scores, nw, np.float64), s.height)
+
+    def block(self) -> Strips:
+        """An ocr_word_strips_t viewing these arrays (valid while this object lives)."""
+        def p(a, t):
+            return a.ctypes.data_as(C.POINTER(t))
+        return Strips(self.n_images, self.n_words, self.height, self.total_width, p(self.img_offsets, C.c_int32),
+                      p(self.col_offsets, C.c_int32), p(self.word_info, C.c_int32), p(self.quads, C.c_double), p(self.maps, C.c_float),
+                      p(self.scores, C.c_double))
+
+    @contextlib.contextmanager
+    def polygon_block(self):
+        """ocr_word_strip_polygons as the library's own block (a Polygons, valid inside the with statement): the atlas rectangles
+        without a round trip through Python lists."""
+        blk = self.block()
+        out = C.POINTER(Polygons)()
+        check(lib().ocr_word_strip_polygons(C.byref(blk), C.byref(out)))
+        try:
+            yield out.contents
+        finally:
+            lib().ocr_polygons_free(out)
+
+    def polygons(self):
+        """ocr_word_strip_polygons: (one image of n_words atlas rectangles, their scores) as postprocess returns polygons."""
+        with self.polygon_block() as p:
+            return polygons_to_python(C.pointer(p))
+
+
+def plan_word_strips(polys, adjust_values, h: int, w: int, params=None, scores=None) -> WordStrips:
+    """ocr_plan_word_strips (host only, no GPU): polys per image in original-image pixels (or a Polygons block), adjust_values N x 2,
+    the frame size H x W; params: StripParams, a dict of its fields, or None (defaults); scores: per image per polygon, or None (0)."""
+    if isinstance(polys, Polygons):
+        st, n = polys, polys.n_images
+    else:
+        st, keep = python_to_polygons(polys, scores if scores is not None else [[0.0] * len(p) for p in polys])
+        n = len(polys)
+    adj = np.ascontiguousarray(adjust_values, dtype=np.float64).reshape(-1, 2)
+    prm = _as_strip_params(params)
+    out = C.POINTER(Strips)()
+    check(lib().ocr_plan_word_strips(C.byref(st), adj.ctypes.data_as(C.POINTER(C.c_double)), n, h, w,
+                                     C.byref(prm) if prm is not None else None, C.byref(out)))
+    try:
+        return WordStrips.from_block(out)
+    finally:
+        lib().ocr_word_strips_free(out)
 
 
 class HostBuffer:
@@ -544,6 +665,24 @@ class Detector:
         prm = _as_segment_params(params)
         check(lib().ocr_extract_glyph_crops(self._h, C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, C.byref(blk),
                                             C.byref(prm) if prm is not None else None, C.c_void_p(crops_ptr)))
+
+    def plan_word_strips(self, polys, adjust_values, h: int, w: int, params=None, scores=None) -> WordStrips:
+        """capi.plan_word_strips (host geometry; the handle is not used)."""
+        return plan_word_strips(polys, adjust_values, h, w, params, scores)
+
+    def extract_word_strips(self, frames: np.ndarray, strips: WordStrips) -> np.ndarray:
+        """The atlas of `strips` from host frames N x 1 x H x W f32 -> height x total_width f32."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        n, _, h, w = frames.shape
+        atlas = np.empty((strips.height, strips.total_width), np.float32)
+        blk = strips.block()
+        check(lib().ocr_extract_word_strips(self._h, _ptr(frames), n, h, w, MEM_HOST, C.byref(blk), _ptr(atlas) if atlas.size else None))
+        return atlas
+
+    def extract_word_strips_device(self, frames_ptr: int, n: int, h: int, w: int, strips: WordStrips, atlas_ptr: int) -> None:
+        """The same on device memory: atlas_ptr points at height x total_width f32."""
+        blk = strips.block()
+        check(lib().ocr_extract_word_strips(self._h, C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, C.byref(blk), C.c_void_p(atlas_ptr or None)))
 
     def debug_stage(self, stage_id: int, shape_nhwc) -> np.ndarray:
         """Test hook: NHWC intermediate of the last forward, returned as NCHW."""

@@ -204,6 +204,15 @@ void launch_segment(const float* frames_dev, int H, int W, const WordBox* words_
 void launch_glyph_crops(const float* frames_dev, int H, int W, const GlyphJob* jobs_dev, int n_glyphs, int glyph_box, int ink_high,
                         float* crops_dev, hipStream_t s);
 
+// word strips (strips.hip; rule: include/ocr_amd.h ocr_plan_word_strips, tests/strip_oracle.py).  One record per word: its f32 map,
+// frame and first atlas column; col_word[j] is the word that owns atlas column j.
+struct StripWord {
+  float ox, oy, ux, uy, vx, vy;
+  int frame, c0;
+};
+void launch_word_strips(const float* frames_dev, int H, int W, const StripWord* words_dev, const int32_t* col_word_dev, int height,
+                        int total_width, float* atlas_dev, hipStream_t s);
+
 // recognition net (rec_net.hip): conv1 + pool + conv2 + pool on the matrix cores -> feat [n][1024]; fc1 runs as a
 // conv_igemm 1x1 GEMM over the whole batch; fc2 + softmax(f64) + top-1 in one kernel
 struct RecWeights {

@@ -7,6 +7,7 @@
 //   text_detection::metrics::get_boxes_and_box_scores            metrics.rs:37-56
 //   char_recognition::Net::{new_, forward_t}, utils::topk        model.rs:13-39, utils.rs:28-43
 //   read_words: detected words -> glyphs -> text, the pipeline's segmentation step (README.md:20-26), which the reference never built
+//   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words
 #pragma once
 #include <array>
 #include <cstdint>
@@ -184,6 +185,94 @@ inline std::vector<std::vector<WordReading>> read_words(const text_detection::Fu
         r.text.push_back(utils::VALUES()[labels[j]]);
         r.probs.push_back(probs[j]);
         r.boxes.push_back({g->boxes[4 * j], g->boxes[4 * j + 1], g->boxes[4 * j + 2], g->boxes[4 * j + 3]});
+      }
+      out[b].push_back(std::move(r));
+    }
+  }
+  return out;
+}
+
+// One detected word read through its upright strip: text, the probability of every character, and every glyph box mapped back to the
+// frame as a quad (x0, y0), (x1, y0), (x1, y1), (x0, y1) of strip pixels -> TL + cs * (U / Ws) + rs * (V / Hs), f64 frame coordinates.
+struct WordReadingRectified {
+  std::string text;
+  std::vector<double> probs;
+  std::vector<std::array<double, 8>> quads;
+};
+// ocr_plan_word_strips -> ocr_extract_word_strips -> ocr_word_strip_polygons -> ocr_segment_glyphs -> ocr_extract_glyph_crops ->
+// ocr_rec_classify over host memory (the atlas is one frame of the glyph calls, adj = (1, 1)); per image, per polygon of `ps`.
+inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
+    const text_detection::FuncT& det_net, const char_recognition::Net& rec_net, const Tensor& frames,
+    const text_detection::metrics::PolygonScores& ps, const std::vector<double>& adjust_values,
+    const ocr_strip_params_t* strip_params = nullptr, const ocr_segment_params_t* params = nullptr) {
+  if (frames.c != 1) throw Error(OCR_ERR_INVALID, "expected N x 1 x H x W");
+  if ((int)ps.polygons.size() != frames.n || (int)adjust_values.size() != 2 * frames.n)
+    throw Error(OCR_ERR_INVALID, "polygons / adjust_values do not match the frames");
+  std::vector<int32_t> img_off{0}, poly_off{0};
+  std::vector<uint32_t> xy;
+  std::vector<double> scores;
+  for (size_t b = 0; b < ps.polygons.size(); ++b) {
+    for (size_t k = 0; k < ps.polygons[b].size(); ++k) {
+      for (const auto& v : ps.polygons[b][k]) {
+        xy.push_back(v.first);
+        xy.push_back(v.second);
+      }
+      poly_off.push_back((int32_t)(xy.size() / 2));
+      scores.push_back(b < ps.scores.size() && k < ps.scores[b].size() ? ps.scores[b][k] : 0.0);
+    }
+    img_off.push_back((int32_t)scores.size());
+  }
+  const ocr_polygons_t polys{frames.n, (int32_t)scores.size(), (int32_t)(xy.size() / 2), img_off.data(), poly_off.data(), xy.data(),
+                             scores.data()};
+  ocr_word_strips_t* st = nullptr;
+  check(ocr_plan_word_strips(&polys, adjust_values.data(), frames.n, frames.h, frames.w, strip_params, &st));
+  struct FreeStrips {
+    ocr_word_strips_t* s;
+    ~FreeStrips() { ocr_word_strips_free(s); }
+  } free_st{st};
+  std::vector<std::vector<WordReadingRectified>> out(frames.n);
+  if (st->total_width == 0) return out;
+  const int hs = st->height, tw = st->total_width;
+  std::vector<float> atlas((size_t)hs * tw);
+  check(ocr_extract_word_strips(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, st, atlas.data()));
+  ocr_polygons_t* rects = nullptr;
+  check(ocr_word_strip_polygons(st, &rects));
+  struct FreeRects {
+    ocr_polygons_t* p;
+    ~FreeRects() { ocr_polygons_free(p); }
+  } free_r{rects};
+  const double one[2] = {1.0, 1.0};
+  ocr_glyphs_t* g = nullptr;
+  check(ocr_segment_glyphs(det_net.handle(), atlas.data(), 1, hs, tw, OCR_MEM_HOST, rects, one, params, &g));
+  struct FreeGlyphs {
+    ocr_glyphs_t* g;
+    ~FreeGlyphs() { ocr_glyphs_free(g); }
+  } free_g{g};
+  const int ng = g->n_glyphs;
+  std::vector<float> crops((size_t)ng * 784);
+  std::vector<int32_t> labels(ng);
+  std::vector<double> probs(ng);
+  if (ng > 0) {
+    check(ocr_extract_glyph_crops(det_net.handle(), atlas.data(), 1, hs, tw, OCR_MEM_HOST, g, params, crops.data()));
+    check(ocr_rec_classify(rec_net.handle(), crops.data(), ng, labels.data(), probs.data(), OCR_MEM_HOST));
+  }
+  for (int b = 0; b < frames.n; ++b) {
+    for (int k = st->img_offsets[b]; k < st->img_offsets[b + 1]; ++k) {
+      const double* q = st->quads + 8 * (size_t)k;
+      const double c0 = st->col_offsets[k], ws = st->col_offsets[k + 1] - st->col_offsets[k];
+      const double cux = (q[2] - q[0]) / ws, cuy = (q[3] - q[1]) / ws, rvx = (q[6] - q[0]) / hs, rvy = (q[7] - q[1]) / hs;
+      WordReadingRectified r;
+      for (int j = g->word_offsets[k]; j < g->word_offsets[k + 1]; ++j) {
+        r.text.push_back(utils::VALUES()[labels[j]]);
+        r.probs.push_back(probs[j]);
+        const int32_t* bx = g->boxes + 4 * (size_t)j;
+        const double cs[4] = {bx[0] - c0, bx[2] - c0, bx[2] - c0, bx[0] - c0}, rs[4] = {(double)bx[1], (double)bx[1], (double)bx[3], (double)bx[3]};
+        std::array<double, 8> quad;
+        for (int c = 0; c < 4; ++c) {
+          quad[2 * c] = (q[0] + cs[c] * cux) + rs[c] * rvx;
+          quad[2 * c + 1] = (q[1] + cs[c] * cuy) + rs[c] * rvy;
+        }
+        r.quads.push_back(quad);
       }
       out[b].push_back(std::move(r));
     }

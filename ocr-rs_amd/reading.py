@@ -6,7 +6,13 @@ recognition -> output text), composed over the C ABI.
         ocr_extract_glyph_crops   every glyph -> one 28 x 28 crop, on the device         (csrc/glyphs.hip, glyph_crop_kernel)
         ocr_rec_classify          every crop -> label in VALUES (utils.rs:7) and its probability
 
-The segmentation rule is build-defined (the reference never built the step): include/ocr_amd.h, restated in tests/glyph_oracle.py.
+    read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values)
+        ocr_plan_word_strips      every word -> its minimum-area rectangle, upright      (csrc/word_strips.cpp, host)
+        ocr_extract_word_strips   every word -> one strip of the atlas, on the device    (csrc/strips.hip)
+        then the three calls above on the atlas, through the rectangles of ocr_word_strip_polygons
+
+The segmentation and strip rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
+tests/glyph_oracle.py and tests/strip_oracle.py.
 """
 from __future__ import annotations
 
@@ -23,6 +29,24 @@ def _handle(net, kind):
     if not isinstance(h, kind):
         raise TypeError(f"expected a {kind.__name__} or a wrapper with .handle, got {type(net).__name__}")
     return h
+
+
+def _device_frames(det, frames):
+    """frames (numpy or CUDA f32 tensor, N x 1 x H x W) -> a contiguous CUDA tensor, with torch's queued work finished."""
+    import torch
+    if isinstance(frames, np.ndarray):
+        dev = torch.device("cuda", det.device)
+        x = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.float32)).to(dev)
+    else:
+        if not (frames.is_cuda and frames.dtype == torch.float32):
+            raise capi.OcrError(1, "frames: expected a numpy array or a CUDA f32 tensor N x 1 x H x W")
+        dev = frames.device
+        x = frames.contiguous()
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise capi.OcrError(1, f"frames: expected N x 1 x H x W, got {tuple(x.shape)}")
+    # the library's calls run on their handles' streams: whatever torch queued to produce x is finished first
+    torch.cuda.current_stream(dev).synchronize()
+    return x
 
 
 def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None
@@ -81,3 +105,68 @@ def glyph_crops(det_net, frames: np.ndarray, polygon_scores, adjust_values, para
     polys = getattr(polygon_scores, "polygons", polygon_scores)
     glyphs = det.segment_glyphs(frames, polys, adjust_values, params)
     return glyphs, det.extract_glyph_crops(frames, glyphs, params)
+
+
+def strip_glyph_quads(strips: "capi.WordStrips", words: np.ndarray, boxes: np.ndarray) -> np.ndarray:
+    """Glyph boxes (x0, y0, x1, y1, half-open atlas pixels), glyph g of strip words[g] -> k x 4 x 2 f64 frame coordinates of the
+    corners (x0, y0), (x1, y0), (x1, y1), (x0, y1): TL + cs * (U / Ws) + rs * (V / Hs), in that order, with cs = x - col_offsets[word]
+    and U, V the sides of the word's quad."""
+    words = np.asarray(words, np.int64)
+    q = strips.quads[words]
+    c0 = strips.col_offsets[words].astype(np.float64)[:, None]
+    ws = (strips.col_offsets[words + 1] - strips.col_offsets[words]).astype(np.float64)
+    hs = float(strips.height)
+    cux, cuy = ((q[:, 2] - q[:, 0]) / ws)[:, None], ((q[:, 3] - q[:, 1]) / ws)[:, None]
+    rvx, rvy = ((q[:, 6] - q[:, 0]) / hs)[:, None], ((q[:, 7] - q[:, 1]) / hs)[:, None]
+    b = np.asarray(boxes, np.int64).reshape(-1, 4)
+    cs = np.stack([b[:, 0], b[:, 2], b[:, 2], b[:, 0]], axis=1).astype(np.float64) - c0
+    rs = np.stack([b[:, 1], b[:, 1], b[:, 3], b[:, 3]], axis=1).astype(np.float64)
+    return np.stack([(q[:, 0:1] + cs * cux) + rs * rvx, (q[:, 1:2] + cs * cuy) + rs * rvy], axis=2)
+
+
+def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None
+                         ) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+    """Reads every detected word of a batch through its upright strip: rotated words are read along their own axis.
+
+    Arguments as read_words; strip_params: capi.StripParams, a dict of its fields (strip_height, max_width) or None for the defaults;
+    params: the segmentation parameters, applied to the atlas.  Returns per image, per polygon: (text, probability of every character
+    (f64), glyph quads k x 4 x 2 f64: the corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of every glyph box mapped back to frame
+    coordinates, strip_glyph_quads).  A flat word reads as ""."""
+    import torch
+
+    det = _handle(det_net, capi.Detector)
+    rec = _handle(rec_net, capi.Recognizer)
+    polys = getattr(polygon_scores, "polygons", polygon_scores)
+    scores = getattr(polygon_scores, "scores", None)
+    x = _device_frames(det, frames)
+    dev = x.device
+    n, _, h, w = x.shape
+    strips = det.plan_word_strips(polys, adjust_values, h, w, strip_params, scores)
+    if strips.total_width == 0:
+        return [[] for _ in range(n)]
+    atlas = torch.empty((strips.height, strips.total_width), dtype=torch.float32, device=dev)
+    det.extract_word_strips_device(x.data_ptr(), n, h, w, strips, atlas.data_ptr())      # blocking
+    hs, tw = strips.height, strips.total_width
+    with strips.polygon_block() as rects:
+        glyphs = det.segment_glyphs_device(atlas.data_ptr(), 1, hs, tw, rects, [[1.0, 1.0]], params)
+    ng = glyphs.n_glyphs
+    labels = np.zeros(0, np.int32)
+    probs = np.zeros(0, np.float64)
+    if ng:
+        crops = torch.empty((ng, 784), dtype=torch.float32, device=dev)
+        det.extract_glyph_crops_device(atlas.data_ptr(), 1, hs, tw, glyphs, crops.data_ptr(), params)
+        lab = torch.empty(ng, dtype=torch.int32, device=dev)
+        pr = torch.empty(ng, dtype=torch.float64, device=dev)
+        rec.classify_device(crops.data_ptr(), ng, 0, lab.data_ptr(), pr.data_ptr())
+        rec.synchronize()
+        labels, probs = lab.cpu().numpy(), pr.cpu().numpy()
+    quads = strip_glyph_quads(strips, np.repeat(np.arange(glyphs.n_words), np.diff(glyphs.word_offsets)), glyphs.boxes)
+    text = "".join(VALUES[int(c)] for c in labels)
+    out = []
+    for b in range(n):
+        words = []
+        for k in range(int(strips.img_offsets[b]), int(strips.img_offsets[b + 1])):
+            g0, g1 = int(glyphs.word_offsets[k]), int(glyphs.word_offsets[k + 1])
+            words.append((text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy()))
+        out.append(words)
+    return out
