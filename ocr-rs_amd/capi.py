@@ -1055,19 +1055,22 @@ def host_contour_candidates(bitmap01: np.ndarray) -> List[List[Tuple[int, int]]]
     return out
 
 
-def _contours_call(fn, bitmap01, extra_status=False, max_pts=1 << 20, max_polys=1 << 16, tail=()):
+def _contours_call(fn, bitmap01, extra_status=False, max_pts=1 << 20, max_polys=1 << 16, tail=(), extra_out=0):
     bm = np.ascontiguousarray(bitmap01, dtype=np.uint8)
     h, w = bm.shape
     xy = np.empty(2 * max_pts, np.int32)
     cnt = np.empty(max_polys, np.int32)
     n, st = C.c_int(0), C.c_int(0)
+    extra = [C.c_int(0) for _ in range(extra_out)]
     args = [_ptr(bm), h, w, _ptr(xy), _ptr(cnt), max_pts, max_polys, C.byref(n)] + ([C.byref(st)] if extra_status else []) + list(tail)
-    check(fn(*args))
+    check(fn(*args, *[C.byref(e) for e in extra]))
     out, pos = [], 0
     for k in range(n.value):
         c = int(cnt[k])
         out.append([(int(xy[2 * (pos + i)]), int(xy[2 * (pos + i) + 1])) for i in range(c)])
         pos += c
+    if extra_out:
+        return (out, st.value, *(e.value for e in extra))
     return (out, st.value) if extra_status else out
 
 
@@ -1078,12 +1081,26 @@ def host_contours(bitmap01: np.ndarray):
     return _contours_call(L.ocr_test_host_contours, bitmap01)
 
 
-def device_contours(bitmap01: np.ndarray, max_pts: int = 1 << 20, max_polys: int = 1 << 16, sequential: bool = False):
+def device_contours(bitmap01: np.ndarray, max_pts: int = 1 << 20, max_polys: int = 1 << 16, sequential: bool = False, report: bool = False):
     """Raw contours of the device tracer (contours.hip; the parallel form, or the one-wave-per-image form) and its status
-    (0 ok, 1 buffers too small, 2 guard, 3 parallel form: a start outside its list of plausible starts)."""
+    (0 ok, 1 buffers too small, 2 guard, 3 parallel form: a start outside its list of plausible starts).  report: also the form that
+    ran (contour_trace_form: 1 one wave, else the parallel instantiation's LDS words) and the parallel form's count of plausible
+    starts K (0 for the one-wave form) - (contours, status, form, K)."""
     L = test_lib()
-    L.ocr_test_device_contours.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
-    return _contours_call(L.ocr_test_device_contours, bitmap01, True, max_pts, max_polys, tail=(int(sequential),))
+    L.ocr_test_device_contours.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    r = _contours_call(L.ocr_test_device_contours, bitmap01, True, max_pts, max_polys, tail=(int(sequential),), extra_out=2)
+    return r if report else r[:2]
+
+
+def contour_trace_form(h: int, w: int, sequential: bool = False, have_spec: bool = True) -> int:
+    """The form the device tracer runs for an h x w map (contour_trace_form; needs no GPU): 0 the map does not fit, 1 the one-wave
+    form, else the LDS words of the parallel form's instantiation (14336, 22528 or 35840)."""
+    L = test_lib()
+    L.ocr_test_contour_trace_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    f = C.c_int(-1)
+    check(L.ocr_test_contour_trace_form(h, w, int(sequential), int(have_spec), C.byref(f)))
+    return f.value
 
 
 def device_candidates(contours, h: int, w: int, max_pts: int = 1 << 18, max_polys: int = 1 << 14):

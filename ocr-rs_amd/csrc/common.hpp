@@ -164,8 +164,12 @@ size_t binarize_pack_words(size_t px_per_image);
 void launch_binarize_pack(const float* prob, uint32_t* bits, float thresh, int n_images, size_t px_per_image, hipStream_t s);
 // contours.hip: Suzuki-Abe border following of the packed bit images on the device, one wave per image (maps whose bit image and
 // two label planes fit a CU's LDS: contour_trace_fits).  pts [n][cap] (y << 16 | x), starts [n][maxc + 1], hdr [n][4] =
-// {contours, points, status, 0}; pts_packed / lens_packed: the status-0 images' points and contour lengths, densely in image order
+// {contours, points, status, plausible starts (parallel form) or 0}; pts_packed / lens_packed: the status-0 images' points and contour
+// lengths, densely in image order
 bool contour_trace_fits(int h, int w);
+// the form launch_contour_trace runs for an h x w map: 0 the map does not fit, 1 the one-wave form, else the LDS words LW of the
+// parallel form's instantiation (14336, 22528 or 35840: the smallest that holds the map)
+int contour_trace_form(int h, int w, bool sequential, bool have_spec);
 // spec: contour_spec_bytes(n) bytes of scratch for the parallel form (plausible starts walked by a lane each, the raster scan only
 // replays the label tests); sequential != 0 or spec == nullptr or h > 1024: the one-wave-per-image form
 size_t contour_spec_bytes(int n);

@@ -547,28 +547,39 @@ bool contour_trace_fits(int h, int w) { return parallel_fits(h, w) || sequential
 
 size_t contour_spec_bytes(int n) { return (size_t)n * (3 * (size_t)kMaxStarts * 4 + (size_t)kContourPool * 4); }
 
+// the parallel form unless the one-wave form was asked for (and the map fits its three planes), or only the one-wave form takes the shape;
+// the parallel form in the smallest LDS footprint that holds the map: 56 KB up to 640 x 640, 88 KB up to 800 x 800, else the CU's
+int contour_trace_form(int h, int w, bool sequential, bool have_spec) {
+  if (have_spec && parallel_fits(h, w) && !(sequential && sequential_fits(h, w))) {
+    const size_t need = parallel_words(h, w);
+    return need <= 14336 ? 14336 : need <= 22528 ? 22528 : kParWords;
+  }
+  return sequential_fits(h, w) ? 1 : 0;
+}
+
 void launch_contour_trace(const uint32_t* bits, size_t words_per_image, int n, int h, int w, uint32_t* pts, int cap, int* starts, int maxc, int* hdr,
                           uint32_t* pts_packed, int* lens_packed, void* spec, int sequential, hipStream_t s) {
   if (n <= 0) return;
   if (!contour_trace_fits(h, w)) fail(OCR_ERR_INTERNAL, "contour_trace: a %dx%d map does not fit a CU's LDS", h, w);
   if (cap <= 0 || maxc <= 0 || words_per_image > 0x7fffffffu) fail(OCR_ERR_INTERNAL, "contour_trace: bad capacities");
   if (words_per_image < ((size_t)h * w + 31) / 32) fail(OCR_ERR_INTERNAL, "contour_trace: %zu words per image for a %dx%d map", words_per_image, h, w);
-  // the parallel form unless the one-wave form was asked for (and the map fits its three planes), or only the one-wave form takes the shape
-  const bool par = spec && parallel_fits(h, w) && !(sequential && sequential_fits(h, w));
-  if (!par) {
-    if (!sequential_fits(h, w)) fail(OCR_ERR_INTERNAL, "contour_trace: a %dx%d map needs the parallel form's scratch", h, w);
-    hipLaunchKernelGGL(contour_trace_kernel, dim3((unsigned)n), dim3(64), 0, s, bits, (int)words_per_image, h, w, pts, cap, starts, maxc, hdr);
-  } else {
-    int* spec_i = static_cast<int*>(spec);
-    uint32_t* pool = reinterpret_cast<uint32_t*>(spec_i + (size_t)n * 3 * kMaxStarts);
-    // the smallest LDS footprint that holds the map: 56 KB up to 640 x 640, 88 KB up to 800 x 800, else the CU's
-    const size_t need = parallel_words(h, w);
-    if (need <= 14336)
+  int* spec_i = static_cast<int*>(spec);
+  uint32_t* pool = spec ? reinterpret_cast<uint32_t*>(spec_i + (size_t)n * 3 * kMaxStarts) : nullptr;
+  switch (contour_trace_form(h, w, sequential != 0, spec != nullptr)) {
+    case 1:
+      hipLaunchKernelGGL(contour_trace_kernel, dim3((unsigned)n), dim3(64), 0, s, bits, (int)words_per_image, h, w, pts, cap, starts, maxc, hdr);
+      break;
+    case 14336:
       hipLaunchKernelGGL(contour_parallel_kernel<14336>, dim3((unsigned)n), dim3(1024), 0, s, bits, (int)words_per_image, h, w, pts, cap, starts, maxc, hdr, spec_i, pool, kContourPool);
-    else if (need <= 22528)
+      break;
+    case 22528:
       hipLaunchKernelGGL(contour_parallel_kernel<22528>, dim3((unsigned)n), dim3(1024), 0, s, bits, (int)words_per_image, h, w, pts, cap, starts, maxc, hdr, spec_i, pool, kContourPool);
-    else
+      break;
+    case kParWords:
       hipLaunchKernelGGL(contour_parallel_kernel<kParWords>, dim3((unsigned)n), dim3(1024), 0, s, bits, (int)words_per_image, h, w, pts, cap, starts, maxc, hdr, spec_i, pool, kContourPool);
+      break;
+    default:
+      fail(OCR_ERR_INTERNAL, "contour_trace: a %dx%d map needs the parallel form's scratch", h, w);
   }
   OCR_HIP(hipGetLastError());
   hipLaunchKernelGGL(contour_compact_kernel, dim3((unsigned)n), dim3(256), 0, s, hdr, pts, cap, starts, maxc, pts_packed, lens_packed);

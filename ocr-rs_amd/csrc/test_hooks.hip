@@ -40,12 +40,18 @@ int ocr_test_contour_candidates(const uint8_t* bitmap01, int h, int w, int32_t* 
     *n_polys = np;
   });
 }
+// the form launch_contour_trace runs for an h x w map (contour_trace_form: 0 does not fit, 1 one wave, else the parallel form's LDS words)
+int ocr_test_contour_trace_form(int h, int w, int sequential, int have_spec, int* form) {
+  return guard([&] { *form = ocr::contour_trace_form(h, w, sequential != 0, have_spec != 0); });
+}
 // the device tracer (contours.hip) on one 0/1 bitmap: raw contours (not the Douglas-Peucker candidates); status = the kernel's
 // (0 ok, 1 buffers too small, 2 iteration guard, 3 parallel form only: a start outside its list).  max_pts / max_polys double as the kernel's capacities.
+// form = the form that ran (contour_trace_form), starts_k = the parallel form's count of plausible starts (header word 3; 0 for the one-wave form)
 int ocr_test_device_contours(const uint8_t* bitmap01, int h, int w, int32_t* xy_out, int32_t* counts_out, int max_pts, int max_polys,
-                             int* n_polys, int* status, int sequential) {
+                             int* n_polys, int* status, int sequential, int* form, int* starts_k) {
   return guard([&] {
-    if (!ocr::contour_trace_fits(h, w)) ocr::fail(OCR_ERR_INVALID, "device contours: %dx%d does not fit", h, w);
+    *form = ocr::contour_trace_form(h, w, sequential != 0, true);
+    if (!*form) ocr::fail(OCR_ERR_INVALID, "device contours: %dx%d does not fit", h, w);
     const size_t npx = (size_t)h * w, wpi = ocr::binarize_pack_words(npx);
     std::vector<uint32_t> bits(wpi, 0u);
     for (size_t i = 0; i < npx; ++i)
@@ -65,6 +71,7 @@ int ocr_test_device_contours(const uint8_t* bitmap01, int h, int w, int32_t* xy_
     int hdr[4];
     OCR_HIP(hipMemcpy(hdr, d_hdr, 16, hipMemcpyDeviceToHost));
     *status = hdr[2];
+    *starts_k = hdr[3];
     *n_polys = 0;
     if (hdr[2] == 0) {
       std::vector<uint32_t> pts((size_t)hdr[1]);

@@ -70,7 +70,7 @@ def test_device_contours_equal_host_contours(case, sequential):
         return
     if status == 1 and not sequential:
         # ... or its speculative walks outgrew their pool: noise, where thousands of plausible starts sit on one giant border
-        assert name.startswith("noise") or name.startswith("blobs ") or name in ("checkerboard", "diagonals", "smooth blobs"), name
+        assert name.startswith("noise") or name in ("checkerboard", "diagonals", "smooth blobs"), name
         return
     assert status == 0
     assert len(got) == len(want), (len(got), len(want))
@@ -89,7 +89,7 @@ def test_parallel_form_takes_the_usual_maps():
     """... and does not give up (status 3) on maps without foreground in column 0: noise, blobs, rings, text-like and dense maps."""
     taken = 0
     for name, bm in CASES:
-        if bm[:, 0].any() or bm.shape[0] > 1024 or name.startswith("noise") or name.startswith("blobs ") or name in ("checkerboard", "diagonals"):
+        if bm[:, 0].any() or bm.shape[0] > 1024 or name.startswith("noise") or name in ("checkerboard", "diagonals"):
             continue
         _, status = capi.device_contours(bm)
         assert status == 0, name
