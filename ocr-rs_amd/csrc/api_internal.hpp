@@ -1,5 +1,5 @@
-// Shared by the translation units that implement the extern "C" surface (api.hip, comm entry points) and by the
-// test-hook library (test_hooks.hip -> libocr_amd_test.so, which links against libocr_amd.so).
+// Shared by the translation units that implement the extern "C" surface (api.hip, postprocess.hip, comm entry points) and by the
+// test-hook library (test_hooks.hip -> libocr_amd_test.so, built from the same objects as libocr_amd.so).
 #pragma once
 #include <memory>
 #include <string>
@@ -48,6 +48,19 @@ int guard(F&& f) {
 }
 
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+// Running 256-byte-aligned offsets inside one block (a scratch slot, the pinned buffer, a device allocation): take() returns where
+// the next piece starts, `end` is the size of what has been taken.  Kernels' launchers that carve a block themselves (candidates.hip)
+// use the same chain, so both sides agree on where every piece lives.
+struct Carve {
+  size_t end = 0;
+  size_t take(size_t bytes) {
+    const size_t o = end;
+    end = o + align256(bytes);
+    return o;
+  }
+};
+template <typename T>
+T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
 
 // ctc_beam.hip (extension, no reference counterpart): CTC prefix beam search, one workgroup per crop; logits [n][t][c] f32 ->
 // labels [n][beam][t] (-1 padded), lengths [n][beam] (-1: unused slot), scores [n][beam] f64.  *bad_crop_dev is lowered (atomicMin) to

@@ -12,12 +12,11 @@
 //     numerator; the FIRST index attaining the maximum wins (the sequential scan's strict >): per-lane strided scans keep their first
 //     maximum, the cross-lane reduction prefers the smaller index among equal distances; split while dmax > epsilon.  The recursion
 //     is an explicit stack (smaller half first: depth <= 16), the result "all kept indices in increasing order", as on the host.
-#include "common.hpp"
+#include "api_internal.hpp"   // Carve: the host sizes the scratch with the chain that launch_candidates carves it with
 
 namespace ocr {
 namespace {
 
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 constexpr int kDpWaves = 4;
 constexpr int kKeepWords = 1024;   // contour points per wave: 32 768 (the tracer's per-image capacity)
 
@@ -258,7 +257,7 @@ __global__ __launch_bounds__(256) void cand_fill_kernel(const int* __restrict__ 
       mny = min(mny, y);
       mxy = max(mxy, y);
     }
-    // the reference clamps x by size[-2] (= H) and y by size[-1] (= W): metrics.rs:151-166 (api.hip refuses non-square maps where that matters)
+    // the reference clamps x by size[-2] (= H) and y by size[-1] (= W): metrics.rs:151-166 (postprocess.hip refuses non-square maps where that matters)
     mnx = min(max(mnx, 0), H - 1);
     mxx = min(max(mxx, 0), H - 1);
     mny = min(max(mny, 0), W - 1);
@@ -269,19 +268,22 @@ __global__ __launch_bounds__(256) void cand_fill_kernel(const int* __restrict__ 
 
 }  // namespace
 
-size_t candidates_scratch_bytes(int n, int cap, int maxc) { return align256((size_t)n * cap * 4) + 3 * align256((size_t)n * maxc * 4) + 256; }
+// cand_pts [n][cap], then cand_len, cand_idx, cand_off [n][maxc] each: the chain launch_candidates carves
+size_t candidates_scratch_bytes(int n, int cap, int maxc) {
+  Carve c;
+  c.take((size_t)n * cap * 4);
+  for (int i = 0; i < 3; ++i) c.take((size_t)n * maxc * 4);
+  return c.end + 256;
+}
 
 void launch_candidates(const int* hdr, const uint32_t* pts, int cap, const int* starts, int maxc, int n, int h, int w, void* scratch, BoxScoreJob* jobs,
                        int max_jobs, int32_t* pts_xy, int max_pts, int* tot, int* totals, hipStream_t s) {
   if (n <= 0) return;
-  char* base = static_cast<char*>(scratch);
-  uint32_t* cand_pts = reinterpret_cast<uint32_t*>(base);
-  base += align256((size_t)n * cap * 4);
-  int* cand_len = reinterpret_cast<int*>(base);
-  base += align256((size_t)n * maxc * 4);
-  int* cand_idx = reinterpret_cast<int*>(base);
-  base += align256((size_t)n * maxc * 4);
-  int* cand_off = reinterpret_cast<int*>(base);
+  Carve c;
+  uint32_t* cand_pts = at<uint32_t>(scratch, c.take((size_t)n * cap * 4));
+  int* cand_len = at<int>(scratch, c.take((size_t)n * maxc * 4));
+  int* cand_idx = at<int>(scratch, c.take((size_t)n * maxc * 4));
+  int* cand_off = at<int>(scratch, c.take((size_t)n * maxc * 4));
   const int wgs = 8;   // 32 waves per image: a dense page's 60 - 130 contours in two to four rounds
   hipLaunchKernelGGL(dp_kernel, dim3((unsigned)(n * wgs)), dim3(64 * kDpWaves), 0, s, hdr, pts, cap, starts, maxc, cand_pts, cand_len, wgs);
   OCR_HIP(hipGetLastError());

@@ -126,9 +126,9 @@ class Detector {
     ocr_postproc_params_t params{};
     hipEvent_t event = nullptr;
     // device_contours: the bit images and contours of this batch were requested on the post-processing stream when the batch was
-    // queued (scratch slot 3, layout of api.hip::ContourBuffers): the call that brings the polygons back only reads them
+    // queued (scratch slot 3, layout of postprocess.hip::ContourBuffers): the call that brings the polygons back only reads them
     bool pretraced = false;
-    bool prechained = false;   // ... and so were Douglas-Peucker, box scores and unclip behind them (scratch slot 4, api.hip::ChainBuffers)
+    bool prechained = false;   // ... and so were Douglas-Peucker, box scores and unclip behind them (scratch slot 4, postprocess.hip::ChainBuffers)
   };
   bool has_pending() const { return pending_.valid; }
   Pending& pending() { return pending_; }

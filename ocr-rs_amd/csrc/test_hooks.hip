@@ -8,7 +8,6 @@
 #include "api_internal.hpp"
 
 using ocr::guard;
-using ocr::align256;
 namespace ocr { void winograd43_set_debug(int d); }
 #ifdef W43_STAMPS
 namespace ocr { void winograd43_read_stamps(long long* out); void winograd43_x3_read_stamps(long long* out); }
@@ -221,15 +220,16 @@ int ocr_test_box_scores(ocr_det_t* det, const float* prob_host, int h, int w, co
       jobs.push_back({0, pos, counts[k], mnx, mny, mxx - mnx + 1, mxy - mny + 1});
       pos += counts[k];
     }
-    const size_t o_jobs = align256((size_t)h * w * 4), o_pts = o_jobs + align256(jobs.size() * sizeof(BoxScoreJob));
-    const size_t o_sum = o_pts + align256((size_t)pos * 8), o_cnt = o_sum + align256((size_t)n_polys * 8);
-    char* sc = static_cast<char*>(det->impl.scratch(0, o_cnt + align256((size_t)n_polys * 8)));
+    Carve c;   // the map first
+    c.take((size_t)h * w * 4);
+    const size_t o_jobs = c.take(jobs.size() * sizeof(BoxScoreJob)), o_pts = c.take((size_t)pos * 8), o_sum = c.take((size_t)n_polys * 8),
+                 o_cnt = c.take((size_t)n_polys * 8);
+    char* sc = static_cast<char*>(det->impl.scratch(0, c.end));
     OCR_HIP(hipMemcpyAsync(sc, prob_host, (size_t)h * w * 4, hipMemcpyHostToDevice, s));
     OCR_HIP(hipMemcpyAsync(sc + o_jobs, jobs.data(), jobs.size() * sizeof(BoxScoreJob), hipMemcpyHostToDevice, s));
     OCR_HIP(hipMemcpyAsync(sc + o_pts, xy, (size_t)pos * 8, hipMemcpyHostToDevice, s));
-    launch_box_scores(reinterpret_cast<const float*>(sc), h, w, reinterpret_cast<const BoxScoreJob*>(sc + o_jobs),
-                      reinterpret_cast<const int32_t*>(sc + o_pts), n_polys, reinterpret_cast<double*>(sc + o_sum),
-                      reinterpret_cast<double*>(sc + o_cnt), s);
+    launch_box_scores(at<const float>(sc, 0), h, w, at<const BoxScoreJob>(sc, o_jobs), at<const int32_t>(sc, o_pts), n_polys, at<double>(sc, o_sum),
+                      at<double>(sc, o_cnt), s);
     OCR_HIP(hipMemcpyAsync(sums_out, sc + o_sum, (size_t)n_polys * 8, hipMemcpyDeviceToHost, s));
     OCR_HIP(hipMemcpyAsync(counts_out, sc + o_cnt, (size_t)n_polys * 8, hipMemcpyDeviceToHost, s));
     OCR_HIP(hipStreamSynchronize(s));
