@@ -343,6 +343,45 @@ int ocr_extract_glyph_crops(ocr_det_t* det, const float* frames, int n, int h, i
                             const ocr_segment_params_t* params, float* crops);
 void ocr_glyphs_free(ocr_glyphs_t* g);
 
+/* Glyph segmentation by connected components (BUILD-DEFINED, like ocr_segment_glyphs): a second entry point beside the column rule,
+ * for words whose letters are kerned - their column ranges overlap, or a speck bridges a gap, without the letters touching.  For
+ * every polygon of `polys` (a word), in polygon order:
+ *  1. steps 1-5 of ocr_segment_glyphs unchanged: word box [X0, X1) x [Y0, Y1), quantise, Otsu, polarity, levels; a flat word (t = -1)
+ *     gives no glyphs;
+ *  2. a run is a maximal horizontal sequence of ink pixels in one row of the box, [a0, a1) in columns;
+ *  3. a component is an 8-connected set of ink pixels: runs [a0, a1) and [b0, b1) of adjacent rows are connected when a0 <= b1 &&
+ *     b0 <= a1;
+ *  4. a component carries its half-open bounding box, its pixel count s and its anchor, the smallest raster index
+ *     (y - Y0) * (X1 - X0) + (x - X0) of its pixels;
+ *  5. limits: a word of more than 8192 runs, or of more than 1024 components before any filter, is segmented by the column rule
+ *     (steps 6-8 of ocr_segment_glyphs, with `params`) and flagged 2; this is not an error;
+ *  6. components with s < min_glyph_pixels are dropped;
+ *  7. the rest is sorted by (x0, anchor) ascending;
+ *  8. grouping walk: the first component opens a group; every next component c is compared with the current (last) group a, over the
+ *     group's accumulated x range: ov = min(a.x1, c.x1) - max(a.x0, c.x0), nar = min(a.x1 - a.x0, c.x1 - c.x0); when
+ *     merge_overlap_pct > 0 && ov > 0 && ov * 100 >= nar * merge_overlap_pct, c joins a (the boxes are united, the counts added),
+ *     otherwise c opens a new group.  This keeps i-dots, accents and broken strokes with their letter;
+ *  9. groups with (y1 - y0) * 100 < min_height_pct * (Y1 - Y0) are dropped;
+ * 10. the first max_glyphs groups are kept; a word that had more is flagged 1 (truncated);
+ * 11. a glyph box is the group's box in frame pixels; the boxes of a word come out ordered by x0 (they may overlap);
+ * 12. min_col_ink is checked and unused, except by the fallback of step 5.
+ * The result is an ordinary glyph block, released with ocr_glyphs_free and taken by ocr_extract_glyph_crops unchanged, except that
+ * word_info[4k+3] is a bit set for this call: 1 = truncated, 2 = fell back to the column rule.
+ * Still out of scope: letters that actually touch (one component, one glyph); crops are not masked by component, so a kerned
+ * neighbour's ink inside a glyph's box shows in its crop; one threshold per word (a word that is one blob under its Otsu threshold
+ * stays one glyph).  Oracle: tests/glyph_cc_oracle.py; kernel: csrc/glyph_cc.hip.
+ * Memory kinds, blocking behaviour and the stream rule are ocr_segment_glyphs's.  OCR_ERR_INVALID in the same cases, and for a field
+ * of `cc` out of range or a nonzero reserved field; the handle stays usable. */
+typedef struct ocr_cc_params {
+  int32_t merge_overlap_pct;  /* 0..100, default 50; 0 = never merge */
+  int32_t min_height_pct;     /* 0..100, default 25 */
+  int32_t reserved[2];        /* must be 0 */
+} ocr_cc_params_t;
+void ocr_cc_default_params(ocr_cc_params_t* p);
+/* params == NULL, cc == NULL -> defaults.  *out must be released with ocr_glyphs_free. */
+int ocr_segment_glyphs_cc(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
+                          const double* adj_xy, const ocr_segment_params_t* params, const ocr_cc_params_t* cc, ocr_glyphs_t** out);
+
 /* Word strips: every detected word (a polygon, possibly rotated) warped into an upright strip of strip_height rows, all strips of a
  * batch side by side in one atlas (BUILD-DEFINED, like ocr_segment_glyphs).  Frame coordinates are continuous: frame pixel p spans
  * [p, p + 1), and a vertex (x, y) is the point (x * adj_x, y * adj_y).

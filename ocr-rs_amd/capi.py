@@ -29,6 +29,7 @@ EXPORTS = [
     "ocr_det_forward_async", "ocr_det_synchronize", "ocr_det_forward_profile",
     "ocr_preprocess_image", "ocr_postproc_default_params", "ocr_det_postprocess", "ocr_det_post_stats", "ocr_det_detect_pipelined", "ocr_polygons_free",
     "ocr_extract_crops", "ocr_segment_default_params", "ocr_segment_glyphs", "ocr_extract_glyph_crops", "ocr_glyphs_free",
+    "ocr_cc_default_params", "ocr_segment_glyphs_cc",
     "ocr_strip_default_params", "ocr_plan_word_strips", "ocr_extract_word_strips", "ocr_word_strip_polygons", "ocr_word_strips_free",
     "ocr_evaluate_image", "ocr_combine_results",
     "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_set_stream", "ocr_rec_set_options", "ocr_rec_synchronize",
@@ -64,6 +65,10 @@ class Polygons(C.Structure):
 class SegmentParams(C.Structure):
     _fields_ = [("polarity", C.c_int32), ("min_col_ink", C.c_int32), ("min_glyph_pixels", C.c_int32), ("max_glyphs", C.c_int32),
                 ("glyph_box", C.c_int32), ("ink_high", C.c_int32)]
+
+
+class CcParams(C.Structure):
+    _fields_ = [("merge_overlap_pct", C.c_int32), ("min_height_pct", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class Glyphs(C.Structure):
@@ -175,6 +180,11 @@ def lib() -> C.CDLL:
         L.ocr_segment_default_params.restype = None
         L.ocr_segment_glyphs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Polygons),
                                          C.POINTER(C.c_double), C.POINTER(SegmentParams), C.POINTER(C.POINTER(Glyphs))]
+        L.ocr_cc_default_params.argtypes = [C.POINTER(CcParams)]
+        L.ocr_cc_default_params.restype = None
+        L.ocr_segment_glyphs_cc.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Polygons),
+                                            C.POINTER(C.c_double), C.POINTER(SegmentParams), C.POINTER(CcParams),
+                                            C.POINTER(C.POINTER(Glyphs))]
         L.ocr_extract_glyph_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Glyphs),
                                               C.POINTER(SegmentParams), C.c_void_p]
         L.ocr_glyphs_free.argtypes = [C.POINTER(Glyphs)]
@@ -324,9 +334,26 @@ def _as_segment_params(params) -> Optional[SegmentParams]:
     return segment_params(**params)
 
 
+def cc_params(**fields) -> CcParams:
+    """ocr_cc_default_params with the given fields overridden (merge_overlap_pct, min_height_pct)."""
+    p = CcParams()
+    lib().ocr_cc_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k not in ("merge_overlap_pct", "min_height_pct"):
+            raise TypeError(f"unknown cc parameter {k!r}")
+        setattr(p, k, int(v))
+    return p
+
+
+def _as_cc_params(cc) -> Optional[CcParams]:
+    if cc is None or isinstance(cc, CcParams):
+        return cc
+    return cc_params(**cc)
+
+
 class GlyphSet:
     """The arrays of an ocr_glyphs_t, copied into numpy: img_offsets [n_images+1], word_offsets [n_words+1], word_info n_words x 4
-    (frame, t, polarity used, truncated), word_levels n_words x 2 f32 (bg, ink), boxes n_glyphs x 4 (x0, y0, x1, y1, half-open)."""
+    (frame, t, polarity used, truncated - from segment_glyphs(cc=...) a bit set: 1 truncated, 2 column fallback), word_levels n_words x 2 f32 (bg, ink), boxes n_glyphs x 4 (x0, y0, x1, y1, half-open)."""
 
     def __init__(self, img_offsets, word_offsets, word_info, word_levels, boxes):
         self.img_offsets = np.ascontiguousarray(img_offsets, dtype=np.int32)
@@ -625,28 +652,35 @@ class Detector:
         finally:
             lib().ocr_polygons_free(out)
 
-    def _segment(self, frames_ptr, n: int, h: int, w: int, mem_kind: int, polys, adjust_values, params) -> GlyphSet:
+    def _segment(self, frames_ptr, n: int, h: int, w: int, mem_kind: int, polys, adjust_values, params, cc=None) -> GlyphSet:
         st, keep = python_to_polygons(polys, [[0.0] * len(p) for p in polys]) if not isinstance(polys, Polygons) else (polys, None)
         adj = np.ascontiguousarray(adjust_values, dtype=np.float64).reshape(-1, 2)
         prm = _as_segment_params(params)
         out = C.POINTER(Glyphs)()
-        check(lib().ocr_segment_glyphs(self._h, frames_ptr, n, h, w, mem_kind, C.byref(st), adj.ctypes.data_as(C.POINTER(C.c_double)),
-                                       C.byref(prm) if prm is not None else None, C.byref(out)))
+        prm_p = C.byref(prm) if prm is not None else None
+        adj_p = adj.ctypes.data_as(C.POINTER(C.c_double))
+        if cc is None:
+            check(lib().ocr_segment_glyphs(self._h, frames_ptr, n, h, w, mem_kind, C.byref(st), adj_p, prm_p, C.byref(out)))
+        else:
+            ccp = _as_cc_params(cc)
+            check(lib().ocr_segment_glyphs_cc(self._h, frames_ptr, n, h, w, mem_kind, C.byref(st), adj_p, prm_p, C.byref(ccp), C.byref(out)))
         try:
             return GlyphSet.from_block(out)
         finally:
             lib().ocr_glyphs_free(out)
 
-    def segment_glyphs(self, frames: np.ndarray, polys, adjust_values, params=None) -> GlyphSet:
+    def segment_glyphs(self, frames: np.ndarray, polys, adjust_values, params=None, cc=None) -> GlyphSet:
         """Glyph segmentation of the words `polys` (per image the polygons in original-image pixels, as postprocess returns them, or a
-        Polygons block) on host frames N x 1 x H x W f32.  params: SegmentParams, a dict of its fields, or None (defaults)."""
+        Polygons block) on host frames N x 1 x H x W f32.  params: SegmentParams, a dict of its fields, or None (defaults).
+        cc: None for the column rule (ocr_segment_glyphs); CcParams or a dict of its fields ({} for the defaults) for the
+        connected-component rule (ocr_segment_glyphs_cc), which splits kerned letters."""
         frames = np.ascontiguousarray(frames, dtype=np.float32)
         n, _, h, w = frames.shape
-        return self._segment(_ptr(frames), n, h, w, MEM_HOST, polys, adjust_values, params)
+        return self._segment(_ptr(frames), n, h, w, MEM_HOST, polys, adjust_values, params, cc)
 
-    def segment_glyphs_device(self, frames_ptr: int, n: int, h: int, w: int, polys, adjust_values, params=None) -> GlyphSet:
+    def segment_glyphs_device(self, frames_ptr: int, n: int, h: int, w: int, polys, adjust_values, params=None, cc=None) -> GlyphSet:
         """The same on device-resident frames (a device pointer to N x 1 x H x W f32)."""
-        return self._segment(C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, polys, adjust_values, params)
+        return self._segment(C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, polys, adjust_values, params, cc)
 
     def extract_glyph_crops(self, frames: np.ndarray, glyphs: GlyphSet, params=None) -> np.ndarray:
         """The 28 x 28 crop of every glyph (host frames) -> n_glyphs x 784 f32."""

@@ -315,23 +315,28 @@ void ocr_segment_default_params(ocr_segment_params_t* p) {
   p->ink_high = 1;
 }
 
-int ocr_segment_glyphs(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
-                       const double* adj_xy, const ocr_segment_params_t* params, ocr_glyphs_t** out) {
+// both segmentation entry points: cc == nullptr is the column rule (ocr_segment_glyphs), else the connected-component rule
+static int segment_glyphs(const char* who, ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
+                          const double* adj_xy, const ocr_segment_params_t* params, const ocr_cc_params_t* cc, ocr_glyphs_t** out) {
   return guard([&] {
     using namespace ocr;
-    if (!det || !frames || !polys || !adj_xy || !out) fail(OCR_ERR_INVALID, "segment_glyphs: null argument");
+    if (!det || !frames || !polys || !adj_xy || !out) fail(OCR_ERR_INVALID, "%s: null argument", who);
     *out = nullptr;
-    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "segment_glyphs: mem_kind %d", mem_kind);
-    if (n < 0 || h < 1 || w < 1) fail(OCR_ERR_INVALID, "segment_glyphs: N=%d H=%d W=%d", n, h, w);
-    if (polys->n_images != n) fail(OCR_ERR_INVALID, "segment_glyphs: polygon block holds %d images, frames %d", polys->n_images, n);
-    const ocr_segment_params_t p = segment_params(params, "segment_glyphs");
+    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "%s: mem_kind %d", who, mem_kind);
+    if (n < 0 || h < 1 || w < 1) fail(OCR_ERR_INVALID, "%s: N=%d H=%d W=%d", who, n, h, w);
+    if (polys->n_images != n) fail(OCR_ERR_INVALID, "%s: polygon block holds %d images, frames %d", who, polys->n_images, n);
+    const ocr_segment_params_t p = segment_params(params, who);
+    if (cc && (cc->merge_overlap_pct < 0 || cc->merge_overlap_pct > 100 || cc->min_height_pct < 0 || cc->min_height_pct > 100 ||
+               cc->reserved[0] != 0 || cc->reserved[1] != 0))
+      fail(OCR_ERR_INVALID, "%s: cc merge_overlap_pct=%d min_height_pct=%d reserved=%d, %d (limits: 0..100, 0..100, reserved 0)", who,
+           cc->merge_overlap_pct, cc->min_height_pct, cc->reserved[0], cc->reserved[1]);
     std::vector<WordBox> words;
     words.reserve(polys->n_polygons);
     for (const CropBox& c : crop_boxes(polys, adj_xy, n, h, w)) {
       const int x0 = std::min(std::max((int)std::floor(c.x0), 0), w), x1 = std::min(std::max((int)std::ceil(c.x1), 0), w);
       const int y0 = std::min(std::max((int)std::floor(c.y0), 0), h), y1 = std::min(std::max((int)std::ceil(c.y1), 0), h);
       if ((int64_t)(x1 - x0) * (y1 - y0) > (int64_t(1) << 22))
-        fail(OCR_ERR_INVALID, "segment_glyphs: word %zu box of %lld pixels (limit 2^22)", words.size(), (long long)(x1 - x0) * (y1 - y0));
+        fail(OCR_ERR_INVALID, "%s: word %zu box of %lld pixels (limit 2^22)", who, words.size(), (long long)(x1 - x0) * (y1 - y0));
       words.push_back({c.frame, x0, y0, x1, y1});
     }
     std::unique_ptr<GlyphsOwned> g(new GlyphsOwned());
@@ -357,16 +362,40 @@ int ocr_segment_glyphs(ocr_det_t* det, const float* frames, int n, int h, int w,
       }
       OCR_HIP(hipMemcpyAsync(sc + o_wd, words.data(), wd_bytes, hipMemcpyHostToDevice, s));
       const GlyphSegParams gp{p.polarity, p.min_col_ink, p.min_glyph_pixels, p.max_glyphs};
-      launch_segment(d_fr, h, w, d_words, nw, gp, d_rec, s);
+      if (cc)
+        launch_segment_cc(d_fr, h, w, d_words, nw, gp, GlyphCcParams{cc->merge_overlap_pct, cc->min_height_pct}, d_rec, s);
+      else
+        launch_segment(d_fr, h, w, d_words, nw, gp, d_rec, s);
       OCR_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s));
       OCR_HIP(hipStreamSynchronize(s));
+      if (cc) {
+        // words over a limit of the component rule (flag 2): the column kernel over just those, their records patched in
+        std::vector<int> over;
+        for (int i = 0; i < nw; ++i)
+          if (rec[(size_t)i * R + 3] & 2) over.push_back(i);
+        if (!over.empty()) {
+          std::vector<WordBox> ow;
+          for (int i : over) ow.push_back(words[i]);
+          std::vector<int32_t> orec(over.size() * (size_t)R);
+          // the word list and the records of the first launch have been read back: their scratch is reused
+          OCR_HIP(hipMemcpyAsync(sc + o_wd, ow.data(), ow.size() * sizeof(WordBox), hipMemcpyHostToDevice, s));
+          launch_segment(d_fr, h, w, d_words, (int)over.size(), gp, d_rec, s);
+          OCR_HIP(hipMemcpyAsync(orec.data(), d_rec, orec.size() * 4, hipMemcpyDeviceToHost, s));
+          OCR_HIP(hipStreamSynchronize(s));
+          for (size_t k = 0; k < over.size(); ++k) {
+            int32_t* r = &rec[(size_t)over[k] * R];
+            std::copy(&orec[k * R], &orec[k * R] + R, r);
+            r[3] |= 2;
+          }
+        }
+      }
       g->word_info.resize((size_t)4 * nw);
       g->word_levels.resize((size_t)2 * nw);
       for (int i = 0; i < nw; ++i) {   // the per-word records -> CSR
         const int32_t* r = &rec[(size_t)i * R];
         std::copy(r, r + 4, &g->word_info[(size_t)4 * i]);
         std::memcpy(&g->word_levels[(size_t)2 * i], r + 4, 8);
-        if (r[6] < 0 || r[6] > p.max_glyphs) fail(OCR_ERR_INTERNAL, "segment_glyphs: word %d reports %d glyphs", i, r[6]);
+        if (r[6] < 0 || r[6] > p.max_glyphs) fail(OCR_ERR_INTERNAL, "%s: word %d reports %d glyphs", who, i, r[6]);
         g->boxes.insert(g->boxes.end(), r + 8, r + 8 + 4 * r[6]);
         g->word_offsets.push_back((int32_t)(g->boxes.size() / 4));
       }
@@ -374,6 +403,26 @@ int ocr_segment_glyphs(ocr_det_t* det, const float* frames, int n, int h, int w,
     g->finish();
     *out = &g.release()->view;
   });
+}
+
+int ocr_segment_glyphs(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
+                       const double* adj_xy, const ocr_segment_params_t* params, ocr_glyphs_t** out) {
+  return segment_glyphs("segment_glyphs", det, frames, n, h, w, mem_kind, polys, adj_xy, params, nullptr, out);
+}
+
+void ocr_cc_default_params(ocr_cc_params_t* p) {
+  if (!p) return;
+  p->merge_overlap_pct = 50;
+  p->min_height_pct = 25;
+  p->reserved[0] = p->reserved[1] = 0;
+}
+
+int ocr_segment_glyphs_cc(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
+                          const double* adj_xy, const ocr_segment_params_t* params, const ocr_cc_params_t* cc, ocr_glyphs_t** out) {
+  ocr_cc_params_t c;
+  ocr_cc_default_params(&c);
+  if (cc) c = *cc;
+  return segment_glyphs("segment_glyphs_cc", det, frames, n, h, w, mem_kind, polys, adj_xy, params, &c, out);
 }
 
 int ocr_extract_glyph_crops(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_glyphs_t* glyphs,

@@ -205,6 +205,13 @@ struct GlyphJob {
 __host__ __device__ inline int glyph_record_ints(int max_glyphs) { return 8 + 4 * max_glyphs; }
 void launch_segment(const float* frames_dev, int H, int W, const WordBox* words_dev, int n_words, const GlyphSegParams& p,
                     int32_t* records_dev, hipStream_t s);
+// connected-component rule (glyph_cc.hip; include/ocr_amd.h ocr_segment_glyphs_cc, tests/glyph_cc_oracle.py): the same records, [3] a
+// bit set (1 truncated, 2 left to the column rule: such a word's record holds no glyphs and launch_segment fills it in)
+struct GlyphCcParams {
+  int merge_overlap_pct, min_height_pct;
+};
+void launch_segment_cc(const float* frames_dev, int H, int W, const WordBox* words_dev, int n_words, const GlyphSegParams& p,
+                       const GlyphCcParams& cc, int32_t* records_dev, hipStream_t s);
 void launch_glyph_crops(const float* frames_dev, int H, int W, const GlyphJob* jobs_dev, int n_glyphs, int glyph_box, int ink_high,
                         float* crops_dev, hipStream_t s);
 

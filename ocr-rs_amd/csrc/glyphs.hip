@@ -6,7 +6,8 @@
 //
 // segment_kernel, one 256-thread workgroup per word:
 //   1. histogram of q = (int)clamp(v, 0, 255) over the word box: one 256-bin LDS histogram per wave, integer atomics (order-free);
-//   2. wave 0 runs Otsu: prefix sums over the 256 bins (4 per lane + a wave scan), the f64 score per t, argmax -> smaller t on ties;
+//   2. wave 0 runs Otsu: prefix sums over the 256 bins (4 per lane + a wave scan), the f64 score per t, argmax -> smaller t on ties
+//      (1 and 2 live in glyph_levels.hpp, shared with glyph_cc.hip);
 //   3. column profile, CHUNK columns at a time: per column the ink count and the first / last ink row, accumulated in registers over a
 //      row slice and merged with LDS atomics (min / max / add: order-free);
 //   4. wave 0 finds the spans of the chunk with a ballot per 64 columns; a span open at the chunk's end carries over.  Per span the
@@ -19,32 +20,19 @@
 // Out of scope of the rule: touching or kerned glyphs (they stay one glyph), rotated or curved words (the word box is axis-aligned and
 // pixels are not masked by the polygon), lexicons, spaces inside a polygon.
 #include "common.hpp"
+#include "glyph_levels.hpp"
 
 namespace ocr {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+using glyph_dev::kThreads;
+using glyph_dev::kWaves;
+using glyph_dev::quantise;
+using glyph_dev::wave_max;
+using glyph_dev::wave_min;
+using glyph_dev::wave_sum;
 constexpr int kChunk = 1024;   // columns of the profile held in LDS at a time
 constexpr int kMaxSlots = 256;
-
-__device__ __forceinline__ int quantise(float v) {
-  // (int)min(max(v, 0), 255) with NaN -> 0, spelt with comparisons so that no min/max NaN convention enters
-  return v >= 0.f ? (v <= 255.f ? (int)v : 255) : 0;
-}
-
-__device__ __forceinline__ int wave_min(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __global__ __launch_bounds__(kThreads) void segment_kernel(const float* __restrict__ frames, int H, int W, const WordBox* __restrict__ words,
                                                            GlyphSegParams prm, int32_t* __restrict__ rec) {
@@ -57,80 +45,11 @@ __global__ __launch_bounds__(kThreads) void segment_kernel(const float* __restri
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const WordBox wb = words[blockIdx.x];
   const float* img = frames + (size_t)wb.frame * H * W;
-  const int bw = wb.x1 - wb.x0, bh = wb.y1 - wb.y0, area = bw * bh;
+  const int bw = wb.x1 - wb.x0;
   int32_t* out = rec + (size_t)blockIdx.x * glyph_record_ints(prm.max_glyphs);
 
-  for (int i = tid; i < kWaves * 256; i += kThreads) (&hist[0][0])[i] = 0;
-  __syncthreads();
-  for (int i = tid; i < area; i += kThreads) {
-    const int y = i / bw, x = i - y * bw;
-    atomicAdd(&hist[wv][quantise(img[(size_t)(wb.y0 + y) * W + wb.x0 + x])], 1u);
-  }
-  __syncthreads();
-
-  if (wv == 0) {
-    // lane owns bins 4*lane .. 4*lane+3: local counts / sums, then an inclusive wave scan of the lane totals
-    long long hc[4], hs[4], c = 0, s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int bin = 4 * lane + k;
-      hc[k] = (long long)hist[0][bin] + hist[1][bin] + hist[2][bin] + hist[3][bin];
-      hs[k] = hc[k] * bin;
-      c += hc[k];
-      s += hs[k];
-    }
-    long long ic = c, is = s;
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long pc = __shfl_up(ic, o), ps = __shfl_up(is, o);
-      if (lane >= o) { ic += pc; is += ps; }
-    }
-    const long long Wt = __shfl(ic, 63), St = __shfl(is, 63);
-    long long w0 = ic - c, s0 = is - s;   // exclusive prefix: bins below 4*lane
-    double best = -1.0;
-    int bt = -1;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      w0 += hc[k];
-      s0 += hs[k];
-      const int t = 4 * lane + k;
-      const long long w1 = Wt - w0, s1 = St - s0;
-      if (t < 255 && w0 > 0 && w1 > 0) {
-        const double d = (double)(s1 * w0 - s0 * w1);
-        const double sc = (d * d) / ((double)w0 * (double)w1);
-        if (sc > best) { best = sc; bt = t; }   // k ascending: ties keep the smaller t
-      }
-    }
-    // argmax over the wave: the higher score, the smaller t on ties (bt = -1 carries best = -1 and never beats a valid t)
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ob = __shfl_xor(best, o);
-      const int ot = __shfl_xor(bt, o);
-      if (ob > best || (ob == best && ot >= 0 && (bt < 0 || ot < bt))) { best = ob; bt = ot; }
-    }
-    if (lane == 0) {
-      int pol = 0;
-      float bg = 0.f, ink = 0.f;
-      if (bt >= 0) {
-        long long W0 = 0, S0 = 0;
-        for (int b = 0; b <= bt; ++b) {
-          const long long h = (long long)hist[0][b] + hist[1][b] + hist[2][b] + hist[3][b];
-          W0 += h;
-          S0 += h * b;
-        }
-        const long long W1 = Wt - W0, S1 = St - S0;
-        pol = prm.polarity != 0 ? prm.polarity : (W0 <= W1 ? 1 : 2);
-        const float mu0 = (float)((double)S0 / (double)W0), mu1 = (float)((double)S1 / (double)W1);
-        bg = pol == 1 ? mu1 : mu0;
-        ink = pol == 1 ? mu0 : mu1;
-      }
-      s_t = bt;
-      s_pol = pol;
-      out[0] = wb.frame;
-      out[1] = bt;
-      out[2] = pol;
-      out[4] = __float_as_int(bg);
-      out[5] = __float_as_int(ink);
-    }
-  }
+  glyph_dev::box_histogram(hist, img, W, wb);
+  glyph_dev::otsu_levels(hist, wb, prm.polarity, out, &s_t, &s_pol);
   __syncthreads();
   const int t = s_t, pol = s_pol;
   if (t < 0) {   // flat box: no glyphs

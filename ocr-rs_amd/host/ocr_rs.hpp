@@ -138,10 +138,13 @@ struct WordReading {
 };
 // ocr_segment_glyphs -> ocr_extract_glyph_crops -> ocr_rec_classify over host memory: per image, per polygon of `ps`.  frames are the
 // detector's input (N x 1 x H x W, raw 0..255), adjust_values N x 2 as given to get_boxes_and_box_scores; params == nullptr: defaults.
+// cc == nullptr segments by the column rule; a pointer (see ocr_cc_default_params) segments by connected components
+// (ocr_segment_glyphs_cc), which splits kerned letters.
 inline std::vector<std::vector<WordReading>> read_words(const text_detection::FuncT& det_net, const char_recognition::Net& rec_net,
                                                         const Tensor& frames, const text_detection::metrics::PolygonScores& ps,
                                                         const std::vector<double>& adjust_values,
-                                                        const ocr_segment_params_t* params = nullptr) {
+                                                        const ocr_segment_params_t* params = nullptr,
+                                                        const ocr_cc_params_t* cc = nullptr) {
   if (frames.c != 1) throw Error(OCR_ERR_INVALID, "expected N x 1 x H x W");
   if ((int)ps.polygons.size() != frames.n || (int)adjust_values.size() != 2 * frames.n)
     throw Error(OCR_ERR_INVALID, "polygons / adjust_values do not match the frames");
@@ -162,8 +165,10 @@ inline std::vector<std::vector<WordReading>> read_words(const text_detection::Fu
   const ocr_polygons_t polys{frames.n, (int32_t)scores.size(), (int32_t)(xy.size() / 2), img_off.data(), poly_off.data(), xy.data(),
                              scores.data()};
   ocr_glyphs_t* g = nullptr;
-  check(ocr_segment_glyphs(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, &polys,
-                           adjust_values.data(), params, &g));
+  check(cc ? ocr_segment_glyphs_cc(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, &polys,
+                                   adjust_values.data(), params, cc, &g)
+           : ocr_segment_glyphs(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, &polys,
+                                adjust_values.data(), params, &g));
   struct Free {
     ocr_glyphs_t* g;
     ~Free() { ocr_glyphs_free(g); }
@@ -201,10 +206,12 @@ struct WordReadingRectified {
 };
 // ocr_plan_word_strips -> ocr_extract_word_strips -> ocr_word_strip_polygons -> ocr_segment_glyphs -> ocr_extract_glyph_crops ->
 // ocr_rec_classify over host memory (the atlas is one frame of the glyph calls, adj = (1, 1)); per image, per polygon of `ps`.
+// cc as in read_words: a pointer segments the atlas by connected components.
 inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
     const text_detection::FuncT& det_net, const char_recognition::Net& rec_net, const Tensor& frames,
     const text_detection::metrics::PolygonScores& ps, const std::vector<double>& adjust_values,
-    const ocr_strip_params_t* strip_params = nullptr, const ocr_segment_params_t* params = nullptr) {
+    const ocr_strip_params_t* strip_params = nullptr, const ocr_segment_params_t* params = nullptr,
+    const ocr_cc_params_t* cc = nullptr) {
   if (frames.c != 1) throw Error(OCR_ERR_INVALID, "expected N x 1 x H x W");
   if ((int)ps.polygons.size() != frames.n || (int)adjust_values.size() != 2 * frames.n)
     throw Error(OCR_ERR_INVALID, "polygons / adjust_values do not match the frames");
@@ -243,7 +250,8 @@ inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
   } free_r{rects};
   const double one[2] = {1.0, 1.0};
   ocr_glyphs_t* g = nullptr;
-  check(ocr_segment_glyphs(det_net.handle(), atlas.data(), 1, hs, tw, OCR_MEM_HOST, rects, one, params, &g));
+  check(cc ? ocr_segment_glyphs_cc(det_net.handle(), atlas.data(), 1, hs, tw, OCR_MEM_HOST, rects, one, params, cc, &g)
+           : ocr_segment_glyphs(det_net.handle(), atlas.data(), 1, hs, tw, OCR_MEM_HOST, rects, one, params, &g));
   struct FreeGlyphs {
     ocr_glyphs_t* g;
     ~FreeGlyphs() { ocr_glyphs_free(g); }

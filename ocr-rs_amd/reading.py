@@ -3,6 +3,7 @@ recognition -> output text), composed over the C ABI.
 
     read_words(det_net, rec_net, frames, polygon_scores, adjust_values)
         ocr_segment_glyphs        every detected word (polygon) -> glyph boxes          (csrc/glyphs.hip, segment_kernel)
+          or, with cc=..., ocr_segment_glyphs_cc: connected components, kerned letters split   (csrc/glyph_cc.hip)
         ocr_extract_glyph_crops   every glyph -> one 28 x 28 crop, on the device         (csrc/glyphs.hip, glyph_crop_kernel)
         ocr_rec_classify          every crop -> label in VALUES (utils.rs:7) and its probability
 
@@ -12,7 +13,7 @@ recognition -> output text), composed over the C ABI.
         then the three calls above on the atlas, through the rectangles of ocr_word_strip_polygons
 
 The segmentation and strip rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
-tests/glyph_oracle.py and tests/strip_oracle.py.
+tests/glyph_oracle.py, tests/glyph_cc_oracle.py and tests/strip_oracle.py.
 """
 from __future__ import annotations
 
@@ -49,14 +50,15 @@ def _device_frames(det, frames):
     return x
 
 
-def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None
+def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None, cc=None
                ) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch.
 
     det_net: text_detection.FuncT or capi.Detector (supplies the GPU and stream of the segmentation); rec_net: char_recognition.Net
     or capi.Recognizer.  frames: the detector's input, N x 1 x H x W f32 raw 0..255, a numpy array or a CUDA tensor.
     polygon_scores: what get_boxes_and_box_scores returned (or its per-image polygon lists); adjust_values: N x 2 as given to it.
-    params: capi.SegmentParams, a dict of its fields, or None for the defaults.
+    params: capi.SegmentParams, a dict of its fields, or None for the defaults.  cc: None segments by the column rule; capi.CcParams
+    or a dict of its fields ({} for the defaults) segments by connected components (ocr_segment_glyphs_cc), which splits kerned letters.
     Returns per image, per polygon: (text, probability of every character (f64), glyph boxes k x 4 int32 x0, y0, x1, y1 in frame
     pixels, half-open).  A flat word reads as ""."""
     import torch
@@ -77,7 +79,7 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     n, _, h, w = x.shape
     # the library's calls run on their handles' streams: whatever torch queued to produce x is finished first
     torch.cuda.current_stream(dev).synchronize()
-    glyphs = det.segment_glyphs_device(x.data_ptr(), n, h, w, polys, adjust_values, params)
+    glyphs = det.segment_glyphs_device(x.data_ptr(), n, h, w, polys, adjust_values, params, cc)
     ng = glyphs.n_glyphs
     labels = np.zeros(0, np.int32)
     probs = np.zeros(0, np.float64)
@@ -124,12 +126,12 @@ def strip_glyph_quads(strips: "capi.WordStrips", words: np.ndarray, boxes: np.nd
     return np.stack([(q[:, 0:1] + cs * cux) + rs * rvx, (q[:, 1:2] + cs * cuy) + rs * rvy], axis=2)
 
 
-def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None
+def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None, cc=None
                          ) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch through its upright strip: rotated words are read along their own axis.
 
     Arguments as read_words; strip_params: capi.StripParams, a dict of its fields (strip_height, max_width) or None for the defaults;
-    params: the segmentation parameters, applied to the atlas.  Returns per image, per polygon: (text, probability of every character
+    params and cc: the segmentation parameters and rule as in read_words, applied to the atlas.  Returns per image, per polygon: (text, probability of every character
     (f64), glyph quads k x 4 x 2 f64: the corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of every glyph box mapped back to frame
     coordinates, strip_glyph_quads).  A flat word reads as ""."""
     import torch
@@ -148,7 +150,7 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     det.extract_word_strips_device(x.data_ptr(), n, h, w, strips, atlas.data_ptr())      # blocking
     hs, tw = strips.height, strips.total_width
     with strips.polygon_block() as rects:
-        glyphs = det.segment_glyphs_device(atlas.data_ptr(), 1, hs, tw, rects, [[1.0, 1.0]], params)
+        glyphs = det.segment_glyphs_device(atlas.data_ptr(), 1, hs, tw, rects, [[1.0, 1.0]], params, cc)
     ng = glyphs.n_glyphs
     labels = np.zeros(0, np.int32)
     probs = np.zeros(0, np.float64)
