@@ -161,8 +161,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_c64_kernel(C64Args p) {
       }
       C64_STAMP(5 + 2 * r);
     });
-    // the residual loads are older than the (at most six) patch DMA instructions of this wave: a counted wait leaves
-    // those in flight
+    // the residual loads are older than the (five or six: wave < 4) patch DMA instructions of this wave: a counted wait leaves
+    // those in flight.  No residual = no load was issued (the same uniform condition guards both), nothing to wait for.
+    // (shown from the disassembly of the shipped binary: tests/test_isa_vmcnt.py)
     if (!p.residual) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     else if (has_next) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");

@@ -20,8 +20,9 @@
 //
 // The B loads are inline asm with hand-counted s_waitcnt (a compiler-visible load next to the LDS-DMA makes hipcc wait for
 // the DMA too).  The compiler believes such a register is valid as soon as the asm statement has run, so the code keeps every
-// load's issue, wait and use inside one straight-line chunk body; tests/test_gpu_conv_kernel.py (eight shapes, all 36
-// components, every chunk) and the end-to-end parity tests run the shipped binary and fail on any stale operand.
+// load's issue, wait and use inside one straight-line chunk body.  That every wait covers its loads in the SHIPPED binary is
+// checked from its disassembly, without a GPU: tests/test_isa_vmcnt.py (tests/isa_vmcnt.py, docs/vmcnt_audit.md) - a numerical
+// test cannot show it, since whether a stale operand had arrived anyway depends on what else the chip was doing.
 #include <algorithm>
 #include <cstring>
 #include <type_traits>

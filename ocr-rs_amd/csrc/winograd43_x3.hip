@@ -23,6 +23,7 @@
 //
 // LDS: 4 patch buffers (2 blocks x 2 halves of 16 channels) + V = 158 KB, one workgroup per CU.  Inline-asm loads with
 // hand-counted s_waitcnt as in winograd43_fused.hip: every load's issue, wait and use sit in one straight-line chunk body.
+// (the waits of the shipped binary are checked from its disassembly: tests/test_isa_vmcnt.py)
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
