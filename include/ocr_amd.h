@@ -68,8 +68,6 @@ int ocr_det_create(const void* weights, size_t weights_bytes, int device, ocr_de
  *                               channels (trunk, FPN lateral terms); 0 = direct / unfused-Winograd convs
  *   out4_fused=0|1       (0)    1 = out4 (256 -> 64 at H/16) on the fused kernel too and out5 as a direct conv; 0 = both through the
  *                               unfused F(4x4,3x3) path of layer3 / layer4 (faster at these grid sizes)
- *   winograd43_x3=0|1    (0)    with mfma=split_bf16: 1 = the fused F(4x4,3x3) convs multiply on the bf16 matrix cores as well
- *                               (winograd43_x3.hip, same error bound); measured slower than the f32-MFMA kernel, kept for A/B
  *   winograd=<cin>|0     (256)  unfused Winograd for 3x3 s1 trunk convs with Cin >= cin that have no fused form; 0 = off
  *   winograd43=<cin>|0   (256)  of those, the layers with Cin >= cin use F(4x4,3x3) (36 products per 16 outputs) instead of
  *                               F(2x2,3x3) (16 per 4); 0 = F(2x2) everywhere
@@ -85,15 +83,10 @@ int ocr_det_create(const void* weights, size_t weights_bytes, int device, ocr_de
  *   pyr_p2_direct=0|1    (1)    bf16 precision only: p2's 3x3 term of bin_conv1 as the patch-staged 64 -> 64 conv on top of the phase
  *                               launch over p5, p4, p3 (0: all four sources in the phase launch)
  *   tail_unfused=0|1     (0)    1 = probability head as two launches
- *   transform_fuse=0|1   (0)    layer3 / layer4, block 1: conv1's Winograd output transform and conv2's input transform in one launch (the
- *                               activation between them stays in LDS); bit-identical, and measured to buy nothing (docs/history.md)
  *   overlap=0|1|2|3      (3)    second stream: 1 small independent launches; 2 the FPN branch as it stands; 3 the FPN's fused-Winograd
  *                               launches (lateral terms of p2 / p3) and bin_conv1's p2 term - f32 matrix instructions - beside layer2 / layer3 / layer4 /
  *                               the small FPN convs - bf16 matrix instructions and HBM-bound transforms: 2 % of the step in both precisions (default kernels;
  *                               otherwise, and under ocr_det_forward_profile, one stream).  Sums re-associate by one rounding.  Any other value is OCR_ERR_INVALID
- *   x3_wide=0|1          (0)    the split-bf16 convs with plain NHWC stores and Cout % 128 == 0 (stride-2 3x3, 1x1, the Winograd GEMMs) as 256 x 128 tiles
- *                               on one persistent workgroup per CU (conv_x3w.hip): 30 % fewer operand bytes per MFMA, bit-identical, and measured 0-35 %
- *                               SLOWER than the 128-wide tiles at two workgroups per CU: kept for A/B
  *   bf16_block_fuse=0|1  (1)    bf16 precision: each BasicBlock of layer1 (conv3x3 + BN + ReLU, conv3x3 + BN, + x, ReLU: model.rs:40-55) as ONE launch, the
  *                               activation between its two convs held in LDS (basic_block_bf16_c64.hip): half the HBM traffic of the two launches, 1.25 x
  *                               their matrix work, 5-10 % less time; 0 = two conv3x3_bf16_c64 launches.  The same bits either way
@@ -129,7 +122,9 @@ int ocr_det_create(const void* weights, size_t weights_bytes, int device, ocr_de
  *                               products per pair on v_mfma_f32_32x32x16_bf16, f32 accumulation - the error of an f32 FMA chain
  *                               (dropped terms <= 2^-23 of a product; profiles/r03_bf16x3_accuracy.txt), the same parity bars, up to
  *                               2.67 x the f32 matrix rate.  f32: every conv on v_mfma_f32_32x32x2_f32 (exact f32 FMA chain).
- *   precision=f32|bf16   (f32)  same as ocr_det_set_precision */
+ *   precision=f32|bf16   (f32)  same as ocr_det_set_precision
+ * Any other key is OCR_ERR_INVALID ("unknown detector option").  That includes x3_wide, winograd43_x3 and transform_fuse, which earlier versions
+ * accepted: the kernels they selected were measured no faster than the defaults and left the library (docs/history.md). */
 int ocr_det_create_with_options(const void* weights, size_t weights_bytes, int device, const char* options,
                                 ocr_det_t** out);
 /* Size limit of one launch.  The kernels address every tensor with 32-bit BYTE offsets below the out-of-range marker 2^31

@@ -74,7 +74,6 @@ struct ConvDesc {
                           // neighbour, as 128-column tiles of 2 x 2 / 1 x 2 / 2 x 1 phase blocks; 2 = the four corner phases (0 | 7, 0 | 7)
   int win;                // STORE_PHASE with up 2, Cout 64 (x3 or bf16 operands): the GEMM's rows are the (Hin + 1) x (Win + 1) 2 x 2 windows of the low-res grid and the four
                           // phases that read a window are the four 64-column groups of one 128-wide pair of tiles (same products, same order)
-  int wide;               // x3: take the 256 x 128 persistent form (conv_x3w.hip) where it exists for the launch - same bits
   const void* wgt;
   const float* scale;     // per output column, may be null (then scale 1 / bias 0); always f32
   const float* bias;
@@ -92,10 +91,6 @@ struct ConvDesc {
 // ctc.hip (extension, no reference counterpart): CTC greedy decode, one wave per crop; logits [n][t][c] -> labels [n][t] (-1 padded), lengths [n]
 void launch_ctc_greedy(const float* logits_dev, int n, int t, int c, int blank, int32_t* labels_dev, int32_t* lengths_dev, hipStream_t s);
 void launch_conv_igemm(const ConvDesc& d, hipStream_t s);
-// conv_x3w.hip: the split-bf16 convs with NHWC stores and Cout a multiple of 128 as 256 x 128 tiles on one persistent workgroup per CU
-// (bit-identical to conv_igemm's 128-wide split-bf16 tiles); `cus` = CUs of the device
-bool conv_x3_wide_applicable(const ConvDesc& d);
-void launch_conv_x3_wide(const ConvDesc& d, int cus, hipStream_t s);
 // hi / mid / lo bf16 planes of an f32 weight array whose rows are multiples of 16 long ([3][count] bf16; inside every
 // aligned group of 16 the k order is the one the split-bf16 kernel's A fragments have: 0-3, 8-11, 4-7, 12-15)
 std::vector<uint16_t> split3_weights(const float* w, size_t count);
@@ -135,21 +130,12 @@ void launch_basic_block_bf16_c64(const void* x, const void* wfrag1, const float*
 // of the deep, small-grid layers.  x: [N][H][W][C] f32 -> v: [(m+2)^2][T][C], T = N * ceil(H/m) * ceil(W/m) tiles (zero
 // padding and ragged sizes handled here); mm: [(m+2)^2][T][K] -> y: [N][H][W][K] with folded BN, residual and ReLU.
 void launch_winograd_input(const float* x, float* v, int N, int H, int W, int C, int m, hipStream_t s);
-// F(4x4): output transform of one conv (+ BN, residual, ReLU; y may be null: nothing else reads the activation) and input transform of the next in one launch
-bool winograd43_out_in_fits(int H, int W, int K);
-void launch_winograd43_out_in(const float* mm, const float* scale, const float* bias, const float* residual, int relu, float* y, float* v, int N, int H, int W,
-                              int K, hipStream_t s);
 void launch_winograd_output(const float* mm, const float* scale, const float* bias, const float* residual, int relu,
                             float* y, int N, int H, int W, int K, int m, hipStream_t s);
 // The same conv with both transforms fused into the GEMM kernel, F(4x4,3x3) (winograd43_fused.hip): C = 64, 128 or 256, K a multiple of 64.  ufrag: winograd43_fragments(winograd_weights(.., 4)).
 std::vector<float> winograd43_fragments(const std::vector<float>& u, int cout, int cin);
 void launch_winograd43_fused(const float* x, const float* ufrag, const float* scale, const float* bias, const float* residual,
                              int relu, float* y, int N, int H, int W, int C, int K, int num_cus, hipStream_t s);
-// ... and with its GEMMs on the bf16 matrix cores, f32 operands as three bf16 terms each (winograd43_x3.hip; mfma=split_bf16):
-// two pixel blocks per workgroup, one workgroup per CU.  ufrag: winograd43_x3_fragments(winograd_weights(.., 4)).
-std::vector<uint16_t> winograd43_x3_fragments(const std::vector<float>& u, int cout, int cin);
-void launch_winograd43_x3(const float* x, const void* ufrag, const float* scale, const float* bias, const float* residual,
-                          int relu, float* y, int N, int H, int W, int C, int K, int num_cus, hipStream_t s);
 // tail: convT2x2 s2 64->1 + bias + sigmoid (+ optional binarize)
 void launch_convt2_sigmoid(const float* in, const float* w4x64, float bias, float* prob,
                            uint8_t* bitmap, float thresh, int N, int H2, int W2, hipStream_t s);

@@ -20,7 +20,7 @@
 // Winograd GEMMs of layer3 / layer4  (/root/reference/src/text_detection/model.rs:30-55,75-78,84-98).
 #include <type_traits>
 
-#include "common.hpp"
+#include "test_kernels.hpp"
 
 namespace ocr {
 namespace x3w {

@@ -161,7 +161,6 @@ void Detector::add_winograd_fused_weights(ConvW& cw) {
   if ((cw.cin != 64 && cw.cin != 128 && cw.cin != 256) || cw.cout % 64 || cw.ks != 3) fail(OCR_ERR_INTERNAL, "fused Winograd: unsupported conv shape");
   const std::vector<float> u = winograd_weights(cw.host.data(), cw.cout, cw.cin, 4);
   cw.wino43_fused = arena_.upload(winograd43_fragments(u, cw.cout, cw.cin));
-  if (split_bf16_ && winograd43_x3_) cw.wino43_x3 = arena_.upload_u16(winograd43_x3_fragments(u, cw.cout, cw.cin));
 }
 
 // hi / mid / lo bf16 planes of a conv's f32 weights (and of its Winograd form): what conv_igemm's split-bf16 kernels read
@@ -239,7 +238,6 @@ void Detector::parse_options(const char* options) {
       return (int)v;
     };
     if (key == "winograd_fused") winograd_fused_ = num() != 0;
-    else if (key == "winograd43_x3") winograd43_x3_ = num() != 0;
     else if (key == "out4_fused") out4_fused_ = num() != 0;
     else if (key == "winograd") winograd_min_cin_ = num() > 0 ? num() : (1 << 30);
     else if (key == "winograd43") winograd43_min_cin_ = num() > 0 ? num() : (1 << 30);
@@ -248,7 +246,6 @@ void Detector::parse_options(const char* options) {
     else if (key == "pyr_p2_direct") pyr_p2_direct_ = num() != 0;
     else if (key == "pyr_grouped") pyr_grouped_ = num() != 0;
     else if (key == "phase_windows") phase_windows_ = num() != 0;
-    else if (key == "x3_wide") x3_wide_ = num() != 0;
     else if (key == "bf16_block_fuse") bf16_block_fuse_ = num() != 0;
     else if (key == "tail_unfused") fused_tail_ = num() == 0;
     else if (key == "overlap") {
@@ -279,7 +276,6 @@ void Detector::parse_options(const char* options) {
       head_cus_yield_ = num();
       if (head_cus_yield_ < 0 || head_cus_yield_ > 4) fail(OCR_ERR_INVALID, "detector option head_cus_yield: %d (0 .. 4)", head_cus_yield_);
     }
-    else if (key == "transform_fuse") transform_fuse_ = num() != 0;
     else if (key == "device_unclip") {
       device_unclip_ = num();
       if (device_unclip_ < 0 || device_unclip_ > 2) fail(OCR_ERR_INVALID, "detector option device_unclip: %d (0, 1 or 2)", device_unclip_);
@@ -883,7 +879,7 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
   if (head_cus_yield_ >= 2 && chain_beside) grid_cus = num_cus_ * head_cus_yield_;
   const bool overlap3 = overlap_ >= 3 && !prof && fpn_composed_ && bin_pyr_on_ && fused_tail_ &&
                         (bf16_ ? (fpn_a_[0].w_bf16_c64 && bin_p2_.w_bf16_c64 && pyr_p2_direct_)
-                               : (fpn_a_[0].wino43_fused && fpn_a_[1].wino43_fused && bin_p2_.wino43_fused && !fpn_a_[0].wino43_x3 && split_bf16_));
+                               : (fpn_a_[0].wino43_fused && fpn_a_[1].wino43_fused && bin_p2_.wino43_fused && split_bf16_));
   const bool overlap = overlap3 || (overlap_ == 2 && !prof && fpn_composed_ && !bf16_);   // the FPN branch on the side stream, joined before bin_conv1
   const bool overlap_small = (overlap_ == 1 || overlap_ == 2) && !prof;   // (3: the side stream is the FPN branch's alone)
   // run `side_work` on the second stream from this point of the main stream on; join() makes the main stream
@@ -935,7 +931,6 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
     d.wgt = in_bf ? cw.w_bf16 : static_cast<const void*>(cw.w);
     if (!bf && split_bf16_ && cw.w_x3 && !ex.cat4 && ex.store != STORE_SHUFFLE2 && !(ex.pyr4 && ex.pyr_nsrc != 3)) {
       d.x3 = 1;
-      d.wide = x3_wide_ ? 1 : 0;
       d.wgt = cw.w_x3;
       d.wgt_bytes = cw.w_bytes / 4 * 6;
     }
@@ -1003,7 +998,6 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
     d.wgt_bytes = cw.wino_bytes;
     if (split_bf16_ && cw.wino_x3) {
       d.x3 = 1;
-      d.wide = x3_wide_ ? 1 : 0;
       d.wgt = cw.wino_x3;
       d.wgt_bytes = cw.wino_bytes / 4 * 6;
     }
@@ -1033,37 +1027,11 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
     rec.end(wm == 4 ? "winograd43_output_transform" : "winograd_output_transform", 0.0,
             (double)wa * T * cw.cout * 4.0 + (double)n * hh * ww * cw.cout * 4.0 * (residual ? 2.0 : 1.0));
   };
-  // ... and the output transform of one conv fused with the input transform of the next (winograd.hip: the image of a workgroup's 16
-  // channels stays in LDS); y may be null when only the next conv reads the activation
-  auto wino_out_in = [&](const ConvW& cw, int hh, int ww, void* y, const void* residual, bool relu) {
-    size_t wm, wa, T;
-    wino_dims(cw, hh, ww, wm, wa, T);
-    rec.begin();
-    launch_winograd43_out_in(wino_m_, cw.scale, cw.bias, static_cast<const float*>(residual), relu ? 1 : 0, static_cast<float*>(y), wino_v_, n, hh, ww,
-                             cw.cout, stream_);
-    rec.end("winograd43_output+input_transform", 0.0, 2.0 * (double)wa * T * cw.cout * 4.0 + (double)n * hh * ww * cw.cout * 4.0 * ((residual ? 1.0 : 0.0) + (y ? 1.0 : 0.0)));
-  };
-  // can this conv take the unfused F(4x4) path with fused neighbours?  (the conditions of conv3x3's last branch + the LDS image)
-  auto wino43_unfused = [&](const ConvW& cw, int hh, int ww) {
-    if (bf || !cw.wino || !wino_v_ || cw.wino_tile != 4 || cw.wino43_x3 || cw.wino43_fused || cw.cin != cw.cout) return false;
-    size_t wm, wa, T;
-    wino_dims(cw, hh, ww, wm, wa, T);
-    return wa * T * (size_t)cw.cin * 4 < ((size_t)1 << 31) && winograd43_out_in_fits(hh, ww, cw.cout);
-  };
 
   // 3x3 s1 conv + BN (+ residual) + ReLU of the deep layers as Winograd F(2x2,3x3): input transform, sixteen
   // [tiles x Cin] x [Cin x Cout] GEMMs in one batched launch, output transform with the epilogue (f32 only)
   auto conv3x3 = [&](const char* name, const ConvW& cw, const void* src, int hh, int ww, void* out, const void* residual,
                      bool relu = true) {
-    if (!bf && cw.wino43_x3) {  // transforms fused into the GEMM kernel, the GEMMs on the bf16 matrix cores (split-bf16)
-      rec.begin();
-      launch_winograd43_x3(static_cast<const float*>(src), cw.wino43_x3, cw.scale, cw.bias, static_cast<const float*>(residual),
-                           relu ? 1 : 0, static_cast<float*>(out), n, hh, ww, cw.cin, cw.cout, num_cus_, cs);
-      const double px43 = (double)n * hh * ww;
-      rec.end(cw.cin == 64 ? "winograd43_fused_x3<c64>" : cw.cin == 128 ? "winograd43_fused_x3<c128>" : "winograd43_fused_x3<c256>",
-              2.0 * 36.0 * (px43 / 16.0) * cw.cin * cw.cout, px43 * 4.0 * (cw.cin + cw.cout * (residual ? 2.0 : 1.0)) + 36.0 * cw.cin * cw.cout * 6);
-      return;
-    }
     if (!bf && cw.wino43_fused) {  // transforms fused into the GEMM kernel
       {
         rec.begin();
@@ -1162,24 +1130,9 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
           sc.residual = d_[l];
         }
       }
-      if (transform_fuse_ && wino43_unfused(layer_[l][0][1], ho, wo) && wino43_unfused(layer_[l][1][0], ho, wo) && wino43_unfused(layer_[l][1][1], ho, wo)) {
-        // three unfused F(4x4) convs in a row (layer3 / layer4): conv1's output inside block 1 is read by conv2 only - M -> y -> V in one
-        // launch, the activation never reaches HBM (model.rs:40-55)
-        // (the pair around the block boundary keeps its two launches: there y = a_[l] must be written anyway - the residual of block 1 -
-        // and the fused launch, one workgroup per CU for its LDS image, is slower than the two streaming kernels: 0.107 vs 0.077 ms at H/16)
-        wino_in(layer_[l][0][1], t_[l], ho, wo);
-        wino_gemm("layer.conv2", layer_[l][0][1], ho, wo);
-        wino_out(layer_[l][0][1], ho, wo, a_[l], sc.residual, true);
-        wino_in(layer_[l][1][0], a_[l], ho, wo);
-        wino_gemm("layer.conv1", layer_[l][1][0], ho, wo);
-        wino_out_in(layer_[l][1][0], ho, wo, nullptr, nullptr, true);
-        wino_gemm("layer.conv2", layer_[l][1][1], ho, wo);
-        wino_out(layer_[l][1][1], ho, wo, x_[l], a_[l], true);
-      } else {
-        conv3x3("layer.conv2", layer_[l][0][1], t_[l], ho, wo, a_[l], sc.residual);
-        conv3x3("layer.conv1", layer_[l][1][0], a_[l], ho, wo, t_[l], nullptr);
-        conv3x3("layer.conv2", layer_[l][1][1], t_[l], ho, wo, x_[l], a_[l]);
-      }
+      conv3x3("layer.conv2", layer_[l][0][1], t_[l], ho, wo, a_[l], sc.residual);
+      conv3x3("layer.conv1", layer_[l][1][0], a_[l], ho, wo, t_[l], nullptr);
+      conv3x3("layer.conv2", layer_[l][1][1], t_[l], ho, wo, x_[l], a_[l]);
     }
     cur = x_[l];
     if (l == 0) grid_cus = num_cus_;   // (the tracer of the previous batch is done by now: 1.1 ms against stem + layer1 = 1.1 ms f32)

@@ -46,7 +46,6 @@ struct ConvW {
   size_t wino_bytes = 0;
   int wino_tile = 2;       // ... or F(4x4,3x3), [36][Cout][Cin], where the option winograd43 asks for it
   float* wino43_fused = nullptr;  // F(4x4,3x3) weights as MFMA B fragments for winograd43_fused.hip (Cin 64 / 128)
-  void* wino43_x3 = nullptr;      // ... as three bf16 planes of B fragments for winograd43_x3.hip (mfma=split_bf16)
   int up = 0;              // STORE_PHASE convs: upsampling factor (weights hold up*up phase sets)
   float* scale = nullptr;  // folded eval batch norm, may stay null
   float* bias = nullptr;
@@ -61,6 +60,7 @@ class Detector {
   void set_stream(hipStream_t s) { stream_ = s ? s : own_stream_; }
   hipStream_t stream() const { return stream_; }
   int device() const { return device_; }
+  int num_cus() const { return num_cus_; }
   void synchronize();
   // 0: f32 everywhere (default).  1: trunk / FPN activations and conv weights in bf16, f32 accumulate,
   // f32 folded batch norm, f32 probability head (BASELINE config 5).
@@ -187,7 +187,6 @@ class Detector {
   // option bin_pyr=0 keeps the four-launch form.
   ConvW bin_pyr_;
   bool bin_pyr_on_ = true;
-  bool x3_wide_ = false;        // split-bf16 convs with NHWC stores and Cout % 128 == 0 on the 256 x 128 persistent form (conv_x3w.hip); 0: conv_igemm's 128-wide tiles.  Same bits
   bool bf16_block_fuse_ = true;  // bf16 precision: layer1's BasicBlocks as one launch each (basic_block_bf16_c64.hip); 0: two conv3x3_bf16_c64 launches.  Same bits
   bool phase_windows_ = true;   // split-bf16 up-2 phase convs indexed by 2 x 2 windows: one operand tile for the four phases (0: one 64-column tile per phase)
   bool pyr_grouped_ = true;     // split-bf16 / bf16 bin_conv1 over p5..p3: phase blocks as 128-column tiles + the corner phases (0: one 64-column tile per phase)
@@ -203,12 +202,8 @@ class Detector {
   float *wino_v_ = nullptr, *wino_m_ = nullptr;  // [(m+2)^2][T][C] and [(m+2)^2][T][K] scratch of the layer in flight
   void add_winograd_weights(ConvW& cw);
   void add_winograd_fused_weights(ConvW& cw);
-  bool winograd43_x3_ = false;   // option winograd43_x3=1: the fused F(4x4,3x3) convs on the bf16 matrix cores too (winograd43_x3.hip; measured
-                                 // slower than the f32-MFMA kernel, DESIGN.md section 3 - kept selectable for A/B)
   bool out4_fused_ = false;      // option out4_fused=1: out4 (256 -> 64 at H/16) on the fused F(4x4,3x3) kernel (0.102 ms) instead of the
                                  // unfused path of layer3 / layer4 (transform + split-bf16 GEMM + transform: 0.084 ms)
-  bool transform_fuse_ = false;  // option transform_fuse=1: inside block 1 of layer3 / layer4 the output transform of conv1 and the input transform of conv2 as one
-                                 // launch (winograd.hip; bit-identical, measured: no gain - DESIGN.md section 9 - so off)
   bool winograd_fused_ = true;   // option winograd_fused=0: direct / unfused-Winograd convs instead of the fused F(4x4,3x3) kernel
   // option mfma=split_bf16 (default) | f32: the MFMA-bound f32 convs without a Winograd kernel of their own (stride-2 3x3,
   // composed FPN phase convs, bin_conv1 over the pyramid, the 36 Winograd GEMMs of layer3 / layer4) run on the bf16 matrix

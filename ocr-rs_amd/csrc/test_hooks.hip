@@ -6,11 +6,12 @@
 #include <cstring>
 
 #include "api_internal.hpp"
+#include "test_kernels.hpp"
 
 using ocr::guard;
 namespace ocr { void winograd43_set_debug(int d); }
 #ifdef W43_STAMPS
-namespace ocr { void winograd43_read_stamps(long long* out); void winograd43_x3_read_stamps(long long* out); }
+namespace ocr { void winograd43_read_stamps(long long* out); }
 #endif
 #ifdef STEM_STAMPS
 namespace ocr { void stem_read_stamps(long long* out); }
@@ -18,6 +19,13 @@ extern "C" int ocr_test_stem_stamps(long long* out) { ocr::stem_read_stamps(out)
 #endif
 #ifdef WS_STAMPS
 #endif
+
+// the conv hooks' launch: the 256 x 128 persistent split-bf16 form (conv_x3w.hip, in this library only) where it is asked for and takes
+// the launch, conv_igemm otherwise
+static void launch_conv(const ocr::ConvDesc& d, bool wide, int cus, hipStream_t s) {
+  if (wide && ocr::conv_x3_wide_applicable(d)) ocr::launch_conv_x3_wide(d, cus, s);
+  else ocr::launch_conv_igemm(d, s);
+}
 
 extern "C" {
 
@@ -345,7 +353,6 @@ int ocr_test_conv_run(ocr_det_t* det, int in_bf16, int out_bf16, const float* in
     }
     if (variant == 2 || variant == 3) {  // the split-bf16 form of the f32 conv: weights as three bf16 planes; 3: the 256 x 128 persistent kernel
       if (variant == 3 && !conv_x3_wide_applicable([&] { ConvDesc t = d; t.x3 = 1; return t; }())) fail(OCR_ERR_INVALID, "variant 3: the wide split-bf16 form does not take this launch");
-      d.wide = variant == 3 ? 1 : 0;
       if (in_bf16 || out_bf16 || cat4) fail(OCR_ERR_INVALID, "variant 2 (split bf16) takes f32 tensors");
       const std::vector<uint16_t> planes = split3_weights_tiled(wgt, w_e, ks * ks * cin);
       void* d_pl = nullptr;
@@ -356,7 +363,7 @@ int ocr_test_conv_run(ocr_det_t* det, int in_bf16, int out_bf16, const float* in
       d.wgt = d_pl;
       d.wgt_bytes = planes.size() * 2;
     }
-    launch_conv_igemm(d, s);
+    launch_conv(d, variant == 3, det->impl.num_cus(), s);
     OCR_HIP(hipStreamSynchronize(s));
     down(out, d_out, out_e, out_bf16);
     down(out2, d_out2, out_e, out_bf16);
@@ -729,7 +736,6 @@ int ocr_test_conv_bench(ocr_det_t* det, int n, int h, int w, int cin, int cout, 
     }
     ConvDesc d{};
     d.x3 = x3;
-    d.wide = wide;
     d.src[0] = in;
     d.src_mode = SRC_PLAIN;
     const int bf = src_mode == 16 ? 1 : 0;  // src_mode 16: bf16 operands and output (the buffers are just reinterpreted)
@@ -741,9 +747,9 @@ int ocr_test_conv_bench(ocr_det_t* det, int n, int h, int w, int cin, int cout, 
     hipEvent_t e0, e1;
     OCR_HIP(hipEventCreate(&e0));
     OCR_HIP(hipEventCreate(&e1));
-    launch_conv_igemm(d, s);
+    launch_conv(d, wide, det->impl.num_cus(), s);
     OCR_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) launch_conv_igemm(d, s);
+    for (int i = 0; i < iters; ++i) launch_conv(d, wide, det->impl.num_cus(), s);
     OCR_HIP(hipEventRecord(e1, s));
     OCR_HIP(hipStreamSynchronize(s));
     float ms = 0.f;

@@ -28,7 +28,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "common.hpp"
+#include "test_kernels.hpp"
 
 namespace ocr {
 namespace {
