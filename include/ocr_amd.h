@@ -87,6 +87,12 @@ int ocr_det_create(const void* weights, size_t weights_bytes, int device, ocr_de
  *                               launches (lateral terms of p2 / p3) and bin_conv1's p2 term - f32 matrix instructions - beside layer2 / layer3 / layer4 /
  *                               the small FPN convs - bf16 matrix instructions and HBM-bound transforms: 2 % of the step in both precisions (default kernels;
  *                               otherwise, and under ocr_det_forward_profile, one stream).  Sums re-associate by one rounding.  Any other value is OCR_ERR_INVALID
+ *   front_split=auto|0|<k> (auto) where overlap=3 is in effect (so never under ocr_det_forward_profile) and the batch has at least two frames: stem, layer1
+ *                               and layer2 run as two frame groups, frames [0, k) on the main stream and [k, N) on the second stream, joined before layer3.
+ *                               Every launch of the front is independent per frame; the group that is a launch behind fills the ragged last round of the
+ *                               other's persistent grids.  Same workspace (a group is a pointer offset), same kernels, the same bits.  0 = off; k >= N = no
+ *                               split; auto = two halves, in the f32 precision, when a half fills the resident slots of layer1's persistent grids once (5.12 frames of
+ *                               640 x 640 on 256 CUs) and no pipelined batch is pending on the handle.  A negative or unparsable value is OCR_ERR_INVALID
  *   bf16_block_fuse=0|1  (1)    bf16 precision: each BasicBlock of layer1 (conv3x3 + BN + ReLU, conv3x3 + BN, + x, ReLU: model.rs:40-55) as ONE launch, the
  *                               activation between its two convs held in LDS (basic_block_bf16_c64.hip): half the HBM traffic of the two launches, 1.25 x
  *                               their matrix work, 5-10 % less time; 0 = two conv3x3_bf16_c64 launches.  The same bits either way
@@ -178,6 +184,9 @@ void ocr_host_free(void* p);
 int ocr_det_forward_async(ocr_det_t* det, const float* x_dev, int n, int h, int w, float* prob_dev,
                           uint8_t* bitmap_dev, float thresh);
 int ocr_det_synchronize(ocr_det_t* det);
+/* Which schedule the most recent forward of this handle took (engine option front_split): *k = frames of the first frame group, 0 = it ran
+ * unsplit (the last chunk's, for a batch that ran in several).  Results never depend on it. */
+int ocr_det_last_front_split(ocr_det_t* det, int32_t* k);
 
 /* Per-kernel timing of one forward (hipEvents on the handle's stream around every
  * launch).  names[i] points to a static string; ms/flops/bytes are per launch:

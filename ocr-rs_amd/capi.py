@@ -26,7 +26,7 @@ EXPORTS = [
     "ocr_varstore_to_blob", "ocr_blob_free", "ocr_det_create_from_varstore", "ocr_rec_create_from_varstore",
     "ocr_det_create", "ocr_det_create_with_options", "ocr_det_destroy", "ocr_det_set_stream", "ocr_det_set_precision", "ocr_det_forward",
     "ocr_det_forward_u8", "ocr_host_alloc", "ocr_host_free", "ocr_det_detect_pipelined_host",
-    "ocr_det_forward_async", "ocr_det_synchronize", "ocr_det_forward_profile",
+    "ocr_det_forward_async", "ocr_det_synchronize", "ocr_det_last_front_split", "ocr_det_forward_profile",
     "ocr_preprocess_image", "ocr_postproc_default_params", "ocr_det_postprocess", "ocr_det_post_stats", "ocr_det_detect_pipelined", "ocr_polygons_free",
     "ocr_extract_crops", "ocr_segment_default_params", "ocr_segment_glyphs", "ocr_extract_glyph_crops", "ocr_glyphs_free",
     "ocr_cc_default_params", "ocr_segment_glyphs_cc",
@@ -553,6 +553,14 @@ class Detector:
 
     def synchronize(self) -> None:
         check(lib().ocr_det_synchronize(self._h))
+
+    def last_front_split(self) -> int:
+        """Frames of the first frame group of the most recent forward (option front_split); 0 = it ran unsplit."""
+        k = C.c_int32(-1)
+        f = lib().ocr_det_last_front_split   # (bound here: A/B runs load libraries built before this entry point existed)
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        check(f(self._h, C.byref(k)))
+        return int(k.value)
 
     def forward_host(self, x: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)

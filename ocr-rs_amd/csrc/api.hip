@@ -168,6 +168,13 @@ int ocr_det_forward_async(ocr_det_t* det, const float* x, int n, int h, int w, f
   });
 }
 
+int ocr_det_last_front_split(ocr_det_t* det, int32_t* k) {
+  return guard([&] {
+    if (!det || !k) ocr::fail(OCR_ERR_INVALID, "det_last_front_split: null argument");
+    *k = det->impl.last_front_split();
+  });
+}
+
 int ocr_det_synchronize(ocr_det_t* det) {
   return guard([&] {
     if (!det) ocr::fail(OCR_ERR_INVALID, "null handle");

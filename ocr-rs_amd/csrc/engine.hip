@@ -252,6 +252,13 @@ void Detector::parse_options(const char* options) {
       overlap_ = num();
       if (overlap_ < 0 || overlap_ > 3) fail(OCR_ERR_INVALID, "detector option overlap: %d (0, 1, 2 or 3)", overlap_);
     }
+    else if (key == "front_split") {
+      if (val == "auto") front_split_ = -1;
+      else {
+        front_split_ = num();
+        if (front_split_ < 0) fail(OCR_ERR_INVALID, "detector option front_split: %d (auto, 0 or the first group's frames)", front_split_);
+      }
+    }
     else if (key == "w43_cus") {
       w43_cus_ = num();
       if (w43_cus_ < 0 || w43_cus_ > 4096) fail(OCR_ERR_INVALID, "detector option w43_cus: %d", w43_cus_);
@@ -793,6 +800,9 @@ void Detector::ensure_workspace(int n, int h, int w) {
 }
 
 namespace {
+// front_split=auto: the smaller frame group must fill the resident slots of layer1's persistent grids (two workgroups per CU) this many times
+constexpr long long kFrontSplitMinRounds = 1;
+
 // hipEvent pairs around every launch of ONE forward_chunk; entries are appended to the shared `prof` vector,
 // so a batch that runs in several chunks keeps every chunk's launches (base = first entry of this chunk).
 struct Recorder {
@@ -893,6 +903,52 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
     OCR_HIP(hipEventRecord(ev_join_, side_stream_));
   };
   auto join = [&] { OCR_HIP(hipStreamWaitEvent(stream_, ev_join_, 0)); };
+  // Frame range [fr0, fr0 + frn) of the launches below: the whole batch, except in the split front (front_split), where
+  // stem .. layer2 run as two frame groups, the second on the side stream.  Every activation buffer is frame-major: a group is a pointer offset.
+  int fr0 = 0, frn = n;
+  bool in_front = false;   // a launch of the split front: its persistent grid is sized like a main-stream launch on either stream
+  auto at = [&](auto* p, size_t frame_bytes) -> decltype(p) {
+    return p && fr0 ? reinterpret_cast<decltype(p)>(reinterpret_cast<uintptr_t>(p) + (size_t)fr0 * frame_bytes) : p;
+  };
+  // front_split: where overlap=3 is in effect, and every conv of layer1 / layer2 is ONE launch without shared scratch (fused Winograd or conv_igemm).
+  // auto (f32 precision): two halves, not while a pipelined call's previous batch is pending (its post-processing runs beside this forward: with
+  // the polygon chain on the device layer1's grids are oversubscribed for it, head_cus_yield; with the chain on the host pool the split measured
+  // 2 - 3 % slower), and only where a half still fills every resident slot of layer1's grids once (two workgroups per CU, a block =
+  // 16 x 16 pixels at H/4): measured, 32 and 16 frames of 640 x 640 gain 2.4 % and 3.6 %, 8 frames lose 3 %
+  auto one_launch = [&](const ConvW& cw) { return bf || cw.wino43_fused || !cw.wino || !wino_v_; };
+  int front_k = 0;
+  if (overlap3 && n >= 2 && front_split_ != 0 && one_launch(layer_[0][0][0]) && one_launch(layer_[0][0][1]) && one_launch(layer_[0][1][0]) &&
+      one_launch(layer_[0][1][1]) && one_launch(layer_[1][0][1]) && one_launch(layer_[1][1][0]) && one_launch(layer_[1][1][1])) {
+    if (front_split_ > 0) front_k = front_split_ < n ? front_split_ : 0;
+    else if (!bf && !pending_.valid && (long long)(n / 2) * ((h / 4 + 15) / 16) * ((w / 4 + 15) / 16) >= kFrontSplitMinRounds * 2ll * num_cus_) front_k = n / 2;
+  }
+  struct Group {
+    hipStream_t s;
+    int f0, nf;
+  };
+  Group groups[2] = {{stream_, 0, n}, {side_stream_, front_k, n - front_k}};
+  last_front_k_ = front_k;
+  int ngroups = 1;
+  if (front_k) {
+    groups[0].nf = front_k;
+    ngroups = 2;
+    in_front = true;
+    // the side stream's first launch sits behind everything queued on the main stream: the previous call, the copy that brings x in
+    OCR_HIP(hipEventRecord(ev_fork_, stream_));
+    OCR_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0));
+  }
+  // one launch per frame group, alternating, so that both streams stay fed
+  auto per_group = [&](auto&& launch) {
+    for (int g = 0; g < ngroups; ++g) {
+      cs = groups[g].s;
+      fr0 = groups[g].f0;
+      frn = groups[g].nf;
+      launch();
+    }
+    cs = stream_;
+    fr0 = 0;
+    frn = n;
+  };
   auto conv = [&](const char* name, const ConvW& cw, const void* src, int hin, int win, int stride, void* out,
                   bool relu, const Extra& ex = Extra()) {
     ConvDesc d{};
@@ -905,7 +961,9 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
     d.pyr_group = ex.pyr_group;
     d.up = cw.up;
     const size_t ies = in_bf ? 2 : 4;
-    d.src[0] = src;
+    if (frn != n && (ex.cat4 || ex.pyr4 || ex.up_residual || ex.store != STORE_NHWC))
+      fail(OCR_ERR_INTERNAL, "conv %s: a frame group of a launch that is not frame-major", name);
+    d.src[0] = at(src, (size_t)hin * win * cw.cin * ies);
     d.src_mode = ex.cat4 ? SRC_CAT4 : ex.pyr4 ? SRC_PYR4 : SRC_PLAIN;
     if (ex.cat4 || ex.pyr4) {
       d.src[0] = p_[3];
@@ -915,10 +973,10 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
       d.src_base = pcat_;
       d.src_bytes = pcat_bytes_;
     } else {
-      d.src_bytes = (size_t)n * hin * win * cw.cin * ies;
+      d.src_bytes = (size_t)frn * hin * win * cw.cin * ies;
     }
     d.wgt_bytes = in_bf ? cw.w_bytes / 2 : cw.w_bytes;
-    d.N = n;
+    d.N = frn;
     d.Hin = hin;
     d.Win = win;
     d.Cin = cw.cin;
@@ -938,16 +996,17 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
     if ((d.x3 || in_bf) && ex.store == STORE_PHASE && !ex.pyr4 && cw.up == 2 && cw.cout == 64 && phase_windows_) d.win = 1;
     d.scale = cw.scale;
     d.bias = cw.bias;
-    d.residual = ex.residual;
+    const size_t out_frame = (size_t)d.Ho * d.Wo * cw.cout * (d.out_bf16 ? 2 : 4);   // (NHWC stores; the others run on the whole batch)
+    d.residual = at(ex.residual, out_frame);
     d.up_residual = ex.up_residual;
-    d.out2 = ex.out2;
+    d.out2 = at(ex.out2, out_frame);
     d.relu = relu ? 1 : 0;
     d.store_mode = ex.store;
-    d.out = out;
+    d.out = at(out, out_frame);
     d.name = name;
     rec.begin();
     launch_conv_igemm(d, cs);
-    const double M = (double)n * d.Ho * d.Wo;
+    const double M = (double)frn * d.Ho * d.Wo;
     const double reps = ex.store == STORE_PHASE ? (double)(cw.up * cw.up) : 1.0;  // phase convs per low-res pixel
     // taps executed per low-res pixel over all phases: (up + 2)^2 (edge phases 2, inner phases 1 per direction)
     // PYR4 per cell: (8+2)^2 + 4 (4+2)^2 + 16 (2+2)^2 tap-phases of the upsampled levels + 64 * 9 of p2
@@ -965,10 +1024,15 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
   };
 
   const int h4 = h / 4, w4 = w / 4;
+  auto stem = [&] {
+    const void* xg = at(x, (size_t)h * w * (x_u8 ? 1 : 4));
+    char* sg = at(s_, (size_t)h4 * w4 * 64 * es);
+    if (bf) launch_stem_bf16(xg, x_u8, stem_wb_, stem_scale_, stem_bias_, sg, frn, h, w, cs);
+    else if (stem_wx3_) launch_stem_x3(xg, x_u8, stem_wx3_, stem_scale_, stem_bias_, reinterpret_cast<float*>(sg), frn, h, w, cs);
+    else launch_stem(xg, x_u8, stem_w_, stem_scale_, stem_bias_, sg, 0, frn, h, w, cs);
+  };
   rec.begin();
-  if (bf) launch_stem_bf16(x, x_u8, stem_wb_, stem_scale_, stem_bias_, s_, n, h, w, stream_);
-  else if (stem_wx3_) launch_stem_x3(x, x_u8, stem_wx3_, stem_scale_, stem_bias_, reinterpret_cast<float*>(s_), n, h, w, stream_);
-  else launch_stem(x, x_u8, stem_w_, stem_scale_, stem_bias_, s_, 0, n, h, w, stream_);
+  per_group(stem);
   rec.end(!bf && stem_wx3_ ? "stem_x3_conv7x7_bn_relu_maxpool" : "stem_conv7x7_bn_relu_maxpool", 2.0 * n * (h / 2) * (w / 2) * 64 * 49,
           (double)n * h * w * (x_u8 ? 1 : 4) + (double)n * h4 * w4 * 64 * (double)es);
 
@@ -1035,10 +1099,13 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
     if (!bf && cw.wino43_fused) {  // transforms fused into the GEMM kernel
       {
         rec.begin();
-        launch_winograd43_fused(static_cast<const float*>(src), cw.wino43_fused, cw.scale, cw.bias, static_cast<const float*>(residual),
-                                relu ? 1 : 0, static_cast<float*>(out), n, hh, ww, cw.cin, cw.cout,
-                                cs != stream_ && w43_side_cus_ > 0 ? w43_side_cus_ : w43_cus_ > 0 ? w43_cus_ : cs == stream_ ? grid_cus : num_cus_, cs);
-        const double px43 = (double)n * hh * ww;
+        const size_t px_bytes = (size_t)hh * ww * 4;
+        const bool side = cs != stream_ && !in_front;
+        launch_winograd43_fused(static_cast<const float*>(at(src, px_bytes * cw.cin)), cw.wino43_fused, cw.scale, cw.bias,
+                                static_cast<const float*>(at(residual, px_bytes * cw.cout)), relu ? 1 : 0, static_cast<float*>(at(out, px_bytes * cw.cout)),
+                                frn, hh, ww, cw.cin, cw.cout,
+                                side && w43_side_cus_ > 0 ? w43_side_cus_ : w43_cus_ > 0 ? w43_cus_ : side ? num_cus_ : grid_cus, cs);
+        const double px43 = (double)frn * hh * ww;
         rec.end(cw.cin == 64 ? "winograd43_fused<c64>" : cw.cin == 128 ? "winograd43_fused<c128>" : "winograd43_fused<c256>", 2.0 * 36.0 * (px43 / 16.0) * cw.cin * cw.cout,
                 px43 * 4.0 * (cw.cin + cw.cout * (residual ? 2.0 : 1.0)) + 36.0 * cw.cin * cw.cout * 4);
         return;
@@ -1046,8 +1113,10 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
     }
     if (bf && cw.w_bf16_c64 && (long long)n * hh * ww * 128 < (1ll << 31)) {  // bf16 64 -> 64: patch staged once, weights in registers
       rec.begin();
-      launch_conv3x3_bf16_c64(src, cw.w_bf16_c64, cw.scale, cw.bias, residual, relu ? 1 : 0, out, n, hh, ww, cs == stream_ ? grid_cus : num_cus_, cs);
-      const double px = (double)n * hh * ww;
+      const size_t fb = (size_t)hh * ww * 64 * 2;
+      launch_conv3x3_bf16_c64(at(src, fb), cw.w_bf16_c64, cw.scale, cw.bias, at(residual, fb), relu ? 1 : 0, at(out, fb), frn, hh, ww,
+                              cs == stream_ || in_front ? grid_cus : num_cus_, cs);
+      const double px = (double)frn * hh * ww;
       rec.end("conv3x3_bf16_c64", 2.0 * px * 64 * 576, px * 2.0 * 64 * (residual ? 3.0 : 2.0) + 9.0 * 64 * 64 * 2);
       return;
     }
@@ -1059,6 +1128,7 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
       conv(name, cw, src, hh, ww, 1, out, relu, ex);
       return;
     }
+    if (frn != n) fail(OCR_ERR_INTERNAL, "conv %s: a frame group of the three-launch Winograd form (shared scratch)", name);
     wino_in(cw, src, hh, ww);
     wino_gemm(name, cw, hh, ww);
     wino_out(cw, hh, ww, out, residual, relu);
@@ -1105,11 +1175,14 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
       // the two conv3x3_bf16_c64 launches; model.rs:40-55)
       const void* bin = cur;
       void* bout[2] = {a_[0], x_[0]};
+      const size_t fb = (size_t)ho * wo * 64 * 2;
       for (int b = 0; b < 2; ++b) {
         const ConvW &c1 = layer_[0][b][0], &c2 = layer_[0][b][1];
         rec.begin();
-        launch_basic_block_bf16_c64(bin, c1.w_bf16_c64, c1.scale, c1.bias, c2.w_bf16_c64, c2.scale, c2.bias, bout[b], n, ho, wo,
-                                    cs == stream_ ? grid_cus : num_cus_, cs);
+        per_group([&] {
+          launch_basic_block_bf16_c64(at(bin, fb), c1.w_bf16_c64, c1.scale, c1.bias, c2.w_bf16_c64, c2.scale, c2.bias, at(bout[b], fb), frn, ho, wo,
+                                      cs == stream_ || in_front ? grid_cus : num_cus_, cs);
+        });
         const double px = (double)n * ho * wo;
         rec.end("basic_block_bf16_c64", 2.0 * 2.0 * px * 64 * 576, px * 2.0 * 64 * 2.0 + 2.0 * 9.0 * 64 * 64 * 2);
         bin = bout[b];
@@ -1123,16 +1196,16 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
         join();
         sc.residual = d_[l];
       } else {
-        if (l == 0) conv3x3("layer.conv1", layer_[l][0][0], cur, hin, win, t_[l], nullptr);  // stride 1 in layer1
-        else conv("layer.conv1", layer_[l][0][0], cur, hin, win, stride, t_[l], true);
+        if (l == 0) per_group([&] { conv3x3("layer.conv1", layer_[l][0][0], cur, hin, win, t_[l], nullptr); });  // stride 1 in layer1
+        else per_group([&] { conv("layer.conv1", layer_[l][0][0], cur, hin, win, stride, t_[l], true); });
         if (l > 0) {
-          conv("layer.downsample", down_[l], cur, hin, win, stride, d_[l], false);
+          per_group([&] { conv("layer.downsample", down_[l], cur, hin, win, stride, d_[l], false); });
           sc.residual = d_[l];
         }
       }
-      conv3x3("layer.conv2", layer_[l][0][1], t_[l], ho, wo, a_[l], sc.residual);
-      conv3x3("layer.conv1", layer_[l][1][0], a_[l], ho, wo, t_[l], nullptr);
-      conv3x3("layer.conv2", layer_[l][1][1], t_[l], ho, wo, x_[l], a_[l]);
+      per_group([&] { conv3x3("layer.conv2", layer_[l][0][1], t_[l], ho, wo, a_[l], sc.residual); });
+      per_group([&] { conv3x3("layer.conv1", layer_[l][1][0], a_[l], ho, wo, t_[l], nullptr); });
+      per_group([&] { conv3x3("layer.conv2", layer_[l][1][1], t_[l], ho, wo, x_[l], a_[l]); });
     }
     cur = x_[l];
     if (l == 0) grid_cus = num_cus_;   // (the tracer of the previous batch is done by now: 1.1 ms against stem + layer1 = 1.1 ms f32)
@@ -1143,13 +1216,27 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
       // its upsampled term, bin_conv1's p2 term (into layer1's free temporary) and p3's lateral term follow layer2, p3's upsampled term
       // layer3.  Sums are re-associated (lateral + upsampled instead of upsampled + lateral: the same bits; pyramid + bias + p2 term instead
       // of p2 term + bias + pyramid: one rounding apart)
+      // Split front: the side stream first takes the second group through layer2, and the main stream waits for that before layer3; the
+      // side work follows it, and as it reads whole-batch x_[0] / x_[1], it waits for the first group's layer1 / layer2 as before
       OCR_HIP(hipEventRecord(ev_x1_, stream_));
-      OCR_HIP(hipStreamWaitEvent(side_stream_, ev_x1_, 0));
-      cs = side_stream_;
-      conv3x3("fpn.lateral", fpn_a_[0], x_[0], h4, w4, p_[0], nullptr, false);
-      cs = stream_;
+      if (!front_k) {
+        OCR_HIP(hipStreamWaitEvent(side_stream_, ev_x1_, 0));
+        cs = side_stream_;
+        conv3x3("fpn.lateral", fpn_a_[0], x_[0], h4, w4, p_[0], nullptr, false);
+        cs = stream_;
+      }
     } else if (overlap3 && l == 1) {
       OCR_HIP(hipEventRecord(ev_x2_, stream_));
+      if (front_k) {
+        ngroups = 1;   // from layer3 on: the whole batch
+        groups[0].nf = n;
+        in_front = false;
+        OCR_HIP(hipEventRecord(ev_join_, side_stream_));
+        join();
+        OCR_HIP(hipStreamWaitEvent(side_stream_, ev_x1_, 0));
+        cs = side_stream_;
+        conv3x3("fpn.lateral", fpn_a_[0], x_[0], h4, w4, p_[0], nullptr, false);
+      }
       OCR_HIP(hipStreamWaitEvent(side_stream_, ev_x2_, 0));
       cs = side_stream_;
       {

@@ -66,6 +66,7 @@ class Detector {
   // f32 folded batch norm, f32 probability head (BASELINE config 5).
   void set_precision(int precision);
   int precision() const { return bf16_ ? 1 : 0; }
+  int last_front_split() const { return last_front_k_; }   // ocr_det_last_front_split
   // device pointers; enqueues on stream().  prof != null -> per-launch events.
   // x: N x 1 x H x W frames, f32 or (x_u8 != 0) u8 raw luma; wait_for: an event the first launch waits for (the
   // copy that brings x in), may be null
@@ -163,6 +164,11 @@ class Detector {
                            // engine; anything else falls back to the one-stream schedule)
   int w43_side_cus_ = 0;   // ... of the fused Winograd launches that go to the side stream (overlap >= 2): room for the main stream's workgroups beside them
   int w43_cus_ = 0;        // option w43_cus (tuning): size the fused Winograd kernels' persistent grids for this many CUs (0 = the device's)
+  // option front_split: stem .. layer2 as two frame groups, [0, k) on the main stream and [k, n) on the side stream, where
+  // overlap=3 is in effect - the group that is a launch behind fills the ragged last round of the other's persistent grids.  -1: auto, 0: off,
+  // k > 0: the first group's frames (k >= n: no split)
+  int front_split_ = -1;
+  int last_front_k_ = 0;   // frames of the first group in the most recent forward_chunk (0: it ran unsplit)
   hipStream_t side_stream_ = nullptr;
   hipEvent_t ev_x1_ = nullptr, ev_x2_ = nullptr, ev_x3_ = nullptr, ev_side_ = nullptr, ev_fork_ = nullptr, ev_join_ = nullptr;
   DeviceArena arena_;
