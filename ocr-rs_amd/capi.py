@@ -252,6 +252,10 @@ def test_lib() -> C.CDLL:
         L.ocr_test_winograd_conv.argtypes = ([C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int] +
                                              [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p])
         L.ocr_test_det_stage.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ocr_test_stem_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4
+        L.ocr_test_head_run.argtypes = ([C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_float, C.c_float] +
+                                        [C.c_void_p] * 2)
+        L.ocr_test_rec_features.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.ocr_test_comm_assemble.argtypes = [C.POINTER(C.POINTER(Polygons)), C.c_int, C.POINTER(C.POINTER(Polygons))]
         _test_lib = L
     return _test_lib
@@ -771,6 +775,34 @@ class Detector:
                                            p(out), p(out2)))
         return out, out2
 
+    def debug_stem_run(self, form, frames, w64x49, scale64, bias64):
+        """The stem alone on caller data (test hook): form 0 exact f32, 1 bf16 precision, 2 split bf16.  frames: N x H x W, uint8 (raw luma)
+        or f32; w64x49: conv1.weight as [64][49].  Returns N x H/4 x W/4 x 64 f32 (form 1: the bf16 output widened)."""
+        x = np.ascontiguousarray(frames)
+        if x.dtype != np.uint8:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        n, h, w = x.shape
+        f = lambda a, shape: np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
+        wg, sc, bi = f(w64x49, (64, 49)), f(scale64, (64,)), f(bias64, (64,))
+        out = np.empty((n, h // 4, w // 4, 64), np.float32)
+        check(test_lib().ocr_test_stem_run(self._h, int(form), _ptr(x), int(x.dtype == np.uint8), n, h, w, _ptr(wg), _ptr(sc), _ptr(bi), _ptr(out)))
+        return out
+
+    def debug_head_run(self, form, y_nhwc, wt1, s4, b4, w2t, bias2=0.0, thresh=0.5, want_bitmap=True):
+        """The fused head alone on caller data (test hook): form 0 f32 MFMA, 1 bf16 operands (y and wt1 rounded inside), 2 split bf16.
+        y: N x h4 x w4 x 64; wt1: [4 taps a*2+b][64 co][64 ci]; s4 / b4: [256] (tap * 64 + co); w2t: [64 co][4 u = c'*2+d'].
+        Returns (prob N x 4 h4 x 4 w4 f32, bitmap u8 or None)."""
+        y = np.ascontiguousarray(y_nhwc, dtype=np.float32)
+        n, h4, w4, c = y.shape
+        assert c == 64
+        f = lambda a, shape: np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
+        wt, s, b, w2 = f(wt1, (4, 64, 64)), f(s4, (256,)), f(b4, (256,)), f(w2t, (64, 4))
+        prob = np.empty((n, 4 * h4, 4 * w4), np.float32)
+        bm = np.empty((n, 4 * h4, 4 * w4), np.uint8) if want_bitmap else None
+        check(test_lib().ocr_test_head_run(self._h, int(form), _ptr(y), n, h4, w4, _ptr(wt), _ptr(s), _ptr(b), _ptr(w2), float(bias2), float(thresh),
+                                           _ptr(prob), _ptr(bm) if want_bitmap else None))
+        return prob, bm
+
     def debug_bf16_basic_block(self, x_nhwc, w1, w2, scale1=None, bias1=None, scale2=None, bias2=None, fused=True, num_cus=0, iters=1):
         """one BasicBlock 64 -> 64 of the bf16 precision (test hook): fused = basic_block_bf16_c64.hip (one launch), otherwise two
         conv3x3_bf16_c64 launches.  x N x H x W x 64 f32 (rounded to bf16 inside), w [64][9][64].  Returns (out f32, ms per block)."""
@@ -935,6 +967,17 @@ class Recognizer:
 
     def synchronize(self) -> None:
         check(lib().ocr_rec_synchronize(self._h))
+
+    def debug_rec_features(self, form, crops, w1, b1, w2, b2):
+        """conv1 + pool + conv2 + pool on caller weights (test hook): form 0 the exact-f32 kernel, 1 the small-batch split-bf16 one.
+        crops: n x 784; w1 [32][25], b1 [32], w2 [64][32][25], b2 [64].  Returns n x 1024 f32 in the order co * 16 + p."""
+        f = lambda a, shape: np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
+        x = f(crops, (-1, 784))
+        n = x.shape[0]
+        w1, b1, w2, b2 = f(w1, (32, 25)), f(b1, (32,)), f(w2, (64, 32, 25)), f(b2, (64,))
+        feat = np.empty((n, 1024), np.float32)
+        check(test_lib().ocr_test_rec_features(self._h, int(form), _ptr(x), n, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(feat)))
+        return feat
 
     def set_options(self, options: str) -> None:
         """`small_batch=0`: every batch on the throughput kernels (bit-exact batch-size invariance)."""

@@ -440,6 +440,148 @@ int ocr_test_bf16_basic_block(ocr_det_t* det, const float* x, int n, int h, int 
     }
   });
 }
+}  // extern "C"
+
+// what the stem / head / recogniser hooks below share: host f32 -> bf16 bits (nearest even) and back, device buffers freed on every way out
+namespace {
+uint16_t hook_bf16_bits(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+struct HookBuffers {
+  std::vector<void*> allocs;
+  ~HookBuffers() { for (void* p : allocs) (void)hipFree(p); }
+  void* raw(const void* src, size_t bytes) {   // src == nullptr: zeroed
+    void* d = nullptr;
+    OCR_HIP(hipMalloc(&d, std::max<size_t>(bytes, 16)));
+    allocs.push_back(d);
+    if (src) OCR_HIP(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    else OCR_HIP(hipMemset(d, 0, std::max<size_t>(bytes, 16)));
+    return d;
+  }
+  float* f32(const float* src, size_t elems) { return static_cast<float*>(raw(src, elems * 4)); }
+  void* u16(const std::vector<uint16_t>& v) { return raw(v.data(), v.size() * 2); }
+  void* as_bf16(const float* src, size_t elems) {
+    std::vector<uint16_t> t(elems);
+    for (size_t i = 0; i < elems; ++i) t[i] = hook_bf16_bits(src[i]);
+    return u16(t);
+  }
+};
+}  // namespace
+
+extern "C" {
+
+// the stem alone (stem_tail.hip) on caller data: conv 7x7 s2 p3 (1 -> 64) * scale + bias, ReLU, max pool 3x3 s2 p1.  form 0 = launch_stem
+// (exact f32), 1 = launch_stem_bf16 (bf16 precision; the output is widened to f32), 2 = launch_stem_x3 (split bf16).  x: n x h x w frames, f32
+// or (x_is_u8) u8; w64x49: conv1.weight [64][7][7]; out: [n][h / 4][w / 4][64] f32
+int ocr_test_stem_run(ocr_det_t* det, int form, const void* x, int x_is_u8, int n, int h, int w, const float* w64x49, const float* scale64,
+                      const float* bias64, float* out_nhwc_f32) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !x || !w64x49 || !scale64 || !bias64 || !out_nhwc_f32) fail(OCR_ERR_INVALID, "null argument");
+    if (form < 0 || form > 2 || n <= 0 || h <= 0 || w <= 0) fail(OCR_ERR_INVALID, "stem hook: bad form or shape");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    HookBuffers b;
+    const size_t in_e = (size_t)n * h * w, out_e = (size_t)n * (h / 4) * (w / 4) * 64;
+    void* d_x = b.raw(x, in_e * (x_is_u8 ? 1 : 4));
+    const float* d_sc = b.f32(scale64, 64);
+    const float* d_bi = b.f32(bias64, 64);
+    void* d_out = b.raw(nullptr, out_e * (form == 1 ? 2 : 4));
+    if (form == 0) {   // [64][49] -> [49][64], as the engine uploads it
+      std::vector<float> t(49 * 64);
+      for (int c = 0; c < 64; ++c)
+        for (int k = 0; k < 49; ++k) t[k * 64 + c] = w64x49[c * 49 + k];
+      launch_stem(d_x, x_is_u8, b.f32(t.data(), t.size()), d_sc, d_bi, d_out, 0, n, h, w, s);
+    } else if (form == 1) {
+      launch_stem_bf16(d_x, x_is_u8, b.u16(stem_bf16_fragments(w64x49)), d_sc, d_bi, d_out, n, h, w, s);
+    } else {
+      launch_stem_x3(d_x, x_is_u8, b.u16(stem_x3_fragments(w64x49)), d_sc, d_bi, static_cast<float*>(d_out), n, h, w, s);
+    }
+    OCR_HIP(hipStreamSynchronize(s));
+    if (form == 1) {
+      std::vector<uint16_t> t(out_e);
+      OCR_HIP(hipMemcpy(t.data(), d_out, out_e * 2, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < out_e; ++i) {
+        const uint32_t u = (uint32_t)t[i] << 16;
+        std::memcpy(&out_nhwc_f32[i], &u, 4);
+      }
+    } else {
+      OCR_HIP(hipMemcpy(out_nhwc_f32, d_out, out_e * 4, hipMemcpyDeviceToHost));
+    }
+  });
+}
+// the fused head alone (tail_fused.hip) on caller data: form = launch_tail_fused's `bf16` (0 f32 MFMA, 1 bf16 operands - y and wt1 are
+// rounded on the way in -, 2 split bf16: wt1 as split3_weights planes).  y: [n][h4][w4][64]; wt1: [4 taps][64 co][64 ci]; s4 / b4: [256]
+// (tap * 64 + co); w2t: [64 co][4]; prob: [n][4 h4][4 w4] f32, bitmap (optional) the same shape in u8
+int ocr_test_head_run(ocr_det_t* det, int form, const float* y_nhwc, int n, int h4, int w4, const float* wt1, const float* s4, const float* b4,
+                      const float* w2t, float bias2, float thresh, float* prob_out, uint8_t* bitmap_out_or_null) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !y_nhwc || !wt1 || !s4 || !b4 || !w2t || !prob_out) fail(OCR_ERR_INVALID, "null argument");
+    if (form < 0 || form > 2 || n <= 0 || h4 <= 0 || w4 <= 0) fail(OCR_ERR_INVALID, "head hook: bad form or shape");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    HookBuffers b;
+    const size_t m = (size_t)n * h4 * w4, y_e = m * 64, w_e = (size_t)4 * 64 * 64, px = m * 16;
+    const void* d_y = form == 1 ? b.as_bf16(y_nhwc, y_e) : b.f32(y_nhwc, y_e);
+    const void* d_w = form == 1 ? b.as_bf16(wt1, w_e) : form == 2 ? b.u16(split3_weights(wt1, w_e)) : b.f32(wt1, w_e);
+    float* d_prob = static_cast<float*>(b.raw(nullptr, px * 4));
+    uint8_t* d_bm = bitmap_out_or_null ? static_cast<uint8_t*>(b.raw(nullptr, px)) : nullptr;
+    launch_tail_fused(d_y, d_w, form, b.f32(s4, 256), b.f32(b4, 256), b.f32(w2t, 256), bias2, d_prob, d_bm, thresh, n, h4, w4, s);
+    OCR_HIP(hipStreamSynchronize(s));
+    OCR_HIP(hipMemcpy(prob_out, d_prob, px * 4, hipMemcpyDeviceToHost));
+    if (d_bm) OCR_HIP(hipMemcpy(bitmap_out_or_null, d_bm, px, hipMemcpyDeviceToHost));
+  });
+}
+// conv1 + pool + conv2 + pool of the recogniser (rec_net.hip) on caller weights: form 0 = launch_rec_conv (exact f32, crops per workgroup
+// chosen by n as shipped), 1 = launch_rec_small stage 0 (split-bf16 conv2).  crops: [n][784]; w1: [32][25]; w2: [64][32][25]; feat_out:
+// [n][1024] as k = co * 16 + p in both forms - form 1's kernel writes the operand order of the fc1 kernel, undone here
+int ocr_test_rec_features(ocr_rec_t* rec, int form, const float* crops, int n, const float* w1, const float* b1, const float* w2, const float* b2,
+                          float* feat_out) {
+  return guard([&] {
+    using namespace ocr;
+    if (!rec || !crops || !w1 || !b1 || !w2 || !b2 || !feat_out) fail(OCR_ERR_INVALID, "null argument");
+    if (form < 0 || form > 1 || n <= 0) fail(OCR_ERR_INVALID, "rec hook: bad form or batch");
+    OCR_HIP(hipSetDevice(rec->impl.device()));
+    hipStream_t s = rec->impl.stream();
+    HookBuffers b;
+    RecWeights rw{};
+    rw.c1f = b.f32(rec_conv1_fragments(w1).data(), 13 * 64);
+    rw.c1b = b.f32(b1, 32);
+    rw.c2b = b.f32(b2, 64);
+    const float* d_crops = b.f32(crops, (size_t)n * 784);
+    const size_t tiles = ((size_t)n + 15) / 16;
+    std::vector<float> t(tiles * 16 * 1024);
+    float* d_feat = static_cast<float*>(b.raw(nullptr, t.size() * 4));   // whole 16-crop tiles: the operand order interleaves a tile's crops
+    if (form == 0) {
+      const std::vector<float> f2 = rec_conv2_fragments(w2);
+      rw.c2f = b.f32(f2.data(), f2.size());
+      launch_rec_conv(rw, d_crops, n, d_feat, s);
+    } else {
+      rw.c2x = b.u16(rec_conv2_small_x3_fragments(w2));
+      launch_rec_small(rw, d_crops, n, d_feat, nullptr, nullptr, nullptr, nullptr, s, 0);
+    }
+    OCR_HIP(hipStreamSynchronize(s));
+    OCR_HIP(hipMemcpy(t.data(), d_feat, t.size() * 4, hipMemcpyDeviceToHost));
+    if (form == 0) {
+      std::copy(t.begin(), t.begin() + (size_t)n * 1024, feat_out);
+      return;
+    }
+    // operand order [tile of 16 crops][g: sixteen k][q][r: crop of the tile][e] holds k = 16 g + 4 q + e of crop 16 tile + r
+    for (size_t tile = 0; tile < tiles; ++tile)
+      for (int g = 0; g < 64; ++g)
+        for (int q = 0; q < 4; ++q)
+          for (int r = 0; r < 16; ++r)
+            for (int e = 0; e < 4; ++e) {
+              const size_t crop = tile * 16 + r;
+              if (crop < (size_t)n) feat_out[crop * 1024 + 16 * g + 4 * q + e] = t[((((tile * 64 + g) * 4 + q) * 16 + r) * 4) + e];
+            }
+  });
+}
+
 // one 3x3 s1 p1 conv (+ scale / bias / residual / ReLU) through the Winograd F(2x2,3x3) path on caller data:
 // weight transform, input transform, batched 16-problem GEMM, output transform.  x: NHWC, wgt: [cout][9][cin].
 int ocr_test_winograd_conv(ocr_det_t* det, const float* x, int n, int h, int w, int cin, const float* wgt, int cout,
