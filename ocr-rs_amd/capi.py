@@ -256,6 +256,8 @@ def test_lib() -> C.CDLL:
         L.ocr_test_head_run.argtypes = ([C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_float, C.c_float] +
                                         [C.c_void_p] * 2)
         L.ocr_test_rec_features.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.ocr_test_rec_fc1.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.ocr_test_rec_fc2.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
         L.ocr_test_comm_assemble.argtypes = [C.POINTER(C.POINTER(Polygons)), C.c_int, C.POINTER(C.POINTER(Polygons))]
         _test_lib = L
     return _test_lib
@@ -978,6 +980,33 @@ class Recognizer:
         feat = np.empty((n, 1024), np.float32)
         check(test_lib().ocr_test_rec_features(self._h, int(form), _ptr(x), n, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(feat)))
         return feat
+
+    def debug_rec_fc1(self, form, feat, w, bias, poison=False, guard=8, sentinel=-7.0):
+        """fc1 + bias + ReLU on caller weights (test hook): form 0 the large-batch conv_igemm GEMM, 1 rec_fc1_ksplit_kernel.  feat: n x 1024;
+        w [512][1024], bias [512]; poison: the rows the kernel may read past the batch hold NaN instead of zero.  Returns (n + guard) x 512 f32:
+        the result and, behind it, `guard` rows that went to the device as `sentinel` and come back as the kernel left them."""
+        f = lambda a, shape: np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
+        x = f(feat, (-1, 1024))
+        n = x.shape[0]
+        w, bias = f(w, (512, 1024)), f(bias, (512,))
+        hid = np.full((n + guard, 512), sentinel, np.float32)
+        check(test_lib().ocr_test_rec_fc1(self._h, int(form), _ptr(x), n, _ptr(w), _ptr(bias), int(bool(poison)), _ptr(hid), int(guard)))
+        return hid
+
+    def debug_rec_fc2(self, form, hid, w, bias, want=("logits", "labels", "probs"), guard=8, sentinel=-7):
+        """fc2 + bias + softmax(f64) + top-1 on caller weights (test hook): form 0 rec_fc2_softmax_kernel, 1 rec_fc2_small_kernel.  hid: n x 512;
+        w [62][512], bias [62].  Returns (logits (n + guard) x 62 f32, labels (n + guard) i32, probs (n + guard) f64), None for an output not in
+        `want` (the kernel then gets a null pointer); each went to the device filled with `sentinel`."""
+        f = lambda a, shape: np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
+        x = f(hid, (-1, 512))
+        n = x.shape[0]
+        w, bias = f(w, (62, 512)), f(bias, (62,))
+        logits = np.full((n + guard, 62), sentinel, np.float32) if "logits" in want else None
+        labels = np.full(n + guard, sentinel, np.int32) if "labels" in want else None
+        probs = np.full(n + guard, sentinel, np.float64) if "probs" in want else None
+        check(test_lib().ocr_test_rec_fc2(self._h, int(form), _ptr(x), n, _ptr(w), _ptr(bias), *(None if a is None else _ptr(a) for a in (logits, labels, probs)),
+                                          int(guard)))
+        return logits, labels, probs
 
     def set_options(self, options: str) -> None:
         """`small_batch=0`: every batch on the throughput kernels (bit-exact batch-size invariance)."""

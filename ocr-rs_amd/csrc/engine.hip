@@ -1609,32 +1609,10 @@ void Recognizer::classify(const float* crops, int n, float* logits, int32_t* lab
     launch_rec_conv(w_, crops + (size_t)b * 784, nb, feat_, stream_);
     rec.end(rec_crops_per_block(nb) == 2 ? "rec_conv<2>" : "rec_conv<4>",
             2.0 * nb * (576.0 * 32 * 26 + 64.0 * 64 * 800), (double)nb * (784 + 1024) * 4 + 13 * 64 * 4 + 25 * 2048 * 4);
-    // fc1 + bias + ReLU as a plain GEMM over the batch: M = crops, K = Cin, N = Cout
-    auto fc = [&](const char* name, const float* in, const float* wgt, const float* bias, int cin, int cout, bool relu, float* out) {
-      ConvDesc d{};
-      d.src[0] = in;
-      d.src_mode = SRC_PLAIN;
-      d.src_bytes = (size_t)nb * cin * 4;
-      d.wgt = wgt;
-      d.wgt_bytes = (size_t)cout * cin * 4;
-      d.N = 1;
-      d.Hin = d.Ho = 1;
-      d.Win = d.Wo = nb;
-      d.Cin = cin;
-      d.Cout = cout;
-      d.ks = 1;
-      d.stride = 1;
-      d.pad = 0;
-      d.bias = bias;
-      d.relu = relu ? 1 : 0;
-      d.store_mode = STORE_NHWC;
-      d.out = out;
-      d.name = name;
-      rec.begin();
-      launch_conv_igemm(d, stream_);
-      rec.end(name, 2.0 * nb * cin * cout, 4.0 * ((double)nb * (cin + cout) + (double)cin * cout));
-    };
-    fc("rec_fc1", feat_, w_.f1w, w_.f1b, 1024, 512, true, hid_);
+    // fc1 + bias + ReLU as a plain GEMM over the batch (launch_rec_fc1: M = crops, K = 1024, N = 512)
+    rec.begin();
+    launch_rec_fc1(w_, feat_, nb, hid_, stream_);
+    rec.end("rec_fc1", 2.0 * nb * 1024 * 512, 4.0 * ((double)nb * (1024 + 512) + 1024.0 * 512));
     rec.begin();
     launch_rec_fc2_softmax(w_, hid_, nb, logits ? logits + (size_t)b * 62 : nullptr, labels ? labels + b : nullptr,
                            probs ? probs + b : nullptr, stream_);

@@ -589,6 +589,31 @@ void launch_rec_conv(const RecWeights& w, const float* crops, int n, float* feat
   OCR_HIP(hipGetLastError());
 }
 
+// fc1 + bias + ReLU as a plain GEMM over the batch: M = crops, K = 1024, N = 512
+void launch_rec_fc1(const RecWeights& w, const float* feat, int n, float* hid, hipStream_t s) {
+  if (n <= 0) return;
+  ConvDesc d{};
+  d.src[0] = feat;
+  d.src_mode = SRC_PLAIN;
+  d.src_bytes = (size_t)n * 1024 * 4;
+  d.wgt = w.f1w;
+  d.wgt_bytes = (size_t)512 * 1024 * 4;
+  d.N = 1;
+  d.Hin = d.Ho = 1;
+  d.Win = d.Wo = n;
+  d.Cin = 1024;
+  d.Cout = 512;
+  d.ks = 1;
+  d.stride = 1;
+  d.pad = 0;
+  d.bias = w.f1b;
+  d.relu = 1;
+  d.store_mode = STORE_NHWC;
+  d.out = hid;
+  d.name = "rec_fc1";
+  launch_conv_igemm(d, s);
+}
+
 // fc2 [62][512] -> [2 column tiles][64 g][64 lanes][4]: element e of lane (j, h) is w[32 ct + j][8 g + 4 h + e] (0 for rows 62, 63)
 std::vector<float> rec_fc2_fragments(const float* w) {
   std::vector<float> f((size_t)2 * 64 * 64 * 4, 0.f);

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <limits>
 
 #include "api_internal.hpp"
 #include "test_kernels.hpp"
@@ -579,6 +580,87 @@ int ocr_test_rec_features(ocr_rec_t* rec, int form, const float* crops, int n, c
               const size_t crop = tile * 16 + r;
               if (crop < (size_t)n) feat_out[crop * 1024 + 16 * g + 4 * q + e] = t[((((tile * 64 + g) * 4 + q) * 16 + r) * 4) + e];
             }
+  });
+}
+
+// fc1 + bias + ReLU of the recogniser on caller weights: form 0 = launch_rec_fc1 (the large-batch conv_igemm GEMM, w uploaded as is), 1 =
+// launch_rec_small stage 1 (rec_fc1_ksplit_kernel: w through rec_fc1_small_weights, feat permuted into the operand order [tile][g][q][r][e]).
+// feat: [n][1024]; w: [512][1024]; bias: [512].  Rows the kernel may read but must not use - form 1: the rows n .. 16 ceil(n / 16) - 1 of the last
+// tile; form 0: 16 rows behind the n real ones in the same allocation, past the src_bytes = n * 4096 the launcher states - are zero, or with
+// poison != 0 quiet NaN.  hid_io: [n + guard_rows][512], uploaded before the launch and downloaded whole after it: what the caller put into
+// rows n .. n + guard_rows - 1 comes back only if the kernel wrote nothing there
+int ocr_test_rec_fc1(ocr_rec_t* rec, int form, const float* feat, int n, const float* w, const float* bias, int poison, float* hid_io, int guard_rows) {
+  return guard([&] {
+    using namespace ocr;
+    if (!rec || !feat || !w || !bias || !hid_io) fail(OCR_ERR_INVALID, "null argument");
+    if (form < 0 || form > 1 || n <= 0 || guard_rows < 0) fail(OCR_ERR_INVALID, "rec fc1 hook: bad form, batch or guard");
+    OCR_HIP(hipSetDevice(rec->impl.device()));
+    hipStream_t s = rec->impl.stream();
+    HookBuffers b;
+    RecWeights rw{};
+    rw.f1b = b.f32(bias, 512);
+    const float pad = poison ? std::numeric_limits<float>::quiet_NaN() : 0.f;
+    const size_t hid_e = ((size_t)n + guard_rows) * 512;
+    float* d_hid = b.f32(hid_io, hid_e);
+    if (form == 0) {
+      std::vector<float> t(((size_t)n + 16) * 1024, pad);
+      std::copy(feat, feat + (size_t)n * 1024, t.begin());
+      rw.f1w = b.f32(w, (size_t)512 * 1024);
+      launch_rec_fc1(rw, b.f32(t.data(), t.size()), n, d_hid, s);
+    } else {
+      const size_t tiles = ((size_t)n + 15) / 16;
+      std::vector<float> t(tiles * 16 * 1024);
+      for (size_t tile = 0; tile < tiles; ++tile)
+        for (int g = 0; g < 64; ++g)
+          for (int q = 0; q < 4; ++q)
+            for (int r = 0; r < 16; ++r)
+              for (int e = 0; e < 4; ++e) {
+                const size_t crop = tile * 16 + r;
+                t[((((tile * 64 + g) * 4 + q) * 16 + r) * 4) + e] = crop < (size_t)n ? feat[crop * 1024 + 16 * g + 4 * q + e] : pad;
+              }
+      const std::vector<float> ws = rec_fc1_small_weights(w);
+      rw.f1s = b.f32(ws.data(), ws.size());
+      launch_rec_small(rw, nullptr, n, b.f32(t.data(), t.size()), d_hid, nullptr, nullptr, nullptr, s, 1);
+    }
+    OCR_HIP(hipStreamSynchronize(s));
+    OCR_HIP(hipMemcpy(hid_io, d_hid, hid_e * 4, hipMemcpyDeviceToHost));
+  });
+}
+// fc2 + bias + softmax(f64) + top-1 of the recogniser on caller weights: form 0 = launch_rec_fc2_softmax (w through rec_fc2_fragments), 1 =
+// launch_rec_small stage 2 (rec_fc2_small_kernel, w through rec_fc2_small_fragments).  hid: [n][512]; w: [62][512]; bias: [62], padded to 64
+// with zeros as the Recognizer does.  logits_io [n + guard_rows][62] f32, labels_io [n + guard_rows] i32, probs_io [n + guard_rows] f64: each
+// optional (null goes to the launcher as null), uploaded before the launch and downloaded whole after it
+int ocr_test_rec_fc2(ocr_rec_t* rec, int form, const float* hid, int n, const float* w, const float* bias, float* logits_io, int32_t* labels_io,
+                     double* probs_io, int guard_rows) {
+  return guard([&] {
+    using namespace ocr;
+    if (!rec || !hid || !w || !bias) fail(OCR_ERR_INVALID, "null argument");
+    if (form < 0 || form > 1 || n <= 0 || guard_rows < 0) fail(OCR_ERR_INVALID, "rec fc2 hook: bad form, batch or guard");
+    OCR_HIP(hipSetDevice(rec->impl.device()));
+    hipStream_t s = rec->impl.stream();
+    HookBuffers b;
+    RecWeights rw{};
+    std::vector<float> b2(bias, bias + 62);
+    b2.resize(64, 0.f);
+    rw.f2b = b.f32(b2.data(), 64);
+    const float* d_hid = b.f32(hid, (size_t)n * 512);
+    const size_t rows = (size_t)n + guard_rows;
+    float* d_lg = logits_io ? b.f32(logits_io, rows * 62) : nullptr;
+    int32_t* d_lab = labels_io ? static_cast<int32_t*>(b.raw(labels_io, rows * 4)) : nullptr;
+    double* d_pr = probs_io ? static_cast<double*>(b.raw(probs_io, rows * 8)) : nullptr;
+    if (form == 0) {
+      const std::vector<float> f = rec_fc2_fragments(w);
+      rw.f2f = b.f32(f.data(), f.size());
+      launch_rec_fc2_softmax(rw, d_hid, n, d_lg, d_lab, d_pr, s);
+    } else {
+      const std::vector<float> f = rec_fc2_small_fragments(w);
+      rw.f2s = b.f32(f.data(), f.size());
+      launch_rec_small(rw, nullptr, n, nullptr, const_cast<float*>(d_hid), d_lg, d_lab, d_pr, s, 2);
+    }
+    OCR_HIP(hipStreamSynchronize(s));
+    if (d_lg) OCR_HIP(hipMemcpy(logits_io, d_lg, rows * 62 * 4, hipMemcpyDeviceToHost));
+    if (d_lab) OCR_HIP(hipMemcpy(labels_io, d_lab, rows * 4, hipMemcpyDeviceToHost));
+    if (d_pr) OCR_HIP(hipMemcpy(probs_io, d_pr, rows * 8, hipMemcpyDeviceToHost));
   });
 }
 
