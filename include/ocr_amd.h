@@ -128,6 +128,8 @@ int ocr_det_create(const void* weights, size_t weights_bytes, int device, ocr_de
  *                               products per pair on v_mfma_f32_32x32x16_bf16, f32 accumulation - the error of an f32 FMA chain
  *                               (dropped terms <= 2^-23 of a product; profiles/r03_bf16x3_accuracy.txt), the same parity bars, up to
  *                               2.67 x the f32 matrix rate.  f32: every conv on v_mfma_f32_32x32x2_f32 (exact f32 FMA chain).
+ *   pre_stage_mb=<n>     (256)  device staging budget of ocr_preprocess_batch in MiB, 1..4096 (host sources, frames on their way to the host); a
+ *                               batch that needs more runs in several chunks, an image larger than the budget grows it.  Same bits
  *   precision=f32|bf16   (f32)  same as ocr_det_set_precision
  * Any other key is OCR_ERR_INVALID ("unknown detector option").  That includes x3_wide, winograd43_x3 and transform_fuse, which earlier versions
  * accepted: the kernels they selected were measured no faster than the defaults and left the library (docs/history.md). */
@@ -207,6 +209,39 @@ int ocr_det_forward_profile(ocr_det_t* det, const float* x_dev, int n, int h, in
  * ------------------------------------------------------------------------- */
 int ocr_preprocess_image(ocr_det_t* det, const uint8_t* rgba, int w, int h, int target_w, int target_h,
                          uint8_t* gray, float* gray_f32, double* adj_xy, int mem_kind);
+
+/* The same for a batch of decoded images of differing sizes: images[i] -> frame i of gray (N x target_h x target_w u8) and / or
+ * gray_f32 (N x 1 x target_h x target_w f32, the input of ocr_det_forward), adj_xy[2i], adj_xy[2i + 1] = resized / original.
+ * Rule: frame i and its adjust values are bit for bit what ocr_preprocess_image gives for images[i] alone, whatever the batch and
+ * the position in it; the zero padding right of and below the resized image is written (the outputs may arrive uninitialised).
+ * One kernel launch covers the batch: vertical pass, horizontal pass and luma per output tile, nothing in between goes to HBM;
+ * the weight tables are built once per distinct (in, out) size pair of the call.
+ * Memory kinds: the descriptor array and adj_xy are host memory.  src_mem_kind says where the pixels of EVERY image live,
+ * dst_mem_kind where BOTH outputs live; all four combinations.  Host pixels may be pageable or from ocr_host_alloc, at any
+ * alignment and stride; they are packed into a device staging area (engine option pre_stage_mb=<1..4096>, default 256; an image
+ * larger than that grows it).  A batch that does not fit is staged and run in several chunks inside the call; results do not
+ * depend on the chunking.  Device pixels must be 4-byte aligned.
+ * Stream rule: runs on the handle's stream behind whatever is queued there and blocks until the outputs are complete.  Staging
+ * and plans are storage of the call's own, not the post-processing scratch: the call is legal while a pipelined batch is pending
+ * on the handle (ocr_det_detect_pipelined*) and leaves that batch alone.
+ * Errors: OCR_ERR_INVALID for a null det, images or adj_xy, both outputs null, n < 0, an image with null pixels, w or h outside
+ * 1..16384, a stride below 4 * w or not a multiple of 4, a target size below 1, a memory kind other than the two, a misaligned
+ * device source; the message names the first offending image.  n = 0 does nothing and is OCR_OK.  The handle stays usable.
+ * ocr_preprocess_image is unchanged and remains the single-image form. */
+typedef struct ocr_image {
+  const uint8_t* rgba;    /* h rows of w RGBA pixels (the reference's into_rgba()) */
+  int32_t w, h;           /* 1..16384 each */
+  int64_t stride_bytes;   /* distance between rows; 0 = 4 * w; otherwise >= 4 * w and a multiple of 4 */
+} ocr_image_t;
+int ocr_preprocess_batch(ocr_det_t* det, const ocr_image_t* images, int n, int src_mem_kind, int target_w, int target_h,
+                         uint8_t* gray, float* gray_f32, int dst_mem_kind, double* adj_xy /* [2n], host */);
+/* Device pixels in, device frames out; queues on the handle's stream and returns without synchronising it (nor does it wait to
+ * release its plan: descriptors and weight tables go up in one copy from one of two handle-owned pinned buffers, each guarded by
+ * an event, so back-to-back calls do not wait for each other's kernels).  adj_xy is computed on the host and valid on return.
+ * The frames are consumable by ocr_det_forward_async on the same handle with no synchronisation in between.  Sources and
+ * outputs must stay valid until ocr_det_synchronize.  Same errors as the blocking form. */
+int ocr_preprocess_batch_async(ocr_det_t* det, const ocr_image_t* images, int n, int target_w, int target_h,
+                               uint8_t* gray_dev, float* gray_f32_dev, double* adj_xy);
 
 /* ---------------------------------------------------------------------------
  * Detection post-processing.  Replaces

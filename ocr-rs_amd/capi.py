@@ -27,7 +27,7 @@ EXPORTS = [
     "ocr_det_create", "ocr_det_create_with_options", "ocr_det_destroy", "ocr_det_set_stream", "ocr_det_set_precision", "ocr_det_forward",
     "ocr_det_forward_u8", "ocr_host_alloc", "ocr_host_free", "ocr_det_detect_pipelined_host",
     "ocr_det_forward_async", "ocr_det_synchronize", "ocr_det_last_front_split", "ocr_det_forward_profile",
-    "ocr_preprocess_image", "ocr_postproc_default_params", "ocr_det_postprocess", "ocr_det_post_stats", "ocr_det_detect_pipelined", "ocr_polygons_free",
+    "ocr_preprocess_image", "ocr_preprocess_batch", "ocr_preprocess_batch_async", "ocr_postproc_default_params", "ocr_det_postprocess", "ocr_det_post_stats", "ocr_det_detect_pipelined", "ocr_polygons_free",
     "ocr_extract_crops", "ocr_segment_default_params", "ocr_segment_glyphs", "ocr_extract_glyph_crops", "ocr_glyphs_free",
     "ocr_cc_default_params", "ocr_segment_glyphs_cc",
     "ocr_strip_default_params", "ocr_plan_word_strips", "ocr_extract_word_strips", "ocr_word_strip_polygons", "ocr_word_strips_free",
@@ -60,6 +60,11 @@ class Polygons(C.Structure):
     _fields_ = [("n_images", C.c_int32), ("n_polygons", C.c_int32), ("n_vertices", C.c_int32),
                 ("img_offsets", C.POINTER(C.c_int32)), ("poly_offsets", C.POINTER(C.c_int32)),
                 ("xy", C.POINTER(C.c_uint32)), ("scores", C.POINTER(C.c_double))]
+
+
+class ImageDesc(C.Structure):
+    """ocr_image_t: h rows of w RGBA pixels, stride_bytes apart (0 = 4 * w)."""
+    _fields_ = [("rgba", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32), ("stride_bytes", C.c_int64)]
 
 
 class SegmentParams(C.Structure):
@@ -156,6 +161,10 @@ def lib() -> C.CDLL:
                                               C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.ocr_preprocess_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p, C.POINTER(C.c_double), C.c_int]
+        L.ocr_preprocess_batch.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_int, C.POINTER(C.c_double)]
+        L.ocr_preprocess_batch_async.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(C.c_double)]
         L.ocr_postproc_default_params.argtypes = [C.POINTER(PostprocParams)]
         L.ocr_postproc_default_params.restype = None
         L.ocr_det_post_stats.argtypes = [C.c_void_p, C.c_void_p]
@@ -750,6 +759,66 @@ class Detector:
         check(lib().ocr_preprocess_image(self._h, _ptr(rgba), w, h, target_w, target_h, _ptr(gray),
                                          _ptr(f32) if want_f32 else None, adj, MEM_HOST))
         return (gray, f32, adj[0], adj[1]) if want_f32 else (gray, adj[0], adj[1])
+
+    @staticmethod
+    def _image_descs(images):
+        """images: h x w x 4 u8 numpy arrays, or CUDA u8 tensors of that shape -> (ImageDesc array, mem kind, what keeps the pixels alive).
+        A row stride that the ABI takes (pixels contiguous, rows a multiple of 4 bytes apart and not overlapping) is passed through as
+        stride_bytes; anything else is copied to a contiguous array first."""
+        kinds = {isinstance(im, np.ndarray) for im in images}
+        if len(kinds) > 1:
+            raise TypeError("preprocess_batch: numpy arrays and device tensors in one batch")
+        host = kinds != {False}
+        descs, keep = (ImageDesc * max(1, len(images)))(), []
+        for i, im in enumerate(images):
+            if im.ndim != 3 or im.shape[2] != 4 or (im.dtype != np.uint8 if host else str(im.dtype) != "torch.uint8"):
+                raise TypeError(f"preprocess_batch: image {i} is not h x w x 4 uint8")
+            if not host and not im.is_cuda:
+                raise TypeError(f"preprocess_batch: image {i} is a host tensor (pass numpy arrays or CUDA tensors)")
+            h, w = int(im.shape[0]), int(im.shape[1])
+            st = tuple(im.strides) if host else tuple(int(v) for v in im.stride())
+            if not (st[2] == 1 and st[1] == 4 and (st[0] >= 4 * w and st[0] % 4 == 0 or h == 1)):
+                im = np.ascontiguousarray(im) if host else im.contiguous()
+                st = (4 * w, 4, 1)
+            keep.append(im)
+            descs[i] = ImageDesc(_ptr(im), w, h, st[0] if h > 1 else 0)
+        return descs, (MEM_HOST if host else MEM_DEVICE), keep
+
+    def preprocess_batch(self, images, target_w: int, target_h: int, want_u8: bool = True, want_f32: bool = False, device_out: bool = False):
+        """ocr_preprocess_batch: decoded images of differing sizes -> (gray N x H x W u8 or None, frames N x 1 x H x W f32 or None,
+        adjust N x 2 f64), every frame bit for bit preprocess_image's.  images: a list of h x w x 4 u8 numpy arrays, or of CUDA u8
+        tensors (whose producers must have finished: the handle's stream does not order against torch's); row strides are passed
+        through, not copied.  The outputs are numpy arrays, or with device_out CUDA tensors.  Blocking."""
+        descs, src_kind, keep = self._image_descs(images)
+        n = len(images)
+        if device_out:
+            import torch
+            dev = torch.device("cuda", self.device)
+            gray = torch.empty((n, target_h, target_w), dtype=torch.uint8, device=dev) if want_u8 else None
+            f32 = torch.empty((n, 1, target_h, target_w), dtype=torch.float32, device=dev) if want_f32 else None
+        else:
+            gray = np.empty((n, target_h, target_w), np.uint8) if want_u8 else None
+            f32 = np.empty((n, 1, target_h, target_w), np.float32) if want_f32 else None
+        adj = np.zeros((n, 2), np.float64)
+        check(lib().ocr_preprocess_batch(self._h, descs, n, src_kind, target_w, target_h, _ptr(gray) if want_u8 else None,
+                                         _ptr(f32) if want_f32 else None, MEM_DEVICE if device_out else MEM_HOST,
+                                         adj.ctypes.data_as(C.POINTER(C.c_double))))
+        del keep
+        return gray, f32, adj
+
+    def preprocess_batch_async(self, images, target_w: int, target_h: int, gray=None, f32=None) -> np.ndarray:
+        """ocr_preprocess_batch_async: CUDA u8 tensors in, frames into the CUDA tensors gray (N x H x W u8) and / or f32 (N x 1 x H x W),
+        queued on the handle's stream; returns the N x 2 adjust array (valid at once).  Images and outputs must stay alive and
+        unchanged until synchronize()."""
+        descs, src_kind, keep = self._image_descs(images)
+        if src_kind != MEM_DEVICE and images:
+            raise TypeError("preprocess_batch_async takes device tensors")
+        n = len(images)
+        adj = np.zeros((n, 2), np.float64)
+        check(lib().ocr_preprocess_batch_async(self._h, descs, n, target_w, target_h, _ptr(gray) if gray is not None else None,
+                                               _ptr(f32) if f32 is not None else None, adj.ctypes.data_as(C.POINTER(C.c_double))))
+        self._pre_keep = keep   # (a .contiguous() copy made above lives until the next call)
+        return adj
 
     def debug_conv_bench(self, n, h, w, cin, cout, ks=3, stride=1, src_mode=0, iters=5) -> float:
         """Test hook: average milliseconds of one conv_igemm launch of this shape."""

@@ -233,6 +233,149 @@ int ocr_preprocess_image(ocr_det_t* det, const uint8_t* rgba, int w, int h, int 
   });
 }
 
+// ---- batched pre-processing (preprocess.hip: preprocess_batch_kernel; rule in include/ocr_amd.h)
+namespace {
+// everything both entry points refuse, before anything is queued; fills the effective strides
+void check_preprocess_batch(const char* who, ocr_det_t* det, const ocr_image_t* images, int n, int src_mem_kind, int target_w, int target_h,
+                            const uint8_t* gray, const float* gray_f32, int dst_mem_kind, const double* adj_xy, std::vector<int64_t>& strides) {
+  using ocr::fail;
+  if (!det || !images || !adj_xy) fail(OCR_ERR_INVALID, "%s: null argument", who);
+  if (!gray && !gray_f32) fail(OCR_ERR_INVALID, "%s: both outputs are null", who);
+  if (n < 0) fail(OCR_ERR_INVALID, "%s: n = %d", who, n);
+  if (target_w < 1 || target_h < 1) fail(OCR_ERR_INVALID, "%s: target size %d x %d", who, target_w, target_h);
+  if (src_mem_kind != OCR_MEM_HOST && src_mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "%s: src_mem_kind %d", who, src_mem_kind);
+  if (dst_mem_kind != OCR_MEM_HOST && dst_mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "%s: dst_mem_kind %d", who, dst_mem_kind);
+  strides.resize(n);
+  for (int i = 0; i < n; ++i) {
+    const ocr_image_t& im = images[i];
+    if (!im.rgba) fail(OCR_ERR_INVALID, "%s: image %d: null pixels", who, i);
+    if (im.w < 1 || im.w > 16384 || im.h < 1 || im.h > 16384) fail(OCR_ERR_INVALID, "%s: image %d: %d x %d (1 .. 16384 each)", who, i, im.w, im.h);
+    const int64_t st = im.stride_bytes == 0 ? (int64_t)4 * im.w : im.stride_bytes;
+    if (st < (int64_t)4 * im.w || st % 4 != 0)
+      fail(OCR_ERR_INVALID, "%s: image %d: stride of %lld bytes (0, or at least 4 * w = %d and a multiple of 4)", who, i, (long long)im.stride_bytes, 4 * im.w);
+    if (src_mem_kind == OCR_MEM_DEVICE && reinterpret_cast<uintptr_t>(im.rgba) % 4 != 0)
+      fail(OCR_ERR_INVALID, "%s: image %d: device pixels are not 4-byte aligned", who, i);
+    strides[i] = st;
+  }
+}
+
+void preprocess_adjust(const ocr_image_t* images, int n, int target_w, int target_h, double* adj_xy) {
+  for (int i = 0; i < n; ++i) {
+    int nw, nh;
+    ocr::resize_dimensions(images[i].w, images[i].h, target_w, target_h, &nw, &nh);
+    adj_xy[2 * i] = (double)nw / (double)images[i].w;  // image_ops.rs:200-202
+    adj_xy[2 * i + 1] = (double)nh / (double)images[i].h;
+  }
+}
+
+// one launch: the plan of `cnt` device-resident images into the next plan slot, up in one copy, the kernel behind it.  Nothing waits.
+void preprocess_launch(ocr::Detector& d, ocr::PrePlanner& pl, const ocr::PreSource* src, int cnt, int first_frame, uint8_t* gray_dev,
+                       float* gray_f32_dev, std::vector<uint32_t>& blob, hipStream_t s) {
+  const long long tiles = pl.plan(src, cnt, first_frame, blob);
+  const size_t bytes = blob.size() * 4;
+  ocr::Detector::PrePlanSlot& slot = d.pre_plan_slot(bytes);
+  std::memcpy(slot.host, blob.data(), bytes);
+  struct Mark {   // the slot is busy from its upload on, whatever happens to the launch
+    ocr::Detector::PrePlanSlot& p;
+    hipStream_t s;
+    ~Mark() {
+      if (hipEventRecord(p.done, s) == hipSuccess) p.in_flight = true;
+    }
+  } mark{slot, s};
+  OCR_HIP(hipMemcpyAsync(slot.dev, slot.host, bytes, hipMemcpyHostToDevice, s));
+  ocr::launch_preprocess_batch(slot.dev, cnt, tiles, pl.W, pl.H, gray_dev, gray_f32_dev, s);
+}
+}  // namespace
+
+int ocr_preprocess_batch_async(ocr_det_t* det, const ocr_image_t* images, int n, int target_w, int target_h, uint8_t* gray_dev,
+                               float* gray_f32_dev, double* adj_xy) {
+  return guard([&] {
+    using namespace ocr;
+    std::vector<int64_t> strides;
+    check_preprocess_batch("preprocess_batch_async", det, images, n, OCR_MEM_DEVICE, target_w, target_h, gray_dev, gray_f32_dev, OCR_MEM_DEVICE,
+                           adj_xy, strides);
+    if (n == 0) return;
+    preprocess_adjust(images, n, target_w, target_h, adj_xy);
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    PrePlanner pl{target_w, target_h, {}};
+    std::vector<PreSource> src(n);
+    for (int i = 0; i < n; ++i) src[i] = {images[i].rgba, strides[i], images[i].w, images[i].h};
+    std::vector<uint32_t> blob;
+    const int step = pl.max_images();
+    for (int b = 0; b < n; b += step)
+      preprocess_launch(det->impl, pl, src.data() + b, std::min(step, n - b), b, gray_dev, gray_f32_dev, blob, s);
+  });
+}
+
+int ocr_preprocess_batch(ocr_det_t* det, const ocr_image_t* images, int n, int src_mem_kind, int target_w, int target_h, uint8_t* gray,
+                         float* gray_f32, int dst_mem_kind, double* adj_xy) {
+  return guard([&] {
+    using namespace ocr;
+    std::vector<int64_t> strides;
+    check_preprocess_batch("preprocess_batch", det, images, n, src_mem_kind, target_w, target_h, gray, gray_f32, dst_mem_kind, adj_xy, strides);
+    if (n == 0) return;
+    preprocess_adjust(images, n, target_w, target_h, adj_xy);
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    const bool src_host = src_mem_kind == OCR_MEM_HOST, dst_host = dst_mem_kind == OCR_MEM_HOST;
+    const size_t px = (size_t)target_w * target_h;
+    PrePlanner pl{target_w, target_h, {}};
+    // chunks: what a chunk stages (host sources packed to 4 * w bytes a row, frames on their way to the host) stays within the
+    // budget, except that an image alone may exceed it; a chunk's tiles fit one launch
+    const size_t budget = det->impl.pre_stage_budget();
+    auto staged = [&](int i) {
+      return (src_host ? align256((size_t)4 * images[i].w * images[i].h) : 0) +
+             (dst_host ? (gray ? px : 0) + (gray_f32 ? 4 * px : 0) : 0);
+    };
+    const size_t slack = 512;   // the two output blocks start on 256-byte boundaries
+    std::vector<int> begin{0};
+    size_t used = 0, stage_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+      const int cnt = i - begin.back();
+      if (cnt > 0 && (cnt >= pl.max_images() || used + staged(i) + slack > budget)) {
+        begin.push_back(i);
+        used = 0;
+      }
+      used += staged(i);
+      stage_bytes = std::max(stage_bytes, used + slack);
+    }
+    begin.push_back(n);
+    char* stage = (src_host || dst_host) ? static_cast<char*>(det->impl.pre_stage(stage_bytes)) : nullptr;
+    std::vector<PreSource> src;
+    std::vector<uint32_t> blob;
+    for (size_t c = 0; c + 1 < begin.size(); ++c) {
+      const int b = begin[c], cnt = begin[c + 1] - b;
+      Carve cv;
+      src.resize(cnt);
+      for (int k = 0; k < cnt; ++k) {
+        const ocr_image_t& im = images[b + k];
+        src[k] = {im.rgba, strides[b + k], im.w, im.h};
+        if (!src_host) continue;
+        const size_t row = (size_t)4 * im.w;
+        unsigned char* dst = at<unsigned char>(stage, cv.take(row * im.h));
+        if ((size_t)strides[b + k] == row) OCR_HIP(hipMemcpyAsync(dst, im.rgba, row * im.h, hipMemcpyHostToDevice, s));
+        else OCR_HIP(hipMemcpy2DAsync(dst, row, im.rgba, (size_t)strides[b + k], row, im.h, hipMemcpyHostToDevice, s));
+        src[k].dev = dst;
+        src[k].stride = (int64_t)row;
+      }
+      uint8_t* g = gray;
+      float* f = gray_f32;
+      if (dst_host) {
+        if (gray) g = at<uint8_t>(stage, cv.take(cnt * px));
+        if (gray_f32) f = at<float>(stage, cv.take(cnt * px * 4));
+      }
+      if (cv.end > stage_bytes && stage) fail(OCR_ERR_INTERNAL, "preprocess_batch: chunk of %zu bytes, %zu staged", cv.end, stage_bytes);
+      preprocess_launch(det->impl, pl, src.data(), cnt, dst_host ? 0 : b, g, f, blob, s);
+      if (dst_host) {
+        if (gray) OCR_HIP(hipMemcpyAsync(gray + (size_t)b * px, g, cnt * px, hipMemcpyDeviceToHost, s));
+        if (gray_f32) OCR_HIP(hipMemcpyAsync(gray_f32 + (size_t)b * px, f, cnt * px * 4, hipMemcpyDeviceToHost, s));
+      }
+    }
+    OCR_HIP(hipStreamSynchronize(s));
+  });
+}
+
 // the box of every polygon in frame coordinates (oracle/crop_oracle.py crop_boxes), shared by the crop and glyph entry points
 static std::vector<ocr::CropBox> crop_boxes(const ocr_polygons_t* polys, const double* adj_xy, int n, int h, int w) {
   std::vector<ocr::CropBox> boxes;

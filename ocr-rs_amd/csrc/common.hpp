@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -167,6 +168,37 @@ void resize_dimensions(int width, int height, int nwidth, int nheight, int* ow, 
 size_t preprocess_scratch_bytes(int w, int h, int W, int H);
 void launch_preprocess(const unsigned char* rgba_dev, int w, int h, int W, int H, unsigned char* gray_dev, float* gray_f32_dev,
                        void* scratch, size_t scratch_bytes, double* adj_xy, hipStream_t s);
+// ... and a batch of images of differing sizes in one launch (ocr_preprocess_batch; the kernel and the layout of a plan are in preprocess.hip)
+struct AxisTable {       // per output index: first source index and up to maxk normalised weights
+  std::vector<int> left;
+  std::vector<int> count;
+  std::vector<float> w;  // [out][maxk]
+  int maxk = 0;
+};
+struct PreSource {       // one image where the kernel reads it: h rows of w RGBA pixels on the device, 4-byte aligned
+  const unsigned char* dev;
+  int64_t stride;        // bytes between rows, a multiple of 4
+  int w, h;
+};
+struct PreImage {        // ... and as the kernel finds it at the head of a plan
+  const unsigned char* src;
+  int64_t stride;
+  int32_t w, h, nw, nh;     // source and resized size (resize_dimensions)
+  int32_t tile0;            // first tile of the image in the launch's flat tile list
+  int32_t frame;            // which target_h x target_w frame of the output block it fills
+  uint32_t ty, tx;          // its two weight tables: 4-byte words from the start of the plan
+  int32_t maxk_y, maxk_x;
+  int32_t pad_[2];
+};
+struct PrePlanner {      // one per call: target size and the weight tables built so far, one per distinct (in, out) pair
+  int W, H;
+  std::map<std::pair<int, int>, AxisTable> tables;
+  int max_images() const;   // of one launch: its tiles are counted in 31 bits
+  // the plan of images [0, n), which fill frames first_frame .. of the output block; returns the launch's tiles
+  long long plan(const PreSource* src, int n, int first_frame, std::vector<uint32_t>& blob);
+};
+void launch_preprocess_batch(const void* plan_dev, int n, long long tiles, int W, int H, unsigned char* gray_dev, float* gray_f32_dev,
+                             hipStream_t s);
 
 // crop extraction detect -> recognise (build-defined rule, oracle/crop_oracle.py), crops.hip
 struct CropBox {

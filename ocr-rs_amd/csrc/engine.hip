@@ -271,6 +271,11 @@ void Detector::parse_options(const char* options) {
       post_threads_ = num();
       if (post_threads_ < 0 || post_threads_ > 256) fail(OCR_ERR_INVALID, "detector option post_threads: %d (0 = automatic, at most 256)", post_threads_);
     }
+    else if (key == "pre_stage_mb") {
+      const int mb = num();
+      if (mb < 1 || mb > 4096) fail(OCR_ERR_INVALID, "detector option pre_stage_mb: %d (1 .. 4096)", mb);
+      pre_stage_budget_ = (size_t)mb << 20;
+    }
     else if (key == "device_contours") {
       if (val == "auto") device_contours_ = -1;
       else {
@@ -587,6 +592,12 @@ Detector::~Detector() {
   free_workspace();
   if (host_scratch_) (void)hipHostFree(host_scratch_);
   if (host_adj_) (void)hipHostFree(host_adj_);
+  for (PrePlanSlot& p : pre_plan_) {
+    if (p.host) (void)hipHostFree(p.host);
+    if (p.dev) (void)hipFree(p.dev);
+    if (p.done) (void)hipEventDestroy(p.done);
+  }
+  if (pre_stage_) (void)hipFree(pre_stage_);
   for (void* p : scratch_)
     if (p) (void)hipFree(p);
   for (Staging& st : stage_)
@@ -720,6 +731,41 @@ void* Detector::host_adj(size_t bytes) {
     host_adj_bytes_ = want;
   }
   return host_adj_;
+}
+
+Detector::PrePlanSlot& Detector::pre_plan_slot(size_t bytes) {
+  PrePlanSlot& p = pre_plan_[pre_plan_next_];
+  pre_plan_next_ = (pre_plan_next_ + 1) % kPrePlans;
+  if (!p.done) OCR_HIP(hipEventCreateWithFlags(&p.done, hipEventDisableTiming));
+  if (p.in_flight) {   // the launch that read this slot, kPrePlans launches ago: both buffers are free once it is through
+    OCR_HIP(hipEventSynchronize(p.done));
+    p.in_flight = false;
+  }
+  if (bytes > p.bytes) {
+    if (p.host) OCR_HIP(hipHostFree(p.host));
+    if (p.dev) OCR_HIP(hipFree(p.dev));
+    p.host = p.dev = nullptr;
+    p.bytes = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 2, 65536);
+    OCR_HIP(hipHostMalloc(&p.host, want, hipHostMallocDefault));
+    OCR_HIP(hipMalloc(&p.dev, want));
+    p.bytes = want;
+  }
+  return p;
+}
+
+// only the blocking call stages, it sizes the block before it queues anything and returns with its stream drained: nothing reads the
+// old block when a larger one replaces it
+void* Detector::pre_stage(size_t bytes) {
+  if (bytes > pre_stage_bytes_) {
+    OCR_HIP(hipStreamSynchronize(stream_));   // (a call that failed half way may have left work behind)
+    if (pre_stage_) OCR_HIP(hipFree(pre_stage_));
+    pre_stage_ = nullptr;
+    pre_stage_bytes_ = 0;
+    OCR_HIP(hipMalloc(&pre_stage_, bytes));
+    pre_stage_bytes_ = bytes;
+  }
+  return pre_stage_;
 }
 
 void* Detector::scratch(int slot, size_t bytes) {

@@ -115,6 +115,20 @@ class Detector {
   void* host_scratch(size_t bytes);
   // pinned block for the adjust values of the batch a pipelined call leaves pending (its chain is queued with a really asynchronous upload)
   void* host_adj(size_t bytes);
+  // ocr_preprocess_batch*: storage of its own, none of the five scratch slots (a pipelined batch may be pending in those).
+  // A plan (descriptors + weight tables of one launch) is written into a pinned buffer and goes up in one copy; kPrePlans such pairs of
+  // buffers, each guarded by an event recorded behind the launch that reads it, so a call waits for the launch kPrePlans calls back only.
+  enum { kPrePlans = 2 };
+  struct PrePlanSlot {
+    void *host = nullptr, *dev = nullptr;
+    size_t bytes = 0;
+    hipEvent_t done = nullptr;   // behind the last launch that read `dev`
+    bool in_flight = false;
+  };
+  PrePlanSlot& pre_plan_slot(size_t bytes);   // the next slot, free and at least `bytes` large
+  // device staging of the blocking call (host sources packed, outputs on their way to the host); budget: option pre_stage_mb
+  void* pre_stage(size_t bytes);
+  size_t pre_stage_budget() const { return pre_stage_budget_; }
   // host threads of the post-processing stages (created on first use, one image per task)
   ThreadPool& pool();
   // ocr_det_detect_pipelined: the batch whose forward is in flight and whose post-processing is still owed
@@ -261,6 +275,11 @@ class Detector {
   Staging stage_[2];
   hipStream_t copy_stream_ = nullptr, out_stream_ = nullptr;
   hipEvent_t ev_before_fwd_ = nullptr;
+  PrePlanSlot pre_plan_[kPrePlans];
+  int pre_plan_next_ = 0;
+  void* pre_stage_ = nullptr;
+  size_t pre_stage_bytes_ = 0;
+  size_t pre_stage_budget_ = (size_t)256 << 20;   // option pre_stage_mb
   int post_threads_ = 0;   // option post_threads: 0 = automatic
   int device_contours_ = -1;  // option device_contours (-1 = auto)
   int device_unclip_ = 1;     // option device_unclip: 0 host, 1 device where it pays (default), 2 device always

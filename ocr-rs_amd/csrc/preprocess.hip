@@ -8,19 +8,14 @@
 // and add (no FMA contraction), so the result equals oracle/preprocess_oracle.py bit for bit.
 // HBM-bound: one pass reads the RGBA source, the second writes the padded gray frame (+ f32 copy).
 #include <cmath>
+#include <cstring>
+#include <map>
 #include <vector>
 
 #include "common.hpp"
 
 namespace ocr {
 namespace {
-
-struct AxisTable {       // per output index: first source index and up to maxk normalised weights
-  std::vector<int> left;
-  std::vector<int> count;
-  std::vector<float> w;  // [out][maxk]
-  int maxk = 0;
-};
 
 // image 0.23.11 sample.rs, Triangle filter (support 1.0); every step in f32 like the crate
 AxisTable build_axis(int in_size, int out_size) {
@@ -104,6 +99,103 @@ __global__ __launch_bounds__(256) void resize_horizontal_luma_kernel(const uchar
   if (gray_f32) gray_f32[(size_t)oy * W + ox] = (float)g;  // convert_image_to_tensor(..).to_kind(Float): raw 0..255
 }
 
+
+// ---- the batched form (ocr_preprocess_batch): one launch over the output tiles of every image of a chunk.
+// A tile is kPreTR output rows x kPreTC output columns, one output pixel per lane.  Phase 1 (vertical_sample) runs over the source
+// columns the tile's output columns need - `left` and `left + count` are monotone in the output index, so that is one contiguous
+// span - and leaves truncated R, G, B in LDS (alpha never reaches the luma); phase 2 (horizontal_sample + luma) reads them back.
+// The span is walked in chunks of kPreCH columns, left to right, with every lane's three accumulators in registers across the
+// chunks: the taps of a pixel are added in ascending k whatever the ratio (16384 columns may go into one), and the loop runs once
+// for ordinary ratios.  The nh x w RGBA intermediate of the two kernels above never exists in HBM.
+constexpr int kPreTR = 8, kPreTC = 32, kPreCH = 512;   // 256 lanes; LDS kPreTR * kPreCH * 4 = 16 KiB: eight waves per SIMD
+static_assert(kPreTR * kPreTC == 256, "one output pixel per lane");
+
+__global__ __launch_bounds__(256) void preprocess_batch_kernel(const uint32_t* __restrict__ plan, int n_images, int W, int H,
+                                                               unsigned char* __restrict__ gray, float* __restrict__ gray_f32) {
+  __shared__ uint32_t lds[kPreTR * kPreCH];   // [row][column of the chunk]: R | G << 8 | B << 16 after the vertical pass
+  const PreImage* __restrict__ imgs = reinterpret_cast<const PreImage*>(plan);
+  // the image of this tile: the last one whose first tile is not after it (uniform: scalar loads)
+  const int tile = blockIdx.x;
+  int lo = 0, hi = n_images - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (imgs[mid].tile0 <= tile) lo = mid;
+    else hi = mid - 1;
+  }
+  const PreImage im = imgs[lo];
+  const int t = tile - im.tile0, tiles_x = (W + kPreTC - 1) / kPreTC;
+  const int oy0 = (t / tiles_x) * kPreTR, ox0 = (t % tiles_x) * kPreTC;
+  const int tid = threadIdx.x, r = tid / kPreTC, oy = oy0 + r, ox = ox0 + tid % kPreTC;
+  const bool inside = oy < H && ox < W;
+  const size_t o = ((size_t)im.frame * H + (inside ? oy : 0)) * W + (inside ? ox : 0);
+  if (oy0 >= im.nh || ox0 >= im.nw) {   // a tile wholly in the padding right of / below the resized image (image_ops.rs:204-214)
+    if (inside) {
+      if (gray) gray[o] = 0;
+      if (gray_f32) gray_f32[o] = 0.f;
+    }
+    return;
+  }
+  const int *ly = reinterpret_cast<const int*>(plan + im.ty), *cy = ly + im.nh;
+  const float* wy = reinterpret_cast<const float*>(cy + im.nh);
+  const int *lx = reinterpret_cast<const int*>(plan + im.tx), *cx = lx + im.nw;
+  const float* wx = reinterpret_cast<const float*>(cx + im.nw);
+  const int rows = min(kPreTR, im.nh - oy0), oxl = min(ox0 + kPreTC, im.nw) - 1;
+  const int s0 = lx[ox0], s1 = lx[oxl] + cx[oxl];   // the tile's span of source columns
+  const bool live = oy < im.nh && ox < im.nw;
+  const int l = live ? lx[ox] : 0, c = live ? cx[ox] : 0;
+  const float* wk = wx + (size_t)(live ? ox : 0) * im.maxk_x;
+  float t0 = 0.f, t1 = 0.f, t2 = 0.f;
+  for (int c0 = s0; c0 < s1; c0 += kPreCH) {
+    const int cw = min(kPreCH, s1 - c0);
+    // vertical_sample of columns [c0, c0 + cw) for the tile's rows; consecutive lanes read consecutive source pixels
+    for (int i = tid; i < rows * cw; i += 256) {
+      const int rr = i / cw, col = i - rr * cw;
+      const int yl = ly[oy0 + rr], yc = cy[oy0 + rr];
+      const float* wv = wy + (size_t)(oy0 + rr) * im.maxk_y;
+      const unsigned char* p = im.src + (int64_t)yl * im.stride + (int64_t)(c0 + col) * 4;
+      float v0 = 0.f, v1 = 0.f, v2 = 0.f;
+      for (int k = 0; k < yc; k += 4, p += 4 * im.stride) {
+        // four taps' loads in flight, added in ascending k.  A tap past the count is pixel 0 x weight 0: the sums are never
+        // negative, and adding +0 to such a sum changes no bit
+        uint32_t px[4];
+        float w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool on = k + j < yc;
+          px[j] = on ? *reinterpret_cast<const uint32_t*>(p + j * im.stride) : 0u;
+          w[j] = on ? wv[k + j] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          v0 = __fadd_rn(v0, __fmul_rn((float)(px[j] & 255u), w[j]));
+          v1 = __fadd_rn(v1, __fmul_rn((float)((px[j] >> 8) & 255u), w[j]));
+          v2 = __fadd_rn(v2, __fmul_rn((float)((px[j] >> 16) & 255u), w[j]));
+        }
+      }
+      lds[rr * kPreCH + col] = (uint32_t)to_u8(v0) | (uint32_t)to_u8(v1) << 8 | (uint32_t)to_u8(v2) << 16;
+    }
+    __syncthreads();
+    // horizontal_sample: the taps of this lane's pixel that lie in the chunk, k ascending
+    const int k0 = max(0, c0 - l), k1 = min(c, c0 + cw - l);
+    for (int k = k0; k < k1; ++k) {
+      const uint32_t px = lds[r * kPreCH + (l + k - c0)];
+      const float w = wk[k];
+      t0 = __fadd_rn(t0, __fmul_rn((float)(px & 255u), w));
+      t1 = __fadd_rn(t1, __fmul_rn((float)((px >> 8) & 255u), w));
+      t2 = __fadd_rn(t2, __fmul_rn((float)((px >> 16) & 255u), w));
+    }
+    __syncthreads();
+  }
+  if (!inside) return;
+  unsigned char g = 0;
+  if (live) {
+    const float rf = (float)to_u8(t0), gf = (float)to_u8(t1), bf = (float)to_u8(t2);
+    const float lum = __fadd_rn(__fadd_rn(__fmul_rn(0.2126f, rf), __fmul_rn(0.7152f, gf)), __fmul_rn(0.0722f, bf));
+    g = (unsigned char)lum;  // NumCast: truncation
+  }
+  if (gray) gray[o] = g;
+  if (gray_f32) gray_f32[o] = (float)g;
+}
 }  // namespace
 
 void resize_dimensions(int width, int height, int nwidth, int nheight, int* ow, int* oh) {
@@ -148,6 +240,61 @@ void launch_preprocess(const unsigned char* rgba_dev, int w, int h, int W, int H
     adj_xy[0] = (double)nw / (double)w;  // image_ops.rs:200-202
     adj_xy[1] = (double)nh / (double)h;
   }
+}
+
+// The plan of one launch of preprocess_batch_kernel: n PreImage descriptors, then the weight tables they point to (per table:
+// left[out], count[out], w[out][maxk]; offsets in 4-byte words from the start of the plan).  A table is built once per distinct
+// (in, out) pair of the CALL (PrePlanner::tables) and stored once per plan.
+long long PrePlanner::plan(const PreSource* src, int n, int first_frame, std::vector<uint32_t>& blob) {
+  static_assert(sizeof(PreImage) % 16 == 0, "descriptors are read as an array");
+  const long long tiles_per_image = (long long)((W + kPreTC - 1) / kPreTC) * ((H + kPreTR - 1) / kPreTR);
+  blob.assign((size_t)n * sizeof(PreImage) / 4, 0u);
+  std::map<std::pair<int, int>, std::pair<uint32_t, int>> placed;   // (in, out) -> word offset in this plan, maxk
+  auto place = [&](int in, int out) {
+    const std::pair<int, int> key(in, out);
+    auto hit = placed.find(key);
+    if (hit != placed.end()) return hit->second;
+    auto tab = tables.find(key);
+    if (tab == tables.end()) tab = tables.emplace(key, build_axis(in, out)).first;
+    const AxisTable& t = tab->second;
+    if (blob.size() + 2 * (size_t)out + t.w.size() > (size_t)0x7fffffff) fail(OCR_ERR_INVALID, "preprocess_batch: weight tables of more than 8 GiB");
+    const uint32_t off = (uint32_t)blob.size();
+    blob.insert(blob.end(), t.left.begin(), t.left.end());
+    blob.insert(blob.end(), t.count.begin(), t.count.end());
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(t.w.data());
+    blob.insert(blob.end(), w, w + t.w.size());
+    return placed.emplace(key, std::make_pair(off, t.maxk)).first->second;
+  };
+  for (int i = 0; i < n; ++i) {
+    PreImage im{};
+    im.src = src[i].dev;
+    im.stride = src[i].stride;
+    im.w = src[i].w;
+    im.h = src[i].h;
+    resize_dimensions(im.w, im.h, W, H, &im.nw, &im.nh);
+    im.tile0 = (int32_t)(i * tiles_per_image);
+    im.frame = first_frame + i;
+    const auto ty = place(im.h, im.nh), tx = place(im.w, im.nw);
+    im.ty = ty.first;
+    im.maxk_y = ty.second;
+    im.tx = tx.first;
+    im.maxk_x = tx.second;
+    std::memcpy(reinterpret_cast<char*>(blob.data()) + (size_t)i * sizeof(PreImage), &im, sizeof im);
+  }
+  return n * tiles_per_image;
+}
+
+int PrePlanner::max_images() const {
+  const long long tiles_per_image = (long long)((W + kPreTC - 1) / kPreTC) * ((H + kPreTR - 1) / kPreTR);
+  return (int)std::max<long long>(1, std::min<long long>(1 << 20, ((1ll << 31) - 1) / tiles_per_image));
+}
+
+void launch_preprocess_batch(const void* plan_dev, int n, long long tiles, int W, int H, unsigned char* gray_dev, float* gray_f32_dev,
+                             hipStream_t s) {
+  if (n < 1 || tiles < 1 || tiles > 0x7fffffffll) fail(OCR_ERR_INTERNAL, "preprocess_batch: %d images, %lld tiles in one launch", n, tiles);
+  hipLaunchKernelGGL(preprocess_batch_kernel, dim3((unsigned)tiles), dim3(256), 0, s, static_cast<const uint32_t*>(plan_dev), n, W, H,
+                     gray_dev, gray_f32_dev);
+  OCR_HIP(hipGetLastError());
 }
 
 size_t preprocess_scratch_bytes(int w, int h, int W, int H) {

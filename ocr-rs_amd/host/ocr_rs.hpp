@@ -4,6 +4,7 @@
 // argument meaning and error behaviour (anyhow::Result -> ocr_rs::Error).
 //
 //   text_detection::resnet18(..) -> FuncT, FuncT::forward_t      model.rs:154-156, mod.rs:52-54
+//   text_detection::preprocess_images                            image_ops.rs:188-220, a batch per call
 //   text_detection::metrics::get_boxes_and_box_scores            metrics.rs:37-56
 //   char_recognition::Net::{new_, forward_t}, utils::topk        model.rs:13-39, utils.rs:28-43
 //   read_words: detected words -> glyphs -> text, the pipeline's segmentation step (README.md:20-26), which the reference never built
@@ -60,6 +61,23 @@ class FuncT {  // what resnet18(&nn::Path) returns
   ocr_det_t* h_ = nullptr;
 };
 inline FuncT resnet18(const void* weights, size_t bytes, int device = 0) { return FuncT(weights, bytes, device); }
+
+// image_ops::preprocess_image (image_ops.rs:188-220) after decoding, for a batch: every image's into_rgba() buffer (w x h, rows
+// contiguous) -> N x 1 x H x W frames of raw 0..255 luma (the input of forward_t) and the adjust values x0, y0, x1, y1, ...
+struct RgbaImage {
+  const uint8_t* data;
+  uint32_t width, height;
+};
+inline Tensor preprocess_images(const FuncT& net, const std::vector<RgbaImage>& images, std::vector<double>& adjust_values,
+                                uint32_t width = DEFAULT_WIDTH, uint32_t height = DEFAULT_HEIGHT) {
+  std::vector<ocr_image_t> descs(images.size());
+  for (size_t i = 0; i < images.size(); ++i) descs[i] = {images[i].data, (int32_t)images[i].width, (int32_t)images[i].height, 0};
+  Tensor out((int)images.size(), 1, (int)height, (int)width);
+  adjust_values.assign(2 * images.size(), 0.0);
+  check(ocr_preprocess_batch(net.handle(), descs.data(), (int)descs.size(), OCR_MEM_HOST, (int)width, (int)height, nullptr, out.data.data(),
+                             OCR_MEM_HOST, adjust_values.data()));
+  return out;
+}
 
 namespace metrics {
 using Polygon = std::vector<std::pair<uint32_t, uint32_t>>;

@@ -85,6 +85,13 @@ def preprocess_image(net: FuncT, rgba: np.ndarray, target_dim=(DEFAULT_WIDTH, DE
     return net.handle.preprocess_image(rgba, target_dim[0], target_dim[1])
 
 
+def preprocess_images(net: FuncT, images, target_dim=(DEFAULT_WIDTH, DEFAULT_HEIGHT)):
+    """preprocess_image for a batch of decoded RGBA images of differing sizes in one launch (ocr_preprocess_batch):
+    returns (GrayImages as N x H x W u8, adjust values N x 2: x then y), each frame what preprocess_image gives for that image alone."""
+    gray, _, adj = net.handle.preprocess_batch(images, target_dim[0], target_dim[1])
+    return gray, adj
+
+
 def get_boxes_and_box_scores(net: FuncT, pred, adjust_values, skip_degenerate: bool = False) -> PolygonScores:
     """metrics.rs:37-56.  `net` supplies the GPU/stream the HIP post-processing kernels run on.
     Raises OcrError(code 6) where the reference would abort on `expand_polygon(..).unwrap()`."""
