@@ -268,6 +268,13 @@ def test_lib() -> C.CDLL:
         L.ocr_test_rec_fc1.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.ocr_test_rec_fc2.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
         L.ocr_test_comm_assemble.argtypes = [C.POINTER(C.POINTER(Polygons)), C.c_int, C.POINTER(C.POINTER(Polygons))]
+        L.ocr_test_compose_taps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.ocr_test_phase_weights.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.ocr_test_pyr4_weights.argtypes = [C.c_void_p] * 3
+        L.ocr_test_phase_conv_run.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] +
+                                              [C.c_int] * 3 + [C.c_void_p, C.c_int])
+        L.ocr_test_pyr4_conv_run.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int])
         _test_lib = L
     return _test_lib
 
@@ -846,6 +853,48 @@ class Detector:
                                            p(out), p(out2)))
         return out, out2
 
+    def debug_phase_conv_run(self, form, x_nhwc, wphase, up, win=0, out_bf16=False, bias=None, relu=False, residual=None, poison=False,
+                             guard=64, sentinel=-7.0):
+        """One conv_igemm launch with STORE_PHASE on caller data (test hook): form 0 exact f32, 1 split bf16, 2 bf16 operands (rounded
+        inside).  x: N x h x w x Cin; wphase: [up*up][Cout][2x2][Cin] (phase_weights); residual: N x up h x up w x Cout, added IN PLACE (it is
+        what the output buffer holds before the launch, as the engine runs it); without one the buffer holds `sentinel`.  poison: the guard
+        regions around the source inside its allocation hold NaN instead of zeros.  Returns (out N x up h x up w x Cout f32, the `guard`
+        rows of Cout elements behind it, which went to the device as `sentinel`)."""
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+        x, wg, bi = f(x_nhwc), f(wphase), f(bias)
+        n, h, w, cin = x.shape
+        cout = wg.shape[1]
+        assert wg.shape == (up * up, cout, 4, cin), wg.shape
+        px = n * up * h * up * w
+        io = np.full((px + guard, cout), sentinel, np.float32)
+        if residual is not None:
+            io[:px] = np.asarray(residual, np.float32).reshape(px, cout)
+        check(test_lib().ocr_test_phase_conv_run(self._h, int(form), int(bool(out_bf16)), _ptr(x), n, h, w, cin, _ptr(wg), cout, int(up), int(win),
+                                                 None if bi is None else _ptr(bi), int(bool(relu)), int(residual is not None), int(bool(poison)),
+                                                 _ptr(io), int(guard)))
+        return io[:px].reshape(n, up * h, up * w, cout), io[px:]
+
+    def debug_pyr4_conv_run(self, form, levels, wpyr, nsrc=4, out_bf16=False, bias=None, relu=False, residual=None, launches=0, poison=False,
+                            guard=64, sentinel=-7.0):
+        """One (or, launches = 3, two) conv_igemm launches with SRC_PYR4 on caller data (test hook): form as above; levels = (p5, p4, p3, p2) as
+        N x (h << i) x (w << i) x 64 (p2 may be None with nsrc 3); wpyr: [64][64][21][64] (pyr4_weights); residual: N x 8h x 8w x 64, a separate
+        array; launches: 0 = pyr_group 0, 1 / 2 = that group alone, 3 = group 1 then 2.  poison: the gaps around the four sources inside their
+        shared allocation hold NaN.  Returns (out N x 8h x 8w x 64 f32, guard rows); the output buffer holds `sentinel` before the launch."""
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+        lv = [f(a) for a in levels]
+        n, h, w, _ = lv[0].shape
+        for i, a in enumerate(lv):
+            assert a is None or a.shape == (n, h << i, w << i, 64), (i, a.shape)
+        wg, bi, rs = f(wpyr), f(bias), f(residual)
+        assert wg.shape == (64, 64, 21, 64), wg.shape
+        px = n * 8 * h * 8 * w
+        assert rs is None or rs.size == px * 64
+        io = np.full((px + guard, 64), sentinel, np.float32)
+        p = lambda a: None if a is None else _ptr(a)
+        check(test_lib().ocr_test_pyr4_conv_run(self._h, int(form), int(bool(out_bf16)), p(lv[0]), p(lv[1]), p(lv[2]), p(lv[3]), n, h, w, _ptr(wg),
+                                                int(nsrc), p(bi), int(bool(relu)), p(rs), int(launches), int(bool(poison)), _ptr(io), int(guard)))
+        return io[:px].reshape(n, 8 * h, 8 * w, 64), io[px:]
+
     def debug_stem_run(self, form, frames, w64x49, scale64, bias64):
         """The stem alone on caller data (test hook): form 0 exact f32, 1 bf16 precision, 2 split bf16.  frames: N x H x W, uint8 (raw luma)
         or f32; w64x49: conv1.weight as [64][49].  Returns N x H/4 x W/4 x 64 f32 (form 1: the bf16 output widened)."""
@@ -1219,6 +1268,38 @@ def comm_assemble(shards):
         return polygons_to_python(out)
     finally:
         lib().ocr_polygons_free(out)
+
+
+# ---- the weight builders of the composed FPN (engine.hip; CPU only, through the test library)
+def compose_taps(out_ohwi, in_oi) -> np.ndarray:
+    """out (3x3, [cout][9][mid]) after in (1x1, [mid][cin]) -> f64 taps [cout][9][cin]."""
+    o = np.ascontiguousarray(out_ohwi, dtype=np.float32)
+    i = np.ascontiguousarray(in_oi, dtype=np.float32)
+    cout, nine, mid = o.shape
+    assert nine == 9 and i.shape[0] == mid
+    t = np.empty((cout, 9, i.shape[1]), np.float64)
+    check(test_lib().ocr_test_compose_taps(_ptr(o), cout, mid, _ptr(i), i.shape[1], _ptr(t)))
+    return t
+
+
+def phase_weights(taps, up: int) -> np.ndarray:
+    """f64 taps [cout][9][cin] of a 3x3 conv of the nearest-x-up upsample -> f32 [up*up][cout][2x2][cin] as the engine builds them."""
+    t = np.ascontiguousarray(taps, dtype=np.float64)
+    cout, nine, cin = t.shape
+    assert nine == 9
+    w = np.empty((up * up, cout, 4, cin), np.float32)
+    check(test_lib().ocr_test_phase_weights(_ptr(t), cout, cin, int(up), _ptr(w)))
+    return w
+
+
+def pyr4_weights(bin1_ohwi, scale64) -> np.ndarray:
+    """bin_conv1 [64][9][256] and bin_bn1's folded scale [64] -> f32 [64 phases][64][21 slots][64] as the engine builds them."""
+    o = np.ascontiguousarray(bin1_ohwi, dtype=np.float32)
+    sc = np.ascontiguousarray(scale64, dtype=np.float32)
+    assert o.shape == (64, 9, 256) and sc.shape == (64,)
+    w = np.empty((64, 64, 21, 64), np.float32)
+    check(test_lib().ocr_test_pyr4_weights(_ptr(o), _ptr(sc), _ptr(w)))
+    return w
 
 
 # ---- host-geometry hooks (CPU only; used by tests to pin the C++ geometry to the KATs)

@@ -94,21 +94,23 @@ ConvW Detector::make_conv(const WeightBlob& wb, const std::string& wname, const 
   return cw;
 }
 
-// out (3x3, 256 -> 64, OHWI) after in (1x1, cin -> 256): T[o][tap][i] = sum_c out[o][tap][c] * in[c][i], in f64
-static std::vector<double> compose_taps(const ConvW& out, const ConvW& in) {
-  const int cin = in.cin, mid = out.cin;
-  std::vector<double> t((size_t)out.cout * 9 * cin, 0.0);
-  for (int o = 0; o < out.cout; ++o)
+// out (3x3, mid -> cout, OHWI) after in (1x1, cin -> mid): T[o][tap][i] = sum_c out[o][tap][c] * in[c][i], in f64
+std::vector<double> compose_taps(const float* out_ohwi, int cout, int mid, const float* in_oi, int cin) {
+  std::vector<double> t((size_t)cout * 9 * cin, 0.0);
+  for (int o = 0; o < cout; ++o)
     for (int k = 0; k < 9; ++k) {
       double* row = &t[((size_t)o * 9 + k) * cin];
-      const float* ow = &out.host[((size_t)o * 9 + k) * mid];
+      const float* ow = &out_ohwi[((size_t)o * 9 + k) * mid];
       for (int c = 0; c < mid; ++c) {
         const double a = ow[c];
-        const float* iw = &in.host[(size_t)c * cin];
+        const float* iw = &in_oi[(size_t)c * cin];
         for (int i = 0; i < cin; ++i) row[i] += a * (double)iw[i];
       }
     }
   return t;
+}
+static std::vector<double> compose_taps(const ConvW& out, const ConvW& in) {
+  return compose_taps(out.host.data(), out.cout, out.cin, in.host.data(), in.cin);
 }
 
 ConvW Detector::finish_composed(std::vector<float>&& t, int cout, int cin, int ks) {
@@ -182,7 +184,7 @@ ConvW Detector::compose_lateral(const ConvW& out, const ConvW& in) {
 //   a = up-1     : dy 0, 1 -> i (tap 0);  dy 2 -> i+1 (tap 1)             window starts at i
 // (same for columns), and zero padding of the high-res tensor is zero padding of the low-res one.
 // Layout [phase = up a + b][cout][2x2][cin].
-ConvW Detector::phase_conv(const std::vector<double>& t, int cout, int cin, int up) {
+std::vector<float> phase_weights(const std::vector<double>& t, int cout, int cin, int up) {
   std::vector<float> w((size_t)up * up * cout * 4 * cin);
   auto tap_of = [up](int a, int d) { return a == 0 ? (d == 0 ? 0 : 1) : (a == up - 1 && d == 2) ? 1 : 0; };
   // phases strictly inside a row / column of phases use one tap in that direction; the kernel walks the
@@ -202,9 +204,56 @@ ConvW Detector::phase_conv(const std::vector<double>& t, int cout, int cin, int 
         float* dst = &w[(((size_t)(a * up + b) * cout + o) * 4) * cin];
         for (size_t i = 0; i < acc.size(); ++i) dst[i] = (float)acc[i];
       }
-  ConvW cw = finish_composed(std::move(w), cout, cin, 2);
+  return w;
+}
+
+ConvW Detector::phase_conv(const std::vector<double>& t, int cout, int cin, int up) {
+  ConvW cw = finish_composed(phase_weights(t, cout, cin, up), cout, cin, 2);
   cw.up = up;
   return cw;
+}
+
+// slice s of bin_conv1's 256 input channels (p5, p4, p3, p2 = s 0..3) as f64 taps [64][9][64], bin_bn1's scale folded in
+static std::vector<double> bin1_slice(const float* ohwi, const float* scale64, int sidx) {
+  std::vector<double> t((size_t)64 * 9 * 64);
+  for (int o = 0; o < 64; ++o)
+    for (int k = 0; k < 9; ++k)
+      for (int c = 0; c < 64; ++c)
+        t[((size_t)o * 9 + k) * 64 + c] = (double)scale64[o] * (double)ohwi[((size_t)o * 9 + k) * 256 + sidx * 64 + c];
+  return t;
+}
+
+// [phase = 8 a + b][cout][slot][64]: slots 4 s + (th * nw + tw) for the upsampled sources s = 0 (p5, up 8),
+// 1 (p4, up 4), 2 (p3, up 2) with the tap merging of phase_weights(), slots 12 + 3 dy + dx for p2
+std::vector<float> pyr4_weights(const float* bin1_ohwi, const float* scale64) {
+  std::vector<float> w((size_t)64 * 64 * 21 * 64, 0.f);
+  std::vector<double> acc((size_t)4 * 64);
+  for (int sidx = 0; sidx < 4; ++sidx) {
+    const std::vector<double> t = bin1_slice(bin1_ohwi, scale64, sidx);  // [cout][9][64], bin_bn1 scale folded
+    const int up = 8 >> sidx;
+    auto tap_of = [up](int a, int d) { return a == 0 ? (d == 0 ? 0 : 1) : (a == up - 1 && d == 2) ? 1 : 0; };
+    auto taps_of = [up](int a) { return (a == 0 || a == up - 1) ? 2 : 1; };
+    for (int a = 0; a < 8; ++a)
+      for (int b = 0; b < 8; ++b)
+        for (int o = 0; o < 64; ++o) {
+          float* dst = &w[(((size_t)(a * 8 + b) * 64 + o) * 21 + (sidx < 3 ? 4 * sidx : 12)) * 64];
+          if (sidx == 3) {
+            for (int k = 0; k < 9; ++k)
+              for (int c = 0; c < 64; ++c) dst[k * 64 + c] = (float)t[((size_t)o * 9 + k) * 64 + c];
+            continue;
+          }
+          const int as = a & (up - 1), bs = b & (up - 1);
+          std::fill(acc.begin(), acc.end(), 0.0);
+          for (int dy = 0; dy < 3; ++dy)
+            for (int dx = 0; dx < 3; ++dx) {
+              const int tp = tap_of(as, dy) * taps_of(bs) + tap_of(bs, dx);
+              const double* src = &t[((size_t)o * 9 + dy * 3 + dx) * 64];
+              for (int c = 0; c < 64; ++c) acc[(size_t)tp * 64 + c] += src[c];
+            }
+          for (size_t i = 0; i < acc.size(); ++i) dst[i] = (float)acc[i];
+        }
+  }
+  return w;
 }
 
 // B_k = out_k o up2 o in_{k+1}
@@ -393,50 +442,13 @@ Detector::Detector(const void* blob, size_t bytes, int device, const char* optio
   }
   bin1_ = make_conv(wb, "bin_conv1.weight", "bin_bn1", 64, 256, 3);
   if (fpn_composed_) {
-    // slice s of the 256 input channels (p5, p4, p3, p2 = s 0..3), bin_bn1's scale folded in
-    auto slice = [&](int sidx) {
-      std::vector<double> t((size_t)64 * 9 * 64);
-      for (int o = 0; o < 64; ++o)
-        for (int k = 0; k < 9; ++k)
-          for (int c = 0; c < 64; ++c)
-            t[((size_t)o * 9 + k) * 64 + c] = (double)bin1_.host_scale[o] * (double)bin1_.host[((size_t)o * 9 + k) * 256 + sidx * 64 + c];
-      return t;
-    };
+    auto slice = [&](int sidx) { return bin1_slice(bin1_.host.data(), bin1_.host_scale.data(), sidx); };
     for (int l = 0; l < 3; ++l) bin_up_[l] = phase_conv(slice(2 - l), 64, 64, 2 << l);
     const std::vector<double> t2 = slice(3);
     bin_p2_ = finish_composed(std::vector<float>(t2.begin(), t2.end()), 64, 64, 3);
     bin_up_[2].bias = bin1_.bias;  // the p5 term is accumulated last: it adds the bias and applies the ReLU
     if (bin_pyr_on_) {
-      // [phase = 8 a + b][cout][slot][64]: slots 4 s + (th * nw + tw) for the upsampled sources s = 0 (p5, up 8),
-      // 1 (p4, up 4), 2 (p3, up 2) with the tap merging of phase_conv(), slots 12 + 3 dy + dx for p2
-      std::vector<float> w((size_t)64 * 64 * 21 * 64, 0.f);
-      std::vector<double> acc((size_t)4 * 64);
-      for (int sidx = 0; sidx < 4; ++sidx) {
-        const std::vector<double> t = slice(sidx);  // [cout][9][64], bin_bn1 scale folded
-        const int up = 8 >> sidx;
-        auto tap_of = [up](int a, int d) { return a == 0 ? (d == 0 ? 0 : 1) : (a == up - 1 && d == 2) ? 1 : 0; };
-        auto taps_of = [up](int a) { return (a == 0 || a == up - 1) ? 2 : 1; };
-        for (int a = 0; a < 8; ++a)
-          for (int b = 0; b < 8; ++b)
-            for (int o = 0; o < 64; ++o) {
-              float* dst = &w[(((size_t)(a * 8 + b) * 64 + o) * 21 + (sidx < 3 ? 4 * sidx : 12)) * 64];
-              if (sidx == 3) {
-                for (int k = 0; k < 9; ++k)
-                  for (int c = 0; c < 64; ++c) dst[k * 64 + c] = (float)t[((size_t)o * 9 + k) * 64 + c];
-                continue;
-              }
-              const int as = a & (up - 1), bs = b & (up - 1);
-              std::fill(acc.begin(), acc.end(), 0.0);
-              for (int dy = 0; dy < 3; ++dy)
-                for (int dx = 0; dx < 3; ++dx) {
-                  const int tp = tap_of(as, dy) * taps_of(bs) + tap_of(bs, dx);
-                  const double* src = &t[((size_t)o * 9 + dy * 3 + dx) * 64];
-                  for (int c = 0; c < 64; ++c) acc[(size_t)tp * 64 + c] += src[c];
-                }
-              for (size_t i = 0; i < acc.size(); ++i) dst[i] = (float)acc[i];
-            }
-      }
-      bin_pyr_ = finish_composed(std::move(w), 64, 64, 3);
+      bin_pyr_ = finish_composed(pyr4_weights(bin1_.host.data(), bin1_.host_scale.data()), 64, 64, 3);
       bin_pyr_.up = 8;
       bin_pyr_.bias = bin1_.bias;
       if (winograd_fused_) {

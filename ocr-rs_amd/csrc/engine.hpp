@@ -32,6 +32,13 @@ class DeviceArena {  // bump allocator over one hipMalloc (weights)
 
 // U = G g G^T of a 3x3 conv given as [Cout][3x3][Cin], laid out [(m+2)^2][Cout][Cin] for F(m x m, 3x3), m = 2 or 4 (winograd.hip)
 std::vector<float> winograd_weights(const float* ohwi, int cout, int cin, int m = 2);
+// The weight builders of the composed FPN and of bin_conv1 over the pyramid (engine.hip; layouts in the comments there):
+// out (3x3, mid -> cout, OHWI) after in (1x1, cin -> mid, [mid][cin]) as f64 taps [cout][9][cin]
+std::vector<double> compose_taps(const float* out_ohwi, int cout, int mid, const float* in_oi, int cin);
+// f64 taps [cout][9][cin] of a 3x3 conv of the nearest-x-up upsample -> the low-res phase convs, f32 [up*up][cout][2x2][cin]
+std::vector<float> phase_weights(const std::vector<double>& taps, int cout, int cin, int up);
+// bin_conv1 (OHWI [64][9][256], input channels p5, p4, p3, p2) with bin_bn1's folded scale [64] -> f32 [64 phases][64][21 slots][64]
+std::vector<float> pyr4_weights(const float* bin1_ohwi, const float* scale64);
 
 struct ConvW {
   float* w = nullptr;      // [Cout][ks*ks][Cin]

@@ -1026,3 +1026,190 @@ int ocr_test_w43_debug(int d) { ocr::winograd43_set_debug(d); return 0; }
 #endif
 
 }  // extern "C"
+
+// ---- the phase and pyramid convs of the composed FPN (conv_igemm.hip STORE_PHASE / SRC_PYR4) and their weight builders (engine.hip) ----
+namespace {
+// host f32 -> device buffer of the form's element type, n_pre / n_post elements of `pad` around it inside the allocation
+struct Padded {
+  char* base;      // start of the allocation
+  char* data;      // the tensor
+  size_t bytes;    // the whole allocation
+};
+void fill_elems(std::vector<uint8_t>& buf, size_t at_bytes, const float* src, size_t elems, bool bf, float pad) {   // src == nullptr: `pad`
+  if (bf) {
+    uint16_t* d = reinterpret_cast<uint16_t*>(buf.data() + at_bytes);
+    for (size_t i = 0; i < elems; ++i) d[i] = hook_bf16_bits(src ? src[i] : pad);
+  } else {
+    float* d = reinterpret_cast<float*>(buf.data() + at_bytes);
+    for (size_t i = 0; i < elems; ++i) d[i] = src ? src[i] : pad;
+  }
+}
+// out_io [elems] f32 <-> a device buffer of f32 or bf16
+void* upload_io(HookBuffers& b, const float* io, size_t elems, bool bf) { return bf ? b.as_bf16(io, elems) : static_cast<void*>(b.f32(io, elems)); }
+void download_io(float* io, const void* dev, size_t elems, bool bf) {
+  if (!bf) {
+    OCR_HIP(hipMemcpy(io, dev, elems * 4, hipMemcpyDeviceToHost));
+    return;
+  }
+  std::vector<uint16_t> t(elems);
+  OCR_HIP(hipMemcpy(t.data(), dev, elems * 2, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < elems; ++i) {
+    const uint32_t u = (uint32_t)t[i] << 16;
+    std::memcpy(&io[i], &u, 4);
+  }
+}
+// the weights of a form: 0 f32 as built, 1 split3_weights_tiled (rows of `wrow`), 2 bf16
+const void* upload_form_weights(HookBuffers& b, int form, const float* w, size_t count, int wrow, size_t* bytes) {
+  if (form == 1) {
+    *bytes = count * 6;
+    return b.u16(ocr::split3_weights_tiled(w, count, wrow));
+  }
+  *bytes = count * (form == 2 ? 2 : 4);
+  return form == 2 ? b.as_bf16(w, count) : static_cast<const void*>(b.f32(w, count));
+}
+}  // namespace
+
+extern "C" {
+
+// host only: engine.hip's compose_taps.  out_ohwi [cout][9][mid], in_oi [mid][cin] -> taps_out [cout][9][cin] f64
+int ocr_test_compose_taps(const float* out_ohwi, int cout, int mid, const float* in_oi, int cin, double* taps_out) {
+  return guard([&] {
+    if (!out_ohwi || !in_oi || !taps_out || cout <= 0 || mid <= 0 || cin <= 0) ocr::fail(OCR_ERR_INVALID, "compose_taps hook: bad argument");
+    const std::vector<double> t = ocr::compose_taps(out_ohwi, cout, mid, in_oi, cin);
+    std::copy(t.begin(), t.end(), taps_out);
+  });
+}
+// host only: engine.hip's phase_weights.  taps [cout][9][cin] f64 -> w_out [up*up][cout][2x2][cin] f32
+int ocr_test_phase_weights(const double* taps, int cout, int cin, int up, float* w_out) {
+  return guard([&] {
+    if (!taps || !w_out || cout <= 0 || cin <= 0 || (up != 2 && up != 4 && up != 8)) ocr::fail(OCR_ERR_INVALID, "phase_weights hook: bad argument");
+    const std::vector<float> w = ocr::phase_weights(std::vector<double>(taps, taps + (size_t)cout * 9 * cin), cout, cin, up);
+    std::copy(w.begin(), w.end(), w_out);
+  });
+}
+// host only: engine.hip's pyr4_weights.  bin1_ohwi [64][9][256], scale64 [64] -> w_out [64 phases][64][21 slots][64] f32
+int ocr_test_pyr4_weights(const float* bin1_ohwi, const float* scale64, float* w_out) {
+  return guard([&] {
+    if (!bin1_ohwi || !scale64 || !w_out) ocr::fail(OCR_ERR_INVALID, "null argument");
+    const std::vector<float> w = ocr::pyr4_weights(bin1_ohwi, scale64);
+    std::copy(w.begin(), w.end(), w_out);
+  });
+}
+
+// one launch_conv_igemm with STORE_PHASE / SRC_PLAIN on caller data.  form: 0 exact f32, 1 split bf16 (weights through split3_weights_tiled
+// with rows of 4 * cin, as Detector::add_split_weights), 2 bf16 operands (x and the weights rounded on the way in); out_bf16: bf16 results.
+// x: [n][h][w][cin]; wphase: [up*up][cout][2x2][cin] (phase_weights); bias [cout] or null.  out_io: [n][up h][up w][cout] and, behind it,
+// guard_rows rows of cout elements, f32 on the host (rounded to bf16 on the way in and widened on the way out with out_bf16): uploaded
+// before the launch and downloaded whole after it.  residual_in_place: the launch's residual IS that buffer, as the engine runs it.  The
+// source sits between two guard regions of its allocation that src_bytes does not cover: zeros, or with poison != 0 quiet NaN.  Which
+// combinations exist is conv_igemm.hip's check(): its refusals come back as errors
+int ocr_test_phase_conv_run(ocr_det_t* det, int form, int out_bf16, const float* x, int n, int h, int w, int cin, const float* wphase, int cout, int up,
+                            int win, const float* bias, int relu, int residual_in_place, int poison, float* out_io, int guard_rows) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !x || !wphase || !out_io) fail(OCR_ERR_INVALID, "null argument");
+    if (form < 0 || form > 2 || n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || up <= 0 || up > 8 || guard_rows < 0)
+      fail(OCR_ERR_INVALID, "phase conv hook: bad form or shape");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    HookBuffers b;
+    const bool in_bf = form == 2, out_bf = out_bf16 != 0;
+    const size_t ies = in_bf ? 2 : 4;
+    const size_t x_e = (size_t)n * h * w * cin, w_e = (size_t)up * up * cout * 4 * cin;
+    const size_t out_e = ((size_t)n * up * h * up * w + guard_rows) * cout;
+    const float pad = poison ? std::numeric_limits<float>::quiet_NaN() : 0.f;
+    const size_t gap = (((size_t)2 * (w + 2) * cin * ies + 4095) / 4096) * 4096;   // more than two low-res rows on either side
+    std::vector<uint8_t> img(gap + x_e * ies + gap);
+    fill_elems(img, 0, nullptr, gap / ies, in_bf, pad);
+    fill_elems(img, gap, x, x_e, in_bf, 0.f);
+    fill_elems(img, gap + x_e * ies, nullptr, gap / ies, in_bf, pad);
+    char* d_x = static_cast<char*>(b.raw(img.data(), img.size()));
+    ConvDesc d{};
+    d.in_bf16 = in_bf ? 1 : 0;
+    d.out_bf16 = out_bf ? 1 : 0;
+    d.x3 = form == 1 ? 1 : 0;
+    d.src_mode = SRC_PLAIN;
+    d.src[0] = d_x + gap;
+    d.src_bytes = x_e * ies;
+    d.wgt = upload_form_weights(b, form, wphase, w_e, 4 * cin, &d.wgt_bytes);
+    d.N = n; d.Hin = h; d.Win = w; d.Cin = cin; d.Ho = h; d.Wo = w; d.Cout = cout;
+    d.ks = 2; d.stride = 1; d.pad = 1; d.up = up; d.win = win;
+    d.bias = bias ? b.f32(bias, cout) : nullptr;
+    d.relu = relu ? 1 : 0;
+    d.store_mode = STORE_PHASE;
+    d.name = "test_phase_conv";
+    void* d_out = upload_io(b, out_io, out_e, out_bf);
+    d.out = d_out;
+    d.residual = residual_in_place ? d_out : nullptr;
+    launch_conv_igemm(d, s);
+    OCR_HIP(hipStreamSynchronize(s));
+    download_io(out_io, d_out, out_e, out_bf);
+  });
+}
+
+// the same for SRC_PYR4: bin_conv1 over [up8(p5), up4(p4), up2(p3), p2] on the p5 grid.  p5 [n][h][w][64], p4 [n][2h][2w][64], p3 [n][4h][4w][64],
+// p2 [n][8h][8w][64] (p2 may be null with nsrc 3: its place then holds the gaps' fill); the hook puts them into ONE allocation, a gap in front
+// of, between and behind them, src_bytes covering all of it - zeros, or with poison != 0 quiet NaN: a correct kernel uses no byte of a gap.
+// wpyr: [64 phases][64][21 slots][64] (pyr4_weights); nsrc 3 or 4; residual: [n][8h][8w][64] of the results' type, or null.  launches: 0 = one
+// launch with pyr_group 0, 1 = pyr_group 1 only, 2 = pyr_group 2 only, 3 = 1 then 2 as the engine runs them.  out_io as above
+int ocr_test_pyr4_conv_run(ocr_det_t* det, int form, int out_bf16, const float* p5, const float* p4, const float* p3, const float* p2, int n, int h, int w,
+                           const float* wpyr, int nsrc, const float* bias, int relu, const float* residual, int launches, int poison, float* out_io,
+                           int guard_rows) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !p5 || !p4 || !p3 || !wpyr || !out_io) fail(OCR_ERR_INVALID, "null argument");
+    if (form < 0 || form > 2 || n <= 0 || h <= 0 || w <= 0 || guard_rows < 0 || launches < 0 || launches > 3 || (nsrc != 3 && nsrc != 4) || (nsrc == 4 && !p2))
+      fail(OCR_ERR_INVALID, "pyramid conv hook: bad form, shape, sources or launches");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    HookBuffers b;
+    const bool in_bf = form == 2, out_bf = out_bf16 != 0;
+    const size_t ies = in_bf ? 2 : 4;
+    const size_t w_e = (size_t)64 * 64 * 21 * 64, px = (size_t)n * 8 * h * 8 * w, out_e = (px + guard_rows) * 64;
+    const float pad = poison ? std::numeric_limits<float>::quiet_NaN() : 0.f;
+    const float* lv[4] = {p5, p4, p3, p2};
+    size_t lv_e[4], lv_at[4], at = 0;
+    for (int i = 0; i < 4; ++i) {
+      lv_e[i] = (size_t)n * (h << i) * (w << i) * 64;
+      const size_t gap = (((size_t)2 * ((w << i) + 2) * 64 * ies + 4095) / 4096) * 4096;   // more than two rows of the level behind it
+      at += gap;
+      lv_at[i] = at;
+      at += lv_e[i] * ies;
+    }
+    const size_t total = at + 8192 + (((size_t)2 * (8 * w + 2) * 64 * ies + 4095) / 4096) * 4096;
+    std::vector<uint8_t> img(total);
+    fill_elems(img, 0, nullptr, total / ies, in_bf, pad);
+    for (int i = 0; i < 4; ++i)
+      if (lv[i]) fill_elems(img, lv_at[i], lv[i], lv_e[i], in_bf, 0.f);
+    char* d_src = static_cast<char*>(b.raw(img.data(), img.size()));
+    ConvDesc d{};
+    d.in_bf16 = in_bf ? 1 : 0;
+    d.out_bf16 = out_bf ? 1 : 0;
+    d.x3 = form == 1 ? 1 : 0;
+    d.src_mode = SRC_PYR4;
+    for (int i = 0; i < 4; ++i) d.src[i] = d_src + lv_at[i];
+    d.src_base = d_src;
+    d.src_bytes = total;
+    d.wgt = upload_form_weights(b, form, wpyr, w_e, 21 * 64, &d.wgt_bytes);
+    d.N = n; d.Hin = h; d.Win = w; d.Cin = 64; d.Ho = h; d.Wo = w; d.Cout = 64;
+    d.ks = 3; d.stride = 1; d.pad = 0; d.up = 8;
+    d.pyr_nsrc = nsrc;
+    d.bias = bias ? b.f32(bias, 64) : nullptr;
+    d.relu = relu ? 1 : 0;
+    d.store_mode = STORE_PHASE;
+    d.name = "test_pyr4_conv";
+    d.residual = residual ? upload_io(b, residual, px * 64, out_bf) : nullptr;
+    void* d_out = upload_io(b, out_io, out_e, out_bf);
+    d.out = d_out;
+    for (int g = 1; g <= 2; ++g) {
+      if (launches != 0 && !(launches & g)) continue;
+      d.pyr_group = launches == 0 ? 0 : g;
+      launch_conv_igemm(d, s);
+      if (launches == 0) break;
+    }
+    OCR_HIP(hipStreamSynchronize(s));
+    download_io(out_io, d_out, out_e, out_bf);
+  });
+}
+
+}  // extern "C"

@@ -11,7 +11,8 @@ Per kernel a *Case class im2cols the operands, runs the kernel's epilogue in f32
 output of the same layout (an emulation's or the GPU's) against the same pipeline in f64:
   rms(out) = sqrt(mean(((out - ref) / norm)^2)),  norm = sum |a||b| * |scale| carried through the epilogue.
 `bar(case)` = (rms of six products, smallest rms of five among the drops that change anything, their geometric mean).
-The *_family functions are the inputs of tests/test_gpu_stem_head_kernels.py; tests/test_split_bf16_emul.py checks on the CPU
+The *_family functions are the inputs of tests/test_gpu_stem_head_kernels.py and tests/test_gpu_phase_kernels.py;
+tests/test_split_bf16_emul.py and tests/test_phase_conv_oracle.py check on the CPU
 that each of them separates five products from six by at least 5 x."""
 import numpy as np
 import torch
@@ -255,6 +256,61 @@ class ConvCase(_Case):
         return acc.astype(dt).reshape(self.shape)
 
 
+class _PhasedCase(_Case):
+    """A launch that is one GEMM per output phase (conv_igemm's STORE_PHASE forms): blocks of (A [cells][K], B [K][cout], a, b) with the
+    result of block (a, b) at out[:, a::up, b::up]; K differs between the phases, so every block is emulated on its own.  No epilogue terms."""
+    kgroup = 16
+
+    def _place(self, per_block, dt):
+        n, h, w, cout = self.grid
+        out = np.zeros((n, self.up * h, self.up * w, cout), dt)
+        for (A, B, a, b), v in zip(self.blocks, per_block):
+            out[:, a::self.up, b::self.up] = np.asarray(v, dt).reshape(n, h, w, cout)
+        return out
+
+    def emulated(self, products=PRODUCTS):
+        return self._place([emulate(A, B, products, self.kgroup) for A, B, a, b in self.blocks], f32)
+
+    def chain(self):
+        return self._place([f32_chain(A, B) for A, B, a, b in self.blocks], f32)
+
+    def _finish(self):
+        self.ref = self._place([A.astype(f64) @ B.astype(f64) for A, B, a, b in self.blocks], f64)
+        self.norm = self._place([np.abs(A).astype(f64) @ np.abs(B).astype(f64) for A, B, a, b in self.blocks], f64)
+
+
+class PhaseCase(_PhasedCase):
+    """conv_igemm STORE_PHASE / SRC_PLAIN (debug_phase_conv_run, win 0 or 1: the same products in the same order): x [n][h][w][cin],
+    wphase [up*up][cout][2x2][cin] as built; per phase K = tap * cin + c over its active taps, in groups of 16.  Output [n][up h][up w][cout]."""
+
+    def __init__(self, x, wphase, up):
+        from tests import phase_conv_oracle as O
+        x, wp = np.asarray(x, f32), np.asarray(wphase, f32)
+        n, h, w, cin = x.shape
+        cout = wp.shape[1]
+        self.up, self.grid = up, (n, h, w, cout)
+        self.blocks = []
+        for a, b, A in O.phase_operands(x, up):
+            nt = A.shape[1] // cin
+            self.blocks.append((A.astype(f32), np.ascontiguousarray(wp[a * up + b, :, :nt].reshape(cout, nt * cin).T), a, b))
+        self._finish()
+
+
+class PyrCase(_PhasedCase):
+    """conv_igemm SRC_PYR4 (debug_pyr4_conv_run; one launch or the phase blocks and the corner launch: the same products in the same
+    order): levels (p5, p4, p3[, p2]), wpyr [64][64][21][64] as built; per phase K ordered (source, tap, channel) over the active slots, in
+    groups of 16.  Output [n][8 h][8 w][64]."""
+
+    def __init__(self, levels, wpyr, nsrc=3):
+        from tests import phase_conv_oracle as O
+        lv = [None if a is None else np.asarray(a, f32) for a in levels]
+        wp = np.asarray(wpyr, f32)
+        n, h, w, _ = lv[0].shape
+        self.up, self.grid = 8, (n, h, w, 64)
+        self.blocks = [(A.astype(f32), np.ascontiguousarray(wp[8 * a + b][:, slots].reshape(64, -1).T), a, b) for a, b, slots, A in O.pyr4_operands(lv, nsrc)]
+        self._finish()
+
+
 # ---- the input families of tests/test_gpu_stem_head_kernels.py -------------------------------------------------------------
 
 STEM_FAMILIES = ("fraction", "luma_f32", "luma_u8")
@@ -313,3 +369,27 @@ def conv_family(case, seed=3):
     x = rng.standard_normal((n, h, w, cin)).astype(f32)
     wg = (rng.standard_normal((cout, ks * ks, cin)) / np.sqrt(ks * ks * cin)).astype(f32)
     return x, wg, stride
+
+
+# ---- ... and of tests/test_gpu_phase_kernels.py (group K5): N(0,1) activations, taps N(0,1) / sqrt(9 cin) merged by the engine's builders
+# (`build` = capi.phase_weights / capi.pyr4_weights, passed in so that this module stays free of the library)
+
+PHASE_CASES = ((2, 6, 10, 128, 64, 2), (2, 6, 10, 256, 64, 2))   # n, h, w, cin, cout, up: K = 512 and 1024 per phase
+PYR_CASES = ((2, 3, 5, 3),)                                     # n, h, w, nsrc: K = 192 .. 768 per phase
+
+
+def phase_family(case, build, seed=21):
+    n, h, w, cin, cout, up = case
+    rng = np.random.default_rng(seed + cin)
+    x = rng.standard_normal((n, h, w, cin)).astype(f32)
+    t = rng.standard_normal((cout, 9, cin)) / np.sqrt(9 * cin)
+    return x, build(t, up), up
+
+
+def pyr_family(case, build, seed=23):
+    n, h, w, nsrc = case
+    rng = np.random.default_rng(seed)
+    levels = [rng.standard_normal((n, h << i, w << i, 64)).astype(f32) for i in range(4)]
+    wg = (rng.standard_normal((64, 9, 256)) / np.sqrt(9 * 256)).astype(f32)
+    scale = (0.5 + rng.random(64)).astype(f32)
+    return levels, build(wg, scale), nsrc
