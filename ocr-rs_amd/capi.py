@@ -275,6 +275,10 @@ def test_lib() -> C.CDLL:
                                               [C.c_int] * 3 + [C.c_void_p, C.c_int])
         L.ocr_test_pyr4_conv_run.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int])
+        L.ocr_test_winograd_weights.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.ocr_test_winograd43_fragments.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.ocr_test_winograd_run.argtypes = ([C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4 +
+                                            [C.c_void_p, C.c_int])
         _test_lib = L
     return _test_lib
 
@@ -967,6 +971,33 @@ class Detector:
                                                 int(relu), int(unfused), _ptr(out)))
         return out
 
+    def debug_winograd_run(self, form, x_nhwc, wgt_ohwi, scale=None, bias=None, residual=None, relu=False, inplace=False, num_cus=0,
+                           guard=64, poison=False, sentinel=-7.0):
+        """One 3x3 s1 p1 conv through a Winograd form on caller data (test hook): form 0 the fused F(4x4,3x3) kernel (num_cus sizes its grid),
+        1 the three launches of F(4x4,3x3) with the 36 split-bf16 GEMMs as the engine runs them, 2 the same with exact-f32 GEMMs, 3 the three
+        launches of F(2x2,3x3).  x: N x H x W x Cin; wgt: [Cout][9][Cin]; residual: N x H x W x Cout - with inplace it is what the output buffer
+        holds before the launch and the launch gets residual == y, otherwise a separate buffer; without one the buffer holds `sentinel`.
+        poison: the regions around the source inside its allocation hold NaN instead of zeros.  Returns (out N x H x W x Cout f32, the `guard`
+        rows of Cout elements behind it, which went to the device as `sentinel`)."""
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+        x, wg, sc, bi = f(x_nhwc), f(wgt_ohwi), f(scale), f(bias)
+        n, h, w, cin = x.shape
+        cout = wg.shape[0]
+        assert wg.shape == (cout, 9, cin), wg.shape
+        assert not inplace or residual is not None
+        px = n * h * w
+        io = np.full((px + guard, cout), sentinel, np.float32)
+        rs = None
+        if residual is not None:
+            rs = np.ascontiguousarray(np.asarray(residual, np.float32).reshape(px, cout))
+            if inplace:
+                io[:px] = rs
+                rs = None
+        p = lambda a: None if a is None else _ptr(a)
+        check(test_lib().ocr_test_winograd_run(self._h, int(form), _ptr(x), n, h, w, cin, _ptr(wg), cout, p(sc), p(bi), p(rs), int(bool(relu)),
+                                               int(bool(inplace)), int(num_cus), int(bool(poison)), _ptr(io), int(guard)))
+        return io[:px].reshape(n, h, w, cout), io[px:]
+
     def debug_box_scores(self, pred_hw: np.ndarray, polys):
         """Test hook: raw (sum, count) of the GPU box-score kernel for given polygons."""
         pred = np.ascontiguousarray(pred_hw, dtype=np.float32)
@@ -1300,6 +1331,27 @@ def pyr4_weights(bin1_ohwi, scale64) -> np.ndarray:
     w = np.empty((64, 64, 21, 64), np.float32)
     check(test_lib().ocr_test_pyr4_weights(_ptr(o), _ptr(sc), _ptr(w)))
     return w
+
+
+# ---- the host side of the Winograd convs (engine.hip, winograd43_fused.hip; CPU only, through the test library)
+def winograd_weights(wgt_ohwi, m: int = 4) -> np.ndarray:
+    """[cout][9][cin] -> U = G g G^T as f32 [(m+2)^2][cout][cin], as the engine builds it (f64, rounded once)."""
+    g = np.ascontiguousarray(wgt_ohwi, dtype=np.float32)
+    cout, nine, cin = g.shape
+    assert nine == 9
+    u = np.empty(((m + 2) ** 2, cout, cin), np.float32)
+    check(test_lib().ocr_test_winograd_weights(_ptr(g), cout, cin, int(m), _ptr(u)))
+    return u
+
+
+def winograd43_fragments(u) -> np.ndarray:
+    """U [36][cout][cin] -> the fused kernel's MFMA B-fragment order [cout/64][cin/16][36][4 waves][64 lanes][4]."""
+    u = np.ascontiguousarray(u, dtype=np.float32)
+    comps, cout, cin = u.shape
+    assert comps == 36
+    f = np.empty(u.size, np.float32)
+    check(test_lib().ocr_test_winograd43_fragments(_ptr(u), cout, cin, _ptr(f)))
+    return f.reshape(cout // 64, cin // 16, 36, 4, 64, 4)
 
 
 # ---- host-geometry hooks (CPU only; used by tests to pin the C++ geometry to the KATs)

@@ -151,6 +151,33 @@ std::vector<float> winograd_weights(const float* ohwi, int cout, int cin, int m)
   return u;
 }
 
+// The GEMMs of a three-launch Winograd conv: `comps` = (m+2)^2 independent problems M_xi [T][Cout] = V_xi [T][Cin] x U_xi^T in one batched
+// conv_igemm launch.  v: [comps][T][Cin] f32; u: winograd_weights' [comps][Cout][Cin] f32, or with x3 its split3_weights_tiled planes
+// (rows of Cin); m: [comps][T][Cout].  Returns the descriptor it launched (the profiler names the kernel from it)
+ConvDesc launch_winograd_gemm(const float* v, const void* u, bool x3, int comps, size_t T, int cin, int cout, float* m, const char* name, hipStream_t s) {
+  ConvDesc d{};
+  d.src[0] = v;
+  d.src_mode = SRC_PLAIN;
+  d.src_bytes = (size_t)comps * T * cin * 4;
+  d.wgt = u;
+  d.wgt_bytes = (size_t)comps * cout * cin * (x3 ? 6 : 4);
+  d.x3 = x3 ? 1 : 0;
+  d.batch = comps;
+  d.N = 1;
+  d.Hin = d.Ho = 1;
+  d.Win = d.Wo = (int)T;
+  d.Cin = cin;
+  d.Cout = cout;
+  d.ks = 1;
+  d.stride = 1;
+  d.pad = 0;
+  d.store_mode = STORE_NHWC;
+  d.out = m;
+  d.name = name;
+  launch_conv_igemm(d, s);
+  return d;
+}
+
 void Detector::add_winograd_weights(ConvW& cw) {
   cw.wino_tile = cw.cin >= winograd43_min_cin_ ? 4 : 2;
   const std::vector<float> u = winograd_weights(cw.host.data(), cw.cout, cw.cin, cw.wino_tile);
@@ -1112,31 +1139,9 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
   auto wino_gemm = [&](const char* name, const ConvW& cw, int hh, int ww) {
     size_t wm, wa, T;
     wino_dims(cw, hh, ww, wm, wa, T);
-    ConvDesc d{};
-    d.src[0] = wino_v_;
-    d.src_mode = SRC_PLAIN;
-    d.src_bytes = wa * T * cw.cin * 4;
-    d.wgt = cw.wino;
-    d.wgt_bytes = cw.wino_bytes;
-    if (split_bf16_ && cw.wino_x3) {
-      d.x3 = 1;
-      d.wgt = cw.wino_x3;
-      d.wgt_bytes = cw.wino_bytes / 4 * 6;
-    }
-    d.batch = (int)wa;
-    d.N = 1;
-    d.Hin = d.Ho = 1;
-    d.Win = d.Wo = (int)T;
-    d.Cin = cw.cin;
-    d.Cout = cw.cout;
-    d.ks = 1;
-    d.stride = 1;
-    d.pad = 0;
-    d.store_mode = STORE_NHWC;
-    d.out = wino_m_;
-    d.name = name;
+    const bool x3 = split_bf16_ && cw.wino_x3;
     rec.begin();
-    launch_conv_igemm(d, stream_);
+    const ConvDesc d = launch_winograd_gemm(wino_v_, x3 ? cw.wino_x3 : cw.wino, x3, (int)wa, T, cw.cin, cw.cout, wino_m_, name, stream_);
     rec.end(conv_igemm_kernel_name(d), 2.0 * wa * T * cw.cin * cw.cout,
             (double)wa * 4.0 * ((double)T * cw.cin + (double)T * cw.cout + (double)cw.cin * cw.cout));
   };

@@ -32,6 +32,8 @@ class DeviceArena {  // bump allocator over one hipMalloc (weights)
 
 // U = G g G^T of a 3x3 conv given as [Cout][3x3][Cin], laid out [(m+2)^2][Cout][Cin] for F(m x m, 3x3), m = 2 or 4 (winograd.hip)
 std::vector<float> winograd_weights(const float* ohwi, int cout, int cin, int m = 2);
+// the batched GEMM between launch_winograd_input and launch_winograd_output (engine.hip): what Detector::forward launches for layer3 / layer4 / out4 / out5
+ConvDesc launch_winograd_gemm(const float* v, const void* u, bool x3, int comps, size_t T, int cin, int cout, float* m, const char* name, hipStream_t s);
 // The weight builders of the composed FPN and of bin_conv1 over the pyramid (engine.hip; layouts in the comments there):
 // out (3x3, mid -> cout, OHWI) after in (1x1, cin -> mid, [mid][cin]) as f64 taps [cout][9][cin]
 std::vector<double> compose_taps(const float* out_ohwi, int cout, int mid, const float* in_oi, int cin);

@@ -1213,3 +1213,74 @@ int ocr_test_pyr4_conv_run(ocr_det_t* det, int form, int out_bf16, const float* 
 }
 
 }  // extern "C"
+
+// ---- the Winograd F(4x4,3x3) convs of the trunk: the fused kernel (winograd43_fused.hip), the three-launch form (winograd.hip around
+// launch_winograd_gemm) and their host-side weight transforms ----
+extern "C" {
+
+// host only: engine.hip's winograd_weights.  ohwi [cout][9][cin] -> u_out [(m+2)^2][cout][cin] f32, m = 2 or 4
+int ocr_test_winograd_weights(const float* ohwi, int cout, int cin, int m, float* u_out) {
+  return guard([&] {
+    if (!ohwi || !u_out || cout <= 0 || cin <= 0) ocr::fail(OCR_ERR_INVALID, "winograd_weights hook: bad argument");
+    const std::vector<float> u = ocr::winograd_weights(ohwi, cout, cin, m);
+    std::copy(u.begin(), u.end(), u_out);
+  });
+}
+// host only: winograd43_fused.hip's winograd43_fragments.  u [36][cout][cin] -> f_out, the same count, in the MFMA B-fragment order
+int ocr_test_winograd43_fragments(const float* u, int cout, int cin, float* f_out) {
+  return guard([&] {
+    if (!u || !f_out || cout <= 0 || cin <= 0) ocr::fail(OCR_ERR_INVALID, "winograd43_fragments hook: bad argument");
+    const std::vector<float> f = ocr::winograd43_fragments(std::vector<float>(u, u + (size_t)36 * cout * cin), cout, cin);
+    std::copy(f.begin(), f.end(), f_out);
+  });
+}
+
+// one 3x3 s1 p1 conv (+ scale / bias / residual / ReLU) through a Winograd form on caller data.  form: 0 = launch_winograd43_fused (one
+// launch; num_cus sizes its persistent grid, 0 = 256); 1 = launch_winograd_input, launch_winograd_gemm over split3_weights_tiled(u) (the 36
+// split-bf16 GEMMs, as Detector::forward runs layer3 / layer4 / out4 / out5), launch_winograd_output; 2 = the same three launches with the
+// exact-f32 GEMM; 3 = the three launches of F(2x2,3x3), exact f32.  x: [n][h][w][cin]; wgt: [cout][9][cin]; scale / bias [cout] or null.
+// out_io: [n h w + guard_rows][cout], uploaded before the launch and downloaded whole after it: what the caller put into the guard rows comes
+// back only if no launch wrote there.  inplace != 0: the residual IS the output buffer (residual == y, as fpn.lateral runs), i.e. what
+// out_io holds on the way in; otherwise `residual` is a separate buffer, or null.  The source sits inside one allocation with `lead` >=
+// (w + 1) cin floats in front of it and as many behind it - zeros, or with poison != 0 quiet NaN: winograd43_input_kernel's descriptor
+// starts (w + 1) cin floats before the tensor, so the front region is what a failed mask of it would read
+int ocr_test_winograd_run(ocr_det_t* det, int form, const float* x, int n, int h, int w, int cin, const float* wgt, int cout, const float* scale,
+                          const float* bias, const float* residual, int relu, int inplace, int num_cus, int poison, float* out_io, int guard_rows) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !x || !wgt || !out_io) fail(OCR_ERR_INVALID, "null argument");
+    if (form < 0 || form > 3 || n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || guard_rows < 0 || num_cus < 0 || (inplace && residual))
+      fail(OCR_ERR_INVALID, "winograd hook: bad form, shape or residual");
+    if (form == 1 && (cin % 32 || cout % 16)) fail(OCR_ERR_INVALID, "winograd hook: the split-bf16 GEMMs need Cin a multiple of 32 and Cout of 16");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    HookBuffers b;
+    const int wm = form == 3 ? 2 : 4, comps = (wm + 2) * (wm + 2);
+    const size_t T = (size_t)n * ((h + wm - 1) / wm) * ((w + wm - 1) / wm);
+    const size_t px = (size_t)n * h * w, in_e = px * cin, out_e = (px + guard_rows) * cout;
+    const size_t lead = (((size_t)(w + 1) * cin + 1023) / 1024) * 1024;
+    std::vector<float> img(lead + in_e + lead, poison ? std::numeric_limits<float>::quiet_NaN() : 0.f);
+    std::copy(x, x + in_e, img.begin() + lead);
+    const float* d_x = b.f32(img.data(), img.size()) + lead;
+    const float* d_sc = scale ? b.f32(scale, cout) : nullptr;
+    const float* d_bi = bias ? b.f32(bias, cout) : nullptr;
+    float* d_y = b.f32(out_io, out_e);
+    const float* d_res = inplace ? d_y : residual ? b.f32(residual, px * cout) : nullptr;
+    const std::vector<float> u = winograd_weights(wgt, cout, cin, wm);
+    if (form == 0) {
+      const std::vector<float> uf = winograd43_fragments(u, cout, cin);
+      launch_winograd43_fused(d_x, b.f32(uf.data(), uf.size()), d_sc, d_bi, d_res, relu ? 1 : 0, d_y, n, h, w, cin, cout, num_cus > 0 ? num_cus : 256, s);
+    } else {
+      float* d_v = b.f32(nullptr, (size_t)comps * T * cin);
+      float* d_m = b.f32(nullptr, (size_t)comps * T * cout);
+      const void* d_u = form == 1 ? b.u16(split3_weights_tiled(u.data(), u.size(), cin)) : static_cast<const void*>(b.f32(u.data(), u.size()));
+      launch_winograd_input(d_x, d_v, n, h, w, cin, wm, s);
+      launch_winograd_gemm(d_v, d_u, form == 1, comps, T, cin, cout, d_m, "test_winograd_gemm", s);
+      launch_winograd_output(d_m, d_sc, d_bi, d_res, relu ? 1 : 0, d_y, n, h, w, cout, wm, s);
+    }
+    OCR_HIP(hipStreamSynchronize(s));
+    OCR_HIP(hipMemcpy(out_io, d_y, out_e * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+}  // extern "C"
