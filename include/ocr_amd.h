@@ -406,9 +406,10 @@ void ocr_glyphs_free(ocr_glyphs_t* g);
  * 12. min_col_ink is checked and unused, except by the fallback of step 5.
  * The result is an ordinary glyph block, released with ocr_glyphs_free and taken by ocr_extract_glyph_crops unchanged, except that
  * word_info[4k+3] is a bit set for this call: 1 = truncated, 2 = fell back to the column rule.
- * Still out of scope: letters that actually touch (one component, one glyph); crops are not masked by component, so a kerned
- * neighbour's ink inside a glyph's box shows in its crop; one threshold per word (a word that is one blob under its Otsu threshold
- * stays one glyph).  Oracle: tests/glyph_cc_oracle.py; kernel: csrc/glyph_cc.hip.
+ * Still out of scope: letters that actually touch (one component, one glyph); one threshold per word (a word that is one blob under
+ * its Otsu threshold stays one glyph).  ocr_extract_glyph_crops cuts a crop from its box alone, so a kerned neighbour's ink inside a
+ * glyph's box shows in its crop: ocr_segment_glyphs_cc_labelled and ocr_extract_glyph_crops_masked, below, keep it out.
+ * Oracle: tests/glyph_cc_oracle.py; kernel: csrc/glyph_cc.hip.
  * Memory kinds, blocking behaviour and the stream rule are ocr_segment_glyphs's.  OCR_ERR_INVALID in the same cases, and for a field
  * of `cc` out of range or a nonzero reserved field; the handle stays usable. */
 typedef struct ocr_cc_params {
@@ -420,6 +421,59 @@ void ocr_cc_default_params(ocr_cc_params_t* p);
 /* params == NULL, cc == NULL -> defaults.  *out must be released with ocr_glyphs_free. */
 int ocr_segment_glyphs_cc(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
                           const double* adj_xy, const ocr_segment_params_t* params, const ocr_cc_params_t* cc, ocr_glyphs_t** out);
+
+/* Glyph crops masked by connected component (BUILD-DEFINED, like ocr_segment_glyphs_cc): the segmentation also keeps, per word, which
+ * glyph every ink pixel went to, and the crop call reads a kerned neighbour's ink as background.
+ * Label planes.  Word k with the box [X0, X1) x [Y0, Y1), bw = X1 - X0, bh = Y1 - Y0, owns a plane of bh x bw uint16_t, row-major, at
+ * element offset plane_offsets[k]; plane_offsets[k + 1] - plane_offsets[k] = bw * bh.  After steps 1-11 of ocr_segment_glyphs_cc the
+ * plane holds
+ *   0       where the pixel is not ink, and everywhere when the word is flat (t = -1) or fell back to the column rule (flag 2):
+ *           such a word is not masked;
+ *   g + 1   (1 .. max_glyphs) for an ink pixel of a component in the group that became glyph g of the word (its box is
+ *           word_offsets[k] + g);
+ *   0xFFFF  for every other ink pixel: a component dropped at step 6, a component of a group dropped at step 9, a component of a
+ *           group past the first max_glyphs (step 10), those the truncated walk never reaches included.
+ * Masked tap.  The masked crop call is ocr_extract_glyph_crops with the tap changed and nothing else: sample positions, the operation
+ * order of the bilinear blend and ink_high are that call's.  For glyph g of word k let m = g + 1 and L(x, y) the plane value inside
+ * the word box, 0 outside it.  A tap at pixel (x, y) reads
+ *   1. outside the glyph box: 0;
+ *   2. l = L(x, y); l != 0 && l != m: 0;
+ *   3. l == 0 && halo == 1: over the eight neighbours (x + dx, y + dy), foreign = some neighbour has L not in {0, m}, own = some
+ *      neighbour has L == m; foreign && !own: 0 (the anti-aliased rim of a neighbour's stroke goes with the stroke);
+ *   4. otherwise the unmasked value g = r > 0 ? min(r, 1) : 0, r = (v - bg) / (ink - bg).
+ * Steps 2 and 3 are integer tests: an all-zero plane gives the bits of ocr_extract_glyph_crops, and so does every glyph whose box
+ * holds no foreign ink and has none within one pixel of it.  Oracle: tests/glyph_mask_oracle.py; kernels: csrc/glyph_cc.hip
+ * (segment_cc_labelled_kernel), csrc/glyphs.hip (glyph_crop_masked_kernel).
+ * The labelled segmentation returns, array for array, the glyph block of ocr_segment_glyphs_cc for the same arguments (the fallback
+ * of step 5 included), and the label block beside it.  The planes stay in device memory for either mem_kind - the crop call follows
+ * at once - in one allocation per call that the library owns until the label block is freed; a total of more than 2^31 - 1 plane elements is
+ * OCR_ERR_INVALID.  Blocking; memory kinds and the stream rule are ocr_segment_glyphs_cc's.  The read call copies all planes to host
+ * memory (plane_offsets[n_words] uint16_t), blocking, for inspection and tests.
+ * The masked crop call has the memory kinds, blocking behaviour and checks of ocr_extract_glyph_crops, and is OCR_ERR_INVALID also for
+ * null labels, labels->n_words != glyphs->n_words, labels->device other than the handle's device, a label block whose offsets do not
+ * fit its word boxes, a glyph box not inside its word's word_boxes entry, a word of more than 65534 glyphs, halo outside 0..1 or a
+ * nonzero reserved field; mask == NULL -> defaults.  The handle stays usable after any error. */
+typedef struct ocr_glyph_labels {
+  int32_t n_words;
+  int32_t device;                /* the GPU the planes live on */
+  const int32_t* word_boxes;     /* [4*n_words] X0, Y0, X1, Y1 frame pixels, half-open (host) */
+  const int64_t* plane_offsets;  /* [n_words+1], in elements (host) */
+  const uint16_t* planes;        /* DEVICE memory, plane_offsets[n_words] elements; NULL when that is 0 */
+} ocr_glyph_labels_t;
+typedef struct ocr_mask_params {
+  int32_t halo;         /* 0 | 1, default 1 */
+  int32_t reserved[3];  /* must be 0 */
+} ocr_mask_params_t;
+void ocr_mask_default_params(ocr_mask_params_t* p);
+/* params == NULL, cc == NULL -> defaults.  *out is released with ocr_glyphs_free, *labels with ocr_glyph_labels_free. */
+int ocr_segment_glyphs_cc_labelled(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
+                                   const double* adj_xy, const ocr_segment_params_t* params, const ocr_cc_params_t* cc,
+                                   ocr_glyphs_t** out, ocr_glyph_labels_t** labels);
+int ocr_glyph_labels_read(ocr_det_t* det, const ocr_glyph_labels_t* labels, uint16_t* planes_host);
+int ocr_extract_glyph_crops_masked(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_glyphs_t* glyphs,
+                                   const ocr_glyph_labels_t* labels, const ocr_segment_params_t* params, const ocr_mask_params_t* mask,
+                                   float* crops);
+void ocr_glyph_labels_free(ocr_glyph_labels_t* l);
 
 /* Word strips: every detected word (a polygon, possibly rotated) warped into an upright strip of strip_height rows, all strips of a
  * batch side by side in one atlas (BUILD-DEFINED, like ocr_segment_glyphs).  Frame coordinates are continuous: frame pixel p spans

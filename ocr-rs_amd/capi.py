@@ -30,6 +30,8 @@ EXPORTS = [
     "ocr_preprocess_image", "ocr_preprocess_batch", "ocr_preprocess_batch_async", "ocr_postproc_default_params", "ocr_det_postprocess", "ocr_det_post_stats", "ocr_det_detect_pipelined", "ocr_polygons_free",
     "ocr_extract_crops", "ocr_segment_default_params", "ocr_segment_glyphs", "ocr_extract_glyph_crops", "ocr_glyphs_free",
     "ocr_cc_default_params", "ocr_segment_glyphs_cc",
+    "ocr_mask_default_params", "ocr_segment_glyphs_cc_labelled", "ocr_glyph_labels_read", "ocr_extract_glyph_crops_masked",
+    "ocr_glyph_labels_free",
     "ocr_strip_default_params", "ocr_plan_word_strips", "ocr_extract_word_strips", "ocr_word_strip_polygons", "ocr_word_strips_free",
     "ocr_evaluate_image", "ocr_combine_results",
     "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_set_stream", "ocr_rec_set_options", "ocr_rec_synchronize",
@@ -80,6 +82,16 @@ class Glyphs(C.Structure):
     _fields_ = [("n_images", C.c_int32), ("n_words", C.c_int32), ("n_glyphs", C.c_int32),
                 ("img_offsets", C.POINTER(C.c_int32)), ("word_offsets", C.POINTER(C.c_int32)), ("word_info", C.POINTER(C.c_int32)),
                 ("word_levels", C.POINTER(C.c_float)), ("boxes", C.POINTER(C.c_int32))]
+
+
+class GlyphLabelsBlock(C.Structure):
+    """ocr_glyph_labels_t: word_boxes and plane_offsets are host arrays, planes is device memory."""
+    _fields_ = [("n_words", C.c_int32), ("device", C.c_int32), ("word_boxes", C.POINTER(C.c_int32)),
+                ("plane_offsets", C.POINTER(C.c_int64)), ("planes", C.c_void_p)]
+
+
+class MaskParams(C.Structure):
+    _fields_ = [("halo", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class StripParams(C.Structure):
@@ -198,6 +210,16 @@ def lib() -> C.CDLL:
                                               C.POINTER(SegmentParams), C.c_void_p]
         L.ocr_glyphs_free.argtypes = [C.POINTER(Glyphs)]
         L.ocr_glyphs_free.restype = None
+        L.ocr_mask_default_params.argtypes = [C.POINTER(MaskParams)]
+        L.ocr_mask_default_params.restype = None
+        L.ocr_segment_glyphs_cc_labelled.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Polygons),
+                                                     C.POINTER(C.c_double), C.POINTER(SegmentParams), C.POINTER(CcParams),
+                                                     C.POINTER(C.POINTER(Glyphs)), C.POINTER(C.POINTER(GlyphLabelsBlock))]
+        L.ocr_glyph_labels_read.argtypes = [C.c_void_p, C.POINTER(GlyphLabelsBlock), C.c_void_p]
+        L.ocr_extract_glyph_crops_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Glyphs),
+                                                     C.POINTER(GlyphLabelsBlock), C.POINTER(SegmentParams), C.POINTER(MaskParams), C.c_void_p]
+        L.ocr_glyph_labels_free.argtypes = [C.POINTER(GlyphLabelsBlock)]
+        L.ocr_glyph_labels_free.restype = None
         L.ocr_strip_default_params.argtypes = [C.POINTER(StripParams)]
         L.ocr_strip_default_params.restype = None
         L.ocr_plan_word_strips.argtypes = [C.POINTER(Polygons), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(StripParams),
@@ -416,6 +438,77 @@ class GlyphSet:
             return a.ctypes.data_as(C.POINTER(t))
         return Glyphs(self.n_images, self.n_words, self.n_glyphs, p(self.img_offsets, C.c_int32), p(self.word_offsets, C.c_int32),
                       p(self.word_info, C.c_int32), p(self.word_levels, C.c_float), p(self.boxes, C.c_int32))
+
+
+def mask_params(**fields) -> MaskParams:
+    """ocr_mask_default_params with the given fields overridden (halo)."""
+    p = MaskParams()
+    lib().ocr_mask_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k != "halo":
+            raise TypeError(f"unknown mask parameter {k!r}")
+        setattr(p, k, int(v))
+    return p
+
+
+def _as_mask_params(mask) -> Optional[MaskParams]:
+    """None or True -> the defaults (a null pointer); MaskParams as it is; a dict of its fields -> mask_params(**mask)."""
+    if mask is None or mask is True:
+        return None
+    if isinstance(mask, MaskParams):
+        return mask
+    if not isinstance(mask, dict):
+        raise TypeError(f"mask: expected None, True, a MaskParams or a dict of its fields, got {mask!r} (the unmasked call is extract_glyph_crops)")
+    return mask_params(**mask)
+
+
+class GlyphLabels:
+    """Owner of an ocr_glyph_labels_t: the label planes of one ocr_segment_glyphs_cc_labelled call, resident on the detector's GPU
+    until free() (or the end of a `with` block).  word_boxes n_words x 4 (X0, Y0, X1, Y1) and plane_offsets [n_words+1] are numpy
+    copies; read() brings the planes to the host."""
+
+    def __init__(self, det: "Detector", block):
+        self._det, self._p = det, block
+        b = block.contents
+        nw = b.n_words
+        self.n_words, self.device = nw, b.device
+        self.word_boxes = (np.ctypeslib.as_array(b.word_boxes, shape=(4 * nw,)).copy() if nw else np.zeros(0, np.int32)).reshape(-1, 4)
+        self.plane_offsets = np.ctypeslib.as_array(b.plane_offsets, shape=(nw + 1,)).copy()
+
+    @property
+    def block(self):
+        """The ocr_glyph_labels_t* for the C calls."""
+        if self._p is None:
+            raise OcrError(1, "glyph labels already freed")
+        return self._p
+
+    def read(self) -> np.ndarray:
+        """All planes, plane_offsets[n_words] uint16: word k is read()[plane_offsets[k]:plane_offsets[k + 1]].reshape(bh, bw)."""
+        planes = np.zeros(int(self.plane_offsets[-1]), np.uint16)
+        check(lib().ocr_glyph_labels_read(self._det._h, self.block, _ptr(planes)))
+        return planes
+
+    def plane(self, planes: np.ndarray, k: int) -> np.ndarray:
+        """Word k's bh x bw view of what read() returned."""
+        x0, y0, x1, y1 = (int(v) for v in self.word_boxes[k])
+        return planes[int(self.plane_offsets[k]):int(self.plane_offsets[k + 1])].reshape(y1 - y0, x1 - x0)
+
+    def free(self) -> None:
+        if self._p is not None:
+            lib().ocr_glyph_labels_free(self._p)
+            self._p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def strip_params(**fields) -> StripParams:
@@ -715,6 +808,53 @@ class Detector:
     def segment_glyphs_device(self, frames_ptr: int, n: int, h: int, w: int, polys, adjust_values, params=None, cc=None) -> GlyphSet:
         """The same on device-resident frames (a device pointer to N x 1 x H x W f32)."""
         return self._segment(C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, polys, adjust_values, params, cc)
+
+    def _segment_labelled(self, frames_ptr, n: int, h: int, w: int, mem_kind: int, polys, adjust_values, params, cc):
+        st, keep = python_to_polygons(polys, [[0.0] * len(p) for p in polys]) if not isinstance(polys, Polygons) else (polys, None)
+        adj = np.ascontiguousarray(adjust_values, dtype=np.float64).reshape(-1, 2)
+        prm, ccp = _as_segment_params(params), _as_cc_params(cc)
+        out, lab = C.POINTER(Glyphs)(), C.POINTER(GlyphLabelsBlock)()
+        check(lib().ocr_segment_glyphs_cc_labelled(self._h, frames_ptr, n, h, w, mem_kind, C.byref(st), adj.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   C.byref(prm) if prm is not None else None, C.byref(ccp) if ccp is not None else None,
+                                                   C.byref(out), C.byref(lab)))
+        try:
+            return GlyphSet.from_block(out), GlyphLabels(self, lab)
+        finally:
+            lib().ocr_glyphs_free(out)
+
+    def segment_glyphs_cc_labelled(self, frames: np.ndarray, polys, adjust_values, params=None, cc=None):
+        """segment_glyphs(cc=...) on host frames that also keeps which glyph every ink pixel went to (ocr_segment_glyphs_cc_labelled):
+        (GlyphSet, GlyphLabels).  cc: CcParams, a dict of its fields, or None for the defaults.  The labels live on the GPU until freed
+        and are what extract_glyph_crops_masked needs."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        n, _, h, w = frames.shape
+        return self._segment_labelled(_ptr(frames), n, h, w, MEM_HOST, polys, adjust_values, params, cc)
+
+    def segment_glyphs_cc_labelled_device(self, frames_ptr: int, n: int, h: int, w: int, polys, adjust_values, params=None, cc=None):
+        """The same on device-resident frames (a device pointer to N x 1 x H x W f32)."""
+        return self._segment_labelled(C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, polys, adjust_values, params, cc)
+
+    def extract_glyph_crops_masked(self, frames: np.ndarray, glyphs: GlyphSet, labels: GlyphLabels, params=None, mask=None) -> np.ndarray:
+        """extract_glyph_crops through the label planes (ocr_extract_glyph_crops_masked): a kerned neighbour's ink inside a glyph's box
+        reads as background.  mask: MaskParams, a dict of its fields ({"halo": 0}), or None / True for the defaults."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        n, _, h, w = frames.shape
+        crops = np.empty((glyphs.n_glyphs, 784), np.float32)
+        blk = glyphs.block()
+        prm, mp = _as_segment_params(params), _as_mask_params(mask)
+        check(lib().ocr_extract_glyph_crops_masked(self._h, _ptr(frames), n, h, w, MEM_HOST, C.byref(blk), labels.block,
+                                                   C.byref(prm) if prm is not None else None, C.byref(mp) if mp is not None else None,
+                                                   _ptr(crops)))
+        return crops
+
+    def extract_glyph_crops_masked_device(self, frames_ptr: int, n: int, h: int, w: int, glyphs: GlyphSet, labels: GlyphLabels,
+                                          crops_ptr: int, params=None, mask=None) -> None:
+        """The same on device memory: crops_ptr points at n_glyphs x 784 f32."""
+        blk = glyphs.block()
+        prm, mp = _as_segment_params(params), _as_mask_params(mask)
+        check(lib().ocr_extract_glyph_crops_masked(self._h, C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, C.byref(blk), labels.block,
+                                                   C.byref(prm) if prm is not None else None, C.byref(mp) if mp is not None else None,
+                                                   C.c_void_p(crops_ptr)))
 
     def extract_glyph_crops(self, frames: np.ndarray, glyphs: GlyphSet, params=None) -> np.ndarray:
         """The 28 x 28 crop of every glyph (host frames) -> n_glyphs x 784 f32."""

@@ -465,12 +465,32 @@ void ocr_segment_default_params(ocr_segment_params_t* p) {
   p->ink_high = 1;
 }
 
-// both segmentation entry points: cc == nullptr is the column rule (ocr_segment_glyphs), else the connected-component rule
+struct LabelsOwned {   // the library-owned storage behind an ocr_glyph_labels_t* (released by ocr_glyph_labels_free)
+  ocr_glyph_labels_t view{};
+  std::vector<int32_t> word_boxes;
+  std::vector<int64_t> plane_offsets;
+  uint16_t* d_planes = nullptr;
+  ~LabelsOwned() {
+    if (d_planes) (void)hipFree(d_planes);
+  }
+  void finish(int device) {
+    view.n_words = (int32_t)plane_offsets.size() - 1;
+    view.device = device;
+    view.word_boxes = word_boxes.data();
+    view.plane_offsets = plane_offsets.data();
+    view.planes = d_planes;
+  }
+};
+
+// the three segmentation entry points: cc == nullptr is the column rule (ocr_segment_glyphs), else the connected-component rule;
+// labels != nullptr (with cc) also keeps the label planes of the words on the device
 static int segment_glyphs(const char* who, ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
-                          const double* adj_xy, const ocr_segment_params_t* params, const ocr_cc_params_t* cc, ocr_glyphs_t** out) {
+                          const double* adj_xy, const ocr_segment_params_t* params, const ocr_cc_params_t* cc, ocr_glyphs_t** out,
+                          ocr_glyph_labels_t** labels = nullptr, bool want_labels = false) {
   return guard([&] {
     using namespace ocr;
-    if (!det || !frames || !polys || !adj_xy || !out) fail(OCR_ERR_INVALID, "%s: null argument", who);
+    if (labels) *labels = nullptr;
+    if (!det || !frames || !polys || !adj_xy || !out || (want_labels && !labels)) fail(OCR_ERR_INVALID, "%s: null argument", who);
     *out = nullptr;
     if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "%s: mem_kind %d", who, mem_kind);
     if (n < 0 || h < 1 || w < 1) fail(OCR_ERR_INVALID, "%s: N=%d H=%d W=%d", who, n, h, w);
@@ -493,14 +513,27 @@ static int segment_glyphs(const char* who, ocr_det_t* det, const float* frames, 
     g->img_offsets.assign(polys->img_offsets, polys->img_offsets + n + 1);
     g->word_offsets.push_back(0);
     const int nw = (int)words.size();
+    std::unique_ptr<LabelsOwned> lb;
+    if (want_labels) {
+      lb.reset(new LabelsOwned());
+      lb->plane_offsets.push_back(0);
+      for (const WordBox& wb : words) {
+        lb->word_boxes.insert(lb->word_boxes.end(), {wb.x0, wb.y0, wb.x1, wb.y1});
+        lb->plane_offsets.push_back(lb->plane_offsets.back() + (int64_t)(wb.x1 - wb.x0) * (wb.y1 - wb.y0));
+      }
+      if (lb->plane_offsets.back() > INT32_MAX)
+        fail(OCR_ERR_INVALID, "%s: %lld label plane elements (limit 2^31 - 1)", who, (long long)lb->plane_offsets.back());
+    }
     if (nw > 0) {
       const int R = glyph_record_ints(p.max_glyphs);
       std::vector<int32_t> rec((size_t)nw * R);
       OCR_HIP(hipSetDevice(det->impl.device()));
       hipStream_t s = det->impl.stream();
       const size_t wd_bytes = words.size() * sizeof(WordBox), rec_bytes = rec.size() * 4, fr_bytes = (size_t)n * h * w * 4;
+      const size_t po_bytes = lb ? lb->plane_offsets.size() * 8 : 0, pl_bytes = lb ? (size_t)lb->plane_offsets.back() * 2 : 0;
+      if (pl_bytes) OCR_HIP(hipMalloc(reinterpret_cast<void**>(&lb->d_planes), pl_bytes));
       Carve c;
-      const size_t o_wd = c.take(wd_bytes), o_rec = c.take(rec_bytes);
+      const size_t o_wd = c.take(wd_bytes), o_rec = c.take(rec_bytes), o_po = c.take(po_bytes);
       char* sc = static_cast<char*>(det->impl.scratch(1, c.end));
       const WordBox* d_words = at<const WordBox>(sc, o_wd);
       int32_t* d_rec = at<int32_t>(sc, o_rec);
@@ -512,7 +545,14 @@ static int segment_glyphs(const char* who, ocr_det_t* det, const float* frames, 
       }
       OCR_HIP(hipMemcpyAsync(sc + o_wd, words.data(), wd_bytes, hipMemcpyHostToDevice, s));
       const GlyphSegParams gp{p.polarity, p.min_col_ink, p.min_glyph_pixels, p.max_glyphs};
-      if (cc)
+      if (lb) {
+        // flat words and both fallback exits store nothing: the planes are zero before the kernel starts, on its stream
+        static_assert(sizeof(long long) == sizeof(int64_t), "plane offsets");
+        OCR_HIP(hipMemcpyAsync(sc + o_po, lb->plane_offsets.data(), po_bytes, hipMemcpyHostToDevice, s));
+        if (pl_bytes) OCR_HIP(hipMemsetAsync(lb->d_planes, 0, pl_bytes, s));
+        launch_segment_cc_labelled(d_fr, h, w, d_words, nw, gp, GlyphCcParams{cc->merge_overlap_pct, cc->min_height_pct}, d_rec, lb->d_planes,
+                                   at<const long long>(sc, o_po), s);
+      } else if (cc)
         launch_segment_cc(d_fr, h, w, d_words, nw, gp, GlyphCcParams{cc->merge_overlap_pct, cc->min_height_pct}, d_rec, s);
       else
         launch_segment(d_fr, h, w, d_words, nw, gp, d_rec, s);
@@ -551,6 +591,10 @@ static int segment_glyphs(const char* who, ocr_det_t* det, const float* frames, 
       }
     }
     g->finish();
+    if (lb) {
+      lb->finish(det->impl.device());
+      *labels = &lb.release()->view;
+    }
     *out = &g.release()->view;
   });
 }
@@ -575,44 +619,133 @@ int ocr_segment_glyphs_cc(ocr_det_t* det, const float* frames, int n, int h, int
   return segment_glyphs("segment_glyphs_cc", det, frames, n, h, w, mem_kind, polys, adj_xy, params, &c, out);
 }
 
-int ocr_extract_glyph_crops(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_glyphs_t* glyphs,
-                            const ocr_segment_params_t* params, float* crops) {
+int ocr_segment_glyphs_cc_labelled(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_polygons_t* polys,
+                                   const double* adj_xy, const ocr_segment_params_t* params, const ocr_cc_params_t* cc, ocr_glyphs_t** out,
+                                   ocr_glyph_labels_t** labels) {
+  ocr_cc_params_t c;
+  ocr_cc_default_params(&c);
+  if (cc) c = *cc;
+  return segment_glyphs("segment_glyphs_cc_labelled", det, frames, n, h, w, mem_kind, polys, adj_xy, params, &c, out, labels, true);
+}
+
+void ocr_mask_default_params(ocr_mask_params_t* p) {
+  if (!p) return;
+  p->halo = 1;
+  p->reserved[0] = p->reserved[1] = p->reserved[2] = 0;
+}
+
+int ocr_glyph_labels_read(ocr_det_t* det, const ocr_glyph_labels_t* labels, uint16_t* planes_host) {
   return guard([&] {
     using namespace ocr;
-    if (!det || !frames || !glyphs || (!crops && glyphs->n_glyphs > 0)) fail(OCR_ERR_INVALID, "extract_glyph_crops: null argument");
-    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "extract_glyph_crops: mem_kind %d", mem_kind);
-    if (n < 0 || h < 1 || w < 1) fail(OCR_ERR_INVALID, "extract_glyph_crops: N=%d H=%d W=%d", n, h, w);
-    if (glyphs->n_images != n) fail(OCR_ERR_INVALID, "extract_glyph_crops: glyph block holds %d images, frames %d", glyphs->n_images, n);
-    const ocr_segment_params_t p = segment_params(params, "extract_glyph_crops");
+    if (!det || !labels) fail(OCR_ERR_INVALID, "glyph_labels_read: null argument");
+    if (labels->n_words < 0 || !labels->plane_offsets) fail(OCR_ERR_INVALID, "glyph_labels_read: %d words, or no plane offsets", labels->n_words);
+    if (labels->device != det->impl.device())
+      fail(OCR_ERR_INVALID, "glyph_labels_read: planes on device %d, handle on device %d", labels->device, det->impl.device());
+    const int64_t total = labels->plane_offsets[labels->n_words];
+    if (total < 0 || total > INT32_MAX) fail(OCR_ERR_INVALID, "glyph_labels_read: %lld plane elements", (long long)total);
+    if (total == 0) return;
+    if (!labels->planes || !planes_host) fail(OCR_ERR_INVALID, "glyph_labels_read: null planes");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    OCR_HIP(hipMemcpyAsync(planes_host, labels->planes, (size_t)total * 2, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipStreamSynchronize(s));
+  });
+}
+
+void ocr_glyph_labels_free(ocr_glyph_labels_t* l) {
+  if (!l) return;
+  delete reinterpret_cast<LabelsOwned*>(reinterpret_cast<char*>(l) - offsetof(LabelsOwned, view));
+}
+
+// both crop entry points: labels == nullptr cuts the crops from the boxes alone (ocr_extract_glyph_crops), else through the label planes
+static int extract_glyph_crops(const char* who, ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_glyphs_t* glyphs,
+                               const ocr_glyph_labels_t* labels, bool masked, const ocr_segment_params_t* params,
+                               const ocr_mask_params_t* mask, float* crops) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !frames || !glyphs || (masked && !labels) || (!crops && glyphs->n_glyphs > 0)) fail(OCR_ERR_INVALID, "%s: null argument", who);
+    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "%s: mem_kind %d", who, mem_kind);
+    if (n < 0 || h < 1 || w < 1) fail(OCR_ERR_INVALID, "%s: N=%d H=%d W=%d", who, n, h, w);
+    if (glyphs->n_images != n) fail(OCR_ERR_INVALID, "%s: glyph block holds %d images, frames %d", who, glyphs->n_images, n);
+    const ocr_segment_params_t p = segment_params(params, who);
     const int nw = glyphs->n_words, ng = glyphs->n_glyphs;
-    if (nw < 0 || ng < 0) fail(OCR_ERR_INVALID, "extract_glyph_crops: %d words, %d glyphs", nw, ng);
+    if (nw < 0 || ng < 0) fail(OCR_ERR_INVALID, "%s: %d words, %d glyphs", who, nw, ng);
+    ocr_mask_params_t mp;
+    ocr_mask_default_params(&mp);
+    if (masked) {
+      if (mask) mp = *mask;
+      if (mp.halo < 0 || mp.halo > 1 || mp.reserved[0] != 0 || mp.reserved[1] != 0 || mp.reserved[2] != 0)
+        fail(OCR_ERR_INVALID, "%s: mask halo=%d reserved=%d, %d, %d (limits: halo 0..1, reserved 0)", who, mp.halo, mp.reserved[0],
+             mp.reserved[1], mp.reserved[2]);
+      if (labels->n_words != nw) fail(OCR_ERR_INVALID, "%s: label block holds %d words, glyph block %d", who, labels->n_words, nw);
+      if (labels->device != det->impl.device())
+        fail(OCR_ERR_INVALID, "%s: label planes on device %d, handle on device %d", who, labels->device, det->impl.device());
+    }
     if (ng == 0) return;
     if (!glyphs->word_offsets || !glyphs->word_info || !glyphs->word_levels || !glyphs->boxes)
-      fail(OCR_ERR_INVALID, "extract_glyph_crops: null array in the glyph block");
-    if (glyphs->word_offsets[0] != 0 || glyphs->word_offsets[nw] != ng) fail(OCR_ERR_INVALID, "extract_glyph_crops: word offsets do not span the glyphs");
+      fail(OCR_ERR_INVALID, "%s: null array in the glyph block", who);
+    if (glyphs->word_offsets[0] != 0 || glyphs->word_offsets[nw] != ng) fail(OCR_ERR_INVALID, "%s: word offsets do not span the glyphs", who);
+    if (masked) {   // the kernel reads a plane inside its word box only: the offsets must be the boxes' sizes, end to end
+      if (!labels->word_boxes || !labels->plane_offsets || labels->plane_offsets[0] != 0) fail(OCR_ERR_INVALID, "%s: null array in the label block", who);
+      for (int i = 0; i < nw; ++i) {
+        const int32_t* wbx = labels->word_boxes + 4 * (size_t)i;
+        const int64_t bw = (int64_t)wbx[2] - wbx[0], bh = (int64_t)wbx[3] - wbx[1];
+        if (bw < 0 || bh < 0 || bw * bh > (int64_t(1) << 22) || labels->plane_offsets[i + 1] - labels->plane_offsets[i] != bw * bh)
+          fail(OCR_ERR_INVALID, "%s: word %d box (%d, %d, %d, %d) does not fit its plane of %lld elements", who, i, wbx[0], wbx[1], wbx[2], wbx[3],
+               (long long)(labels->plane_offsets[i + 1] - labels->plane_offsets[i]));
+      }
+      if (labels->plane_offsets[nw] > INT32_MAX) fail(OCR_ERR_INVALID, "%s: %lld label plane elements", who, (long long)labels->plane_offsets[nw]);
+      if (labels->plane_offsets[nw] > 0 && !labels->planes) fail(OCR_ERR_INVALID, "%s: null planes", who);
+    }
     std::vector<GlyphJob> jobs;
-    jobs.reserve(ng);
+    std::vector<GlyphMaskJob> mjobs;
+    if (masked) mjobs.reserve(ng); else jobs.reserve(ng);
     for (int i = 0; i < nw; ++i) {   // every box is checked against the frames: the kernel reads inside them only
       const int fr = glyphs->word_info[4 * i];
       const int k0 = glyphs->word_offsets[i], k1 = glyphs->word_offsets[i + 1];
-      if (k1 < k0 || k1 > ng) fail(OCR_ERR_INVALID, "extract_glyph_crops: word %d glyph range [%d, %d)", i, k0, k1);
-      if (k1 > k0 && (fr < 0 || fr >= n)) fail(OCR_ERR_INVALID, "extract_glyph_crops: word %d on frame %d of %d", i, fr, n);
+      if (k1 < k0 || k1 > ng) fail(OCR_ERR_INVALID, "%s: word %d glyph range [%d, %d)", who, i, k0, k1);
+      if (k1 > k0 && (fr < 0 || fr >= n)) fail(OCR_ERR_INVALID, "%s: word %d on frame %d of %d", who, i, fr, n);
+      if (masked && k1 - k0 > 65534) fail(OCR_ERR_INVALID, "%s: word %d holds %d glyphs (limit 65534: labels are 16 bits)", who, i, k1 - k0);
       for (int k = k0; k < k1; ++k) {
         const int32_t* b = glyphs->boxes + 4 * (size_t)k;
         if (b[0] < 0 || b[1] < 0 || b[2] > w || b[3] > h || b[0] >= b[2] || b[1] >= b[3])
-          fail(OCR_ERR_INVALID, "extract_glyph_crops: glyph %d box (%d, %d, %d, %d) outside the %d x %d frame", k, b[0], b[1], b[2], b[3], w, h);
-        jobs.push_back({fr, b[0], b[1], b[2], b[3], glyphs->word_levels[2 * i], glyphs->word_levels[2 * i + 1]});
+          fail(OCR_ERR_INVALID, "%s: glyph %d box (%d, %d, %d, %d) outside the %d x %d frame", who, k, b[0], b[1], b[2], b[3], w, h);
+        const GlyphJob job{fr, b[0], b[1], b[2], b[3], glyphs->word_levels[2 * i], glyphs->word_levels[2 * i + 1]};
+        if (!masked) {
+          jobs.push_back(job);
+          continue;
+        }
+        const int32_t* wbx = labels->word_boxes + 4 * (size_t)i;
+        if (b[0] < wbx[0] || b[1] < wbx[1] || b[2] > wbx[2] || b[3] > wbx[3])
+          fail(OCR_ERR_INVALID, "%s: glyph %d box (%d, %d, %d, %d) not inside its word's box (%d, %d, %d, %d)", who, k, b[0], b[1], b[2], b[3],
+               wbx[0], wbx[1], wbx[2], wbx[3]);
+        mjobs.push_back({job, wbx[0], wbx[1], wbx[2], wbx[3], k - k0 + 1, labels->planes + labels->plane_offsets[i]});
       }
     }
     OCR_HIP(hipSetDevice(det->impl.device()));
     hipStream_t s = det->impl.stream();
-    const size_t jb_bytes = jobs.size() * sizeof(GlyphJob), fr_bytes = (size_t)n * h * w * 4, cr_bytes = (size_t)ng * 784 * 4;
-    GlyphJob* d_jobs = static_cast<GlyphJob*>(det->impl.scratch(1, ocr::align256(jb_bytes)));
-    OCR_HIP(hipMemcpyAsync(d_jobs, jobs.data(), jb_bytes, hipMemcpyHostToDevice, s));
+    const size_t jb_bytes = masked ? mjobs.size() * sizeof(GlyphMaskJob) : jobs.size() * sizeof(GlyphJob);
+    const size_t fr_bytes = (size_t)n * h * w * 4, cr_bytes = (size_t)ng * 784 * 4;
+    void* d_jobs = det->impl.scratch(1, ocr::align256(jb_bytes));
+    OCR_HIP(hipMemcpyAsync(d_jobs, masked ? static_cast<const void*>(mjobs.data()) : jobs.data(), jb_bytes, hipMemcpyHostToDevice, s));
     const StagedFrames st(det->impl, frames, fr_bytes, crops, cr_bytes, mem_kind, s);
-    launch_glyph_crops(st.frames, h, w, d_jobs, ng, p.glyph_box, p.ink_high, st.out, s);
+    if (masked)
+      launch_glyph_crops_masked(st.frames, h, w, static_cast<const GlyphMaskJob*>(d_jobs), ng, p.glyph_box, p.ink_high, mp.halo, st.out, s);
+    else
+      launch_glyph_crops(st.frames, h, w, static_cast<const GlyphJob*>(d_jobs), ng, p.glyph_box, p.ink_high, st.out, s);
     st.home(crops, cr_bytes, s);
   });
+}
+
+int ocr_extract_glyph_crops(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_glyphs_t* glyphs,
+                            const ocr_segment_params_t* params, float* crops) {
+  return extract_glyph_crops("extract_glyph_crops", det, frames, n, h, w, mem_kind, glyphs, nullptr, false, params, nullptr, crops);
+}
+
+int ocr_extract_glyph_crops_masked(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_glyphs_t* glyphs,
+                                   const ocr_glyph_labels_t* labels, const ocr_segment_params_t* params, const ocr_mask_params_t* mask,
+                                   float* crops) {
+  return extract_glyph_crops("extract_glyph_crops_masked", det, frames, n, h, w, mem_kind, glyphs, labels, true, params, mask, crops);
 }
 
 void ocr_glyphs_free(ocr_glyphs_t* g) {

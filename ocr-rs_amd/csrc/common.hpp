@@ -232,6 +232,19 @@ void launch_segment_cc(const float* frames_dev, int H, int W, const WordBox* wor
                        const GlyphCcParams& cc, int32_t* records_dev, hipStream_t s);
 void launch_glyph_crops(const float* frames_dev, int H, int W, const GlyphJob* jobs_dev, int n_glyphs, int glyph_box, int ink_high,
                         float* crops_dev, hipStream_t s);
+// label planes and masked crops (include/ocr_amd.h ocr_segment_glyphs_cc_labelled, tests/glyph_mask_oracle.py): word k's plane is
+// bh x bw uint16 at planes_dev + plane_off_dev[k], zeroed by the caller in front of the launch on the same stream.  A masked job is
+// the glyph's job, its word's box and plane, and its label m = index in the word + 1; the glyph box lies inside the word box.
+struct GlyphMaskJob {
+  GlyphJob g;
+  int wx0, wy0, wx1, wy1, m;
+  const uint16_t* plane;
+};
+void launch_segment_cc_labelled(const float* frames_dev, int H, int W, const WordBox* words_dev, int n_words, const GlyphSegParams& p,
+                                const GlyphCcParams& cc, int32_t* records_dev, uint16_t* planes_dev, const long long* plane_off_dev,
+                                hipStream_t s);
+void launch_glyph_crops_masked(const float* frames_dev, int H, int W, const GlyphMaskJob* jobs_dev, int n_glyphs, int glyph_box, int ink_high,
+                               int halo, float* crops_dev, hipStream_t s);
 
 // word strips (strips.hip; rule: include/ocr_amd.h ocr_plan_word_strips, tests/strip_oracle.py).  One record per word: its f32 map,
 // frame and first atlas column; col_word[j] is the word that owns atlas column j.

@@ -16,8 +16,11 @@
 //      folds its extent and pixel count into its slot with LDS min / max / add: order-free, so scheduling cannot change a bit;
 //   5. components of at least min_glyph_pixels pixels are sorted by x0 * 1024 + slot (= by (x0, anchor)) with a bitonic sort in LDS,
 //      and lane 0 walks them: merge into the open group or close it (height filter, max_glyphs, truncation).
+//   6. segment_cc_labelled_kernel only (the same body, template flag LABELS): every component carries a label - 0xFFFF until the walk
+//      closes a kept group over it, then the glyph's index in the word + 1 - and every run paints it over its pixels in the word's
+//      uint16 plane, for ocr_extract_glyph_crops_masked.  The label lives in c_cnt, dead once the sort keys are built: no new LDS.
 // LDS: 3 x 32 KB runs, 5 x 4 KB components, 4 KB keys, 4 KB row counts, 4 KB histograms: 128 KB of the CU's 160, so one workgroup per
-// CU - the words of a batch are few next to CUs x rounds.  46 VGPRs, no scratch.
+// CU - the words of a batch are few next to CUs x rounds.  48 VGPRs, no scratch, both forms.
 #include <type_traits>
 
 #include "common.hpp"
@@ -61,8 +64,13 @@ __device__ __forceinline__ void unite(int* parent, int a, int b) {
   }
 }
 
-__global__ __launch_bounds__(kThreads) void segment_cc_kernel(const float* __restrict__ frames, int H, int W, const WordBox* __restrict__ words,
-                                                              GlyphSegParams prm, GlyphCcParams cc, int32_t* __restrict__ rec) {
+// The body of both kernels.  LABELS = false is segment_cc_kernel as it always was; LABELS = true (segment_cc_labelled_kernel) also
+// writes the word's label plane (include/ocr_amd.h, ocr_segment_glyphs_cc_labelled): planes + plane_off[word], bh x bw uint16,
+// zeroed by the host in front of the launch, so the flat and the two fallback exits - all taken before any label exists - store nothing.
+template <bool LABELS>
+__device__ __forceinline__ void segment_cc_body(const float* __restrict__ frames, int H, int W, const WordBox* __restrict__ words,
+                                                GlyphSegParams prm, GlyphCcParams cc, int32_t* __restrict__ rec,
+                                                uint16_t* __restrict__ planes, const long long* __restrict__ plane_off) {
   __shared__ unsigned hist[kWaves][256];
   __shared__ int r_start[kMaxRuns], r_x1[kMaxRuns], parent[kMaxRuns];
   __shared__ int rowcnt[kRowChunk];
@@ -234,6 +242,9 @@ __global__ __launch_bounds__(kThreads) void segment_cc_kernel(const float* __res
       atomicAdd(&s_nsort, 1);
     }
     keys[i] = key;
+    // the count has had its last reader (this thread, this entry): c_cnt becomes the component's label, "ink of no glyph" until the
+    // walk says otherwise - dropped here, by the height filter, behind max_glyphs or never reached by the truncated walk
+    if (LABELS && i < ncomp) c_cnt[i] = 0xFFFF;
   }
   __syncthreads();
   for (int k = 2; k <= npow; k <<= 1)
@@ -252,13 +263,16 @@ __global__ __launch_bounds__(kThreads) void segment_cc_kernel(const float* __res
     const int nsort = s_nsort, pct = cc.merge_overlap_pct, min_h = cc.min_height_pct * bh;
     int nkept = 0, trunc = 0;
     int gx0 = 0, gy0 = 0, gx1 = 0, gy1 = 0;
+    int gfirst = 0;   // LABELS: the open group is keys[gfirst, gend) - a group is a contiguous range of the sorted order
     bool open = false;
-    auto close_group = [&] {
+    auto close_group = [&](int gend) {
       if ((gy1 - gy0) * 100 < min_h) return;
       if (nkept < prm.max_glyphs) {
         int32_t* b = out + 8 + 4 * nkept;
         b[0] = wb.x0 + gx0; b[1] = wb.y0 + gy0; b[2] = wb.x0 + gx1; b[3] = wb.y0 + gy1;
         ++nkept;
+        if (LABELS)
+          for (int k = gfirst; k < gend; ++k) c_cnt[keys[k] & 1023u] = nkept;   // glyph g of the word is label g + 1
       } else {
         trunc = 1;
       }
@@ -272,15 +286,41 @@ __global__ __launch_bounds__(kThreads) void segment_cc_kernel(const float* __res
           gx0 = min(gx0, x0); gy0 = min(gy0, y0); gx1 = max(gx1, x1); gy1 = max(gy1, y1);
           continue;
         }
-        close_group();
+        close_group(n);
       }
       gx0 = x0; gy0 = y0; gx1 = x1; gy1 = y1;
+      gfirst = n;
       open = true;
     }
-    if (open && !trunc) close_group();
+    if (open && !trunc) close_group(nsort);
     out[3] = trunc;
     out[6] = nkept;
   }
+
+  // ---- 6. (LABELS) every run paints its component's label over its pixels: a wave per run, lanes over columns, so the 2-byte stores
+  // of one instruction are contiguous.  Runs partition the ink, so every ink pixel is written once and no other pixel at all
+  if constexpr (LABELS) {
+    __syncthreads();
+    uint16_t* plane = planes + plane_off[blockIdx.x];
+    for (int i = wv; i < nruns; i += kWaves) {
+      const int p = parent[i], slot = p < 0 ? ~p : ~parent[p];
+      const int st = r_start[i], a1 = r_x1[i], y = st / bw;
+      const uint16_t lab = (uint16_t)c_cnt[slot];
+      for (int k = st + lane, e = y * bw + a1; k < e; k += 64) plane[k] = lab;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void segment_cc_kernel(const float* __restrict__ frames, int H, int W, const WordBox* __restrict__ words,
+                                                              GlyphSegParams prm, GlyphCcParams cc, int32_t* __restrict__ rec) {
+  segment_cc_body<false>(frames, H, W, words, prm, cc, rec, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kThreads) void segment_cc_labelled_kernel(const float* __restrict__ frames, int H, int W,
+                                                                       const WordBox* __restrict__ words, GlyphSegParams prm, GlyphCcParams cc,
+                                                                       int32_t* __restrict__ rec, uint16_t* __restrict__ planes,
+                                                                       const long long* __restrict__ plane_off) {
+  segment_cc_body<true>(frames, H, W, words, prm, cc, rec, planes, plane_off);
 }
 
 }  // namespace
@@ -289,6 +329,15 @@ void launch_segment_cc(const float* frames_dev, int H, int W, const WordBox* wor
                        const GlyphCcParams& cc, int32_t* records_dev, hipStream_t s) {
   if (n_words <= 0) return;
   hipLaunchKernelGGL(segment_cc_kernel, dim3(n_words), dim3(kThreads), 0, s, frames_dev, H, W, words_dev, p, cc, records_dev);
+  OCR_HIP(hipGetLastError());
+}
+
+void launch_segment_cc_labelled(const float* frames_dev, int H, int W, const WordBox* words_dev, int n_words, const GlyphSegParams& p,
+                                const GlyphCcParams& cc, int32_t* records_dev, uint16_t* planes_dev, const long long* plane_off_dev,
+                                hipStream_t s) {
+  if (n_words <= 0) return;
+  hipLaunchKernelGGL(segment_cc_labelled_kernel, dim3(n_words), dim3(kThreads), 0, s, frames_dev, H, W, words_dev, p, cc, records_dev, planes_dev,
+                     plane_off_dev);
   OCR_HIP(hipGetLastError());
 }
 

@@ -16,7 +16,8 @@
 //   The box is read from the frame once per pass (histogram, profile): words are small next to the frame and stay in the caches, so
 //   no u8 copy of the box is staged in LDS.
 // glyph_crop_kernel, one 256-thread workgroup per glyph: 784 bilinear samples of the normalised word levels, written to the caller's
-// buffer.
+// buffer.  glyph_crop_masked_kernel (ocr_extract_glyph_crops_masked) is the same sampling with a tap that first asks the word's label
+// plane (glyph_cc.hip) whose ink the pixel is: a kerned neighbour's ink inside the glyph's box reads as background.
 // Out of scope of the rule: touching or kerned glyphs (they stay one glyph), rotated or curved words (the word box is axis-aligned and
 // pixels are not masked by the polygon), lexicons, spaces inside a polygon.
 #include "common.hpp"
@@ -159,13 +160,11 @@ __device__ __forceinline__ float level(const float* img, int W, int x, int y, co
   return r > 0.f ? (r < 1.f ? r : 1.f) : 0.f;   // NaN -> 0, -0 -> +0
 }
 
-__global__ __launch_bounds__(kThreads) void glyph_crop_kernel(const float* __restrict__ frames, int H, int W, const GlyphJob* __restrict__ jobs,
-                                                              int glyph_box, int ink_high, float* __restrict__ crops) {
-  const GlyphJob g = jobs[blockIdx.x];
-  const float* img = frames + (size_t)g.frame * H * W;
+// the 784 samples of one glyph, shared by both crop kernels: tap(x, y) is the level of frame pixel (x, y)
+template <class Tap>
+__device__ __forceinline__ void sample_crop(const GlyphJob& g, int glyph_box, int ink_high, float* __restrict__ crop, Tap tap) {
   const float s = (float)max(g.x1 - g.x0, g.y1 - g.y0) / (float)glyph_box;
   const float cx = (float)(g.x0 + g.x1) * 0.5f, cy = (float)(g.y0 + g.y1) * 0.5f;
-  const float den = g.ink - g.bg;
   for (int o = threadIdx.x; o < 784; o += kThreads) {
     const int i = o / 28, j = o - i * 28;
     const float sy = (cy + (((float)i + 0.5f) - 14.0f) * s) - 0.5f;
@@ -173,12 +172,57 @@ __global__ __launch_bounds__(kThreads) void glyph_crop_kernel(const float* __res
     const float fsy = floorf(sy), fsx = floorf(sx);
     const int iy0 = (int)fsy, ix0 = (int)fsx;
     const float fy = sy - (float)iy0, fx = sx - (float)ix0;
-    const float a = level(img, W, ix0, iy0, g, den), b = level(img, W, ix0 + 1, iy0, g, den);
-    const float c = level(img, W, ix0, iy0 + 1, g, den), d = level(img, W, ix0 + 1, iy0 + 1, g, den);
+    const float a = tap(ix0, iy0), b = tap(ix0 + 1, iy0);
+    const float c = tap(ix0, iy0 + 1), d = tap(ix0 + 1, iy0 + 1);
     const float top = a + fx * (b - a), bot = c + fx * (d - c);
     const float v = top + fy * (bot - top);
-    crops[(size_t)blockIdx.x * 784 + o] = ink_high ? v : 1.0f - v;
+    crop[o] = ink_high ? v : 1.0f - v;
   }
+}
+
+__global__ __launch_bounds__(kThreads) void glyph_crop_kernel(const float* __restrict__ frames, int H, int W, const GlyphJob* __restrict__ jobs,
+                                                              int glyph_box, int ink_high, float* __restrict__ crops) {
+  const GlyphJob g = jobs[blockIdx.x];
+  const float* img = frames + (size_t)g.frame * H * W;
+  const float den = g.ink - g.bg;
+  sample_crop(g, glyph_box, ink_high, crops + (size_t)blockIdx.x * 784, [&](int x, int y) { return level(img, W, x, y, g, den); });
+}
+
+// The masked tap (include/ocr_amd.h, ocr_extract_glyph_crops_masked): integer tests on the word's label plane in front of level(), so
+// whatever passes them is level()'s f32, bit for bit.  The glyph box lies inside the word box (the host checks it), so a pixel that
+// passed level()'s box test has a label; its neighbours may lie outside the word box and read as 0.
+__device__ __forceinline__ float masked_level(const float* img, int W, int x, int y, const GlyphMaskJob& j, float den, int halo) {
+  const GlyphJob& g = j.g;
+  if (x < g.x0 || x >= g.x1 || y < g.y0 || y >= g.y1) return 0.f;
+  const int bw = j.wx1 - j.wx0, m = j.m;
+  const uint16_t* row = j.plane + (size_t)(y - j.wy0) * bw + (x - j.wx0);   // the label of (x, y)
+  const int l = *row;
+  if (l != 0 && l != m) return 0.f;
+  if (l == 0 && halo) {
+    bool foreign = false, own = false;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx) {
+        if (dx == 0 && dy == 0) continue;
+        const int nx = x + dx, ny = y + dy;
+        if (nx < j.wx0 || nx >= j.wx1 || ny < j.wy0 || ny >= j.wy1) continue;
+        const int v = row[dy * bw + dx];
+        foreign |= v != 0 && v != m;
+        own |= v == m;
+      }
+    if (foreign && !own) return 0.f;
+  }
+  return level(img, W, x, y, g, den);
+}
+
+__global__ __launch_bounds__(kThreads) void glyph_crop_masked_kernel(const float* __restrict__ frames, int H, int W,
+                                                                     const GlyphMaskJob* __restrict__ jobs, int glyph_box, int ink_high, int halo,
+                                                                     float* __restrict__ crops) {
+  const GlyphMaskJob j = jobs[blockIdx.x];
+  const float* img = frames + (size_t)j.g.frame * H * W;
+  const float den = j.g.ink - j.g.bg;
+  sample_crop(j.g, glyph_box, ink_high, crops + (size_t)blockIdx.x * 784, [&](int x, int y) { return masked_level(img, W, x, y, j, den, halo); });
 }
 
 }  // namespace
@@ -194,6 +238,14 @@ void launch_glyph_crops(const float* frames_dev, int H, int W, const GlyphJob* j
                         float* crops_dev, hipStream_t s) {
   if (n_glyphs <= 0) return;
   hipLaunchKernelGGL(glyph_crop_kernel, dim3(n_glyphs), dim3(kThreads), 0, s, frames_dev, H, W, jobs_dev, glyph_box, ink_high, crops_dev);
+  OCR_HIP(hipGetLastError());
+}
+
+void launch_glyph_crops_masked(const float* frames_dev, int H, int W, const GlyphMaskJob* jobs_dev, int n_glyphs, int glyph_box, int ink_high,
+                               int halo, float* crops_dev, hipStream_t s) {
+  if (n_glyphs <= 0) return;
+  hipLaunchKernelGGL(glyph_crop_masked_kernel, dim3(n_glyphs), dim3(kThreads), 0, s, frames_dev, H, W, jobs_dev, glyph_box, ink_high, halo,
+                     crops_dev);
   OCR_HIP(hipGetLastError());
 }
 

@@ -154,15 +154,41 @@ struct WordReading {
   std::vector<double> probs;
   std::vector<std::array<int32_t, 4>> boxes;
 };
+// The two glyph calls of both readers over host memory: the column rule (cc == nullptr), connected components (cc), or connected
+// components with every crop masked by its glyph's components (cc and mask: ocr_segment_glyphs_cc_labelled ->
+// ocr_extract_glyph_crops_masked; the label planes live on the GPU between the two calls).  mask without cc is OCR_ERR_INVALID.
+// *g is the caller's to free; crops is resized to n_glyphs x 784.
+inline void segment_and_crop(const text_detection::FuncT& det_net, const float* frames, int n, int h, int w, const ocr_polygons_t* polys,
+                             const double* adjust_values, const ocr_segment_params_t* params, const ocr_cc_params_t* cc,
+                             const ocr_mask_params_t* mask, ocr_glyphs_t** g, std::vector<float>& crops) {
+  if (mask && !cc) throw Error(OCR_ERR_INVALID, "mask: masked crops need the connected-component rule (pass cc)");
+  ocr_glyph_labels_t* labels = nullptr;
+  struct FreeLabels {
+    ocr_glyph_labels_t*& l;
+    ~FreeLabels() { ocr_glyph_labels_free(l); }
+  } free_l{labels};
+  if (mask)
+    check(ocr_segment_glyphs_cc_labelled(det_net.handle(), frames, n, h, w, OCR_MEM_HOST, polys, adjust_values, params, cc, g, &labels));
+  else
+    check(cc ? ocr_segment_glyphs_cc(det_net.handle(), frames, n, h, w, OCR_MEM_HOST, polys, adjust_values, params, cc, g)
+             : ocr_segment_glyphs(det_net.handle(), frames, n, h, w, OCR_MEM_HOST, polys, adjust_values, params, g));
+  crops.resize((size_t)(*g)->n_glyphs * 784);
+  if ((*g)->n_glyphs == 0) return;
+  check(mask ? ocr_extract_glyph_crops_masked(det_net.handle(), frames, n, h, w, OCR_MEM_HOST, *g, labels, params, mask, crops.data())
+             : ocr_extract_glyph_crops(det_net.handle(), frames, n, h, w, OCR_MEM_HOST, *g, params, crops.data()));
+}
+
 // ocr_segment_glyphs -> ocr_extract_glyph_crops -> ocr_rec_classify over host memory: per image, per polygon of `ps`.  frames are the
 // detector's input (N x 1 x H x W, raw 0..255), adjust_values N x 2 as given to get_boxes_and_box_scores; params == nullptr: defaults.
 // cc == nullptr segments by the column rule; a pointer (see ocr_cc_default_params) segments by connected components
-// (ocr_segment_glyphs_cc), which splits kerned letters.
+// (ocr_segment_glyphs_cc), which splits kerned letters.  mask == nullptr cuts every crop from its box alone; a pointer (see
+// ocr_mask_default_params) needs cc and keeps a kerned neighbour's ink out of every crop (segment_and_crop).
 inline std::vector<std::vector<WordReading>> read_words(const text_detection::FuncT& det_net, const char_recognition::Net& rec_net,
                                                         const Tensor& frames, const text_detection::metrics::PolygonScores& ps,
                                                         const std::vector<double>& adjust_values,
                                                         const ocr_segment_params_t* params = nullptr,
-                                                        const ocr_cc_params_t* cc = nullptr) {
+                                                        const ocr_cc_params_t* cc = nullptr,
+                                                        const ocr_mask_params_t* mask = nullptr) {
   if (frames.c != 1) throw Error(OCR_ERR_INVALID, "expected N x 1 x H x W");
   if ((int)ps.polygons.size() != frames.n || (int)adjust_values.size() != 2 * frames.n)
     throw Error(OCR_ERR_INVALID, "polygons / adjust_values do not match the frames");
@@ -183,21 +209,16 @@ inline std::vector<std::vector<WordReading>> read_words(const text_detection::Fu
   const ocr_polygons_t polys{frames.n, (int32_t)scores.size(), (int32_t)(xy.size() / 2), img_off.data(), poly_off.data(), xy.data(),
                              scores.data()};
   ocr_glyphs_t* g = nullptr;
-  check(cc ? ocr_segment_glyphs_cc(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, &polys,
-                                   adjust_values.data(), params, cc, &g)
-           : ocr_segment_glyphs(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, &polys,
-                                adjust_values.data(), params, &g));
   struct Free {
-    ocr_glyphs_t* g;
+    ocr_glyphs_t*& g;
     ~Free() { ocr_glyphs_free(g); }
   } free_g{g};
+  std::vector<float> crops;
+  segment_and_crop(det_net, frames.data.data(), frames.n, frames.h, frames.w, &polys, adjust_values.data(), params, cc, mask, &g, crops);
   const int ng = g->n_glyphs;
-  std::vector<float> crops((size_t)ng * 784);
   std::vector<int32_t> labels(ng);
   std::vector<double> probs(ng);
   if (ng > 0) {
-    check(ocr_extract_glyph_crops(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, g, params,
-                                  crops.data()));
     check(ocr_rec_classify(rec_net.handle(), crops.data(), ng, labels.data(), probs.data(), OCR_MEM_HOST));
   }
   std::vector<std::vector<WordReading>> out(frames.n);
@@ -224,12 +245,12 @@ struct WordReadingRectified {
 };
 // ocr_plan_word_strips -> ocr_extract_word_strips -> ocr_word_strip_polygons -> ocr_segment_glyphs -> ocr_extract_glyph_crops ->
 // ocr_rec_classify over host memory (the atlas is one frame of the glyph calls, adj = (1, 1)); per image, per polygon of `ps`.
-// cc as in read_words: a pointer segments the atlas by connected components.
+// cc and mask as in read_words: a pointer segments the atlas by connected components / masks every crop by its glyph's components.
 inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
     const text_detection::FuncT& det_net, const char_recognition::Net& rec_net, const Tensor& frames,
     const text_detection::metrics::PolygonScores& ps, const std::vector<double>& adjust_values,
     const ocr_strip_params_t* strip_params = nullptr, const ocr_segment_params_t* params = nullptr,
-    const ocr_cc_params_t* cc = nullptr) {
+    const ocr_cc_params_t* cc = nullptr, const ocr_mask_params_t* mask = nullptr) {
   if (frames.c != 1) throw Error(OCR_ERR_INVALID, "expected N x 1 x H x W");
   if ((int)ps.polygons.size() != frames.n || (int)adjust_values.size() != 2 * frames.n)
     throw Error(OCR_ERR_INVALID, "polygons / adjust_values do not match the frames");
@@ -268,18 +289,16 @@ inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
   } free_r{rects};
   const double one[2] = {1.0, 1.0};
   ocr_glyphs_t* g = nullptr;
-  check(cc ? ocr_segment_glyphs_cc(det_net.handle(), atlas.data(), 1, hs, tw, OCR_MEM_HOST, rects, one, params, cc, &g)
-           : ocr_segment_glyphs(det_net.handle(), atlas.data(), 1, hs, tw, OCR_MEM_HOST, rects, one, params, &g));
   struct FreeGlyphs {
-    ocr_glyphs_t* g;
+    ocr_glyphs_t*& g;
     ~FreeGlyphs() { ocr_glyphs_free(g); }
   } free_g{g};
+  std::vector<float> crops;
+  segment_and_crop(det_net, atlas.data(), 1, hs, tw, rects, one, params, cc, mask, &g, crops);
   const int ng = g->n_glyphs;
-  std::vector<float> crops((size_t)ng * 784);
   std::vector<int32_t> labels(ng);
   std::vector<double> probs(ng);
   if (ng > 0) {
-    check(ocr_extract_glyph_crops(det_net.handle(), atlas.data(), 1, hs, tw, OCR_MEM_HOST, g, params, crops.data()));
     check(ocr_rec_classify(rec_net.handle(), crops.data(), ng, labels.data(), probs.data(), OCR_MEM_HOST));
   }
   for (int b = 0; b < frames.n; ++b) {

@@ -5,6 +5,8 @@ recognition -> output text), composed over the C ABI.
         ocr_segment_glyphs        every detected word (polygon) -> glyph boxes          (csrc/glyphs.hip, segment_kernel)
           or, with cc=..., ocr_segment_glyphs_cc: connected components, kerned letters split   (csrc/glyph_cc.hip)
         ocr_extract_glyph_crops   every glyph -> one 28 x 28 crop, on the device         (csrc/glyphs.hip, glyph_crop_kernel)
+          or, with cc=... and mask=..., ocr_segment_glyphs_cc_labelled and ocr_extract_glyph_crops_masked: the crop of a glyph holds
+          its own components' ink only
         ocr_rec_classify          every crop -> label in VALUES (utils.rs:7) and its probability
 
     read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values)
@@ -13,7 +15,7 @@ recognition -> output text), composed over the C ABI.
         then the three calls above on the atlas, through the rectangles of ocr_word_strip_polygons
 
 The segmentation and strip rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
-tests/glyph_oracle.py, tests/glyph_cc_oracle.py and tests/strip_oracle.py.
+tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py and tests/strip_oracle.py.
 """
 from __future__ import annotations
 
@@ -50,7 +52,35 @@ def _device_frames(det, frames):
     return x
 
 
-def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None, cc=None
+def _masked(mask, cc) -> bool:
+    """mask: None / False -> the unmasked path; True, a dict of capi.MaskParams' fields or a capi.MaskParams -> masked, which needs cc."""
+    if mask is None or mask is False:
+        return False
+    if cc is None:
+        raise capi.OcrError(1, "mask: masked crops need the connected-component rule (cc={} for its defaults)")
+    return True
+
+
+def _segment_and_crop(det, frames_ptr, n, h, w, polys, adjust_values, params, cc, mask, dev):
+    """The two glyph calls on device frames -> (GlyphSet, crops tensor or None when there is no glyph); blocking."""
+    import torch
+    if not _masked(mask, cc):
+        glyphs = det.segment_glyphs_device(frames_ptr, n, h, w, polys, adjust_values, params, cc)
+        if not glyphs.n_glyphs:
+            return glyphs, None
+        crops = torch.empty((glyphs.n_glyphs, 784), dtype=torch.float32, device=dev)
+        det.extract_glyph_crops_device(frames_ptr, n, h, w, glyphs, crops.data_ptr(), params)
+        return glyphs, crops
+    glyphs, labels = det.segment_glyphs_cc_labelled_device(frames_ptr, n, h, w, polys, adjust_values, params, cc)
+    with labels:
+        if not glyphs.n_glyphs:
+            return glyphs, None
+        crops = torch.empty((glyphs.n_glyphs, 784), dtype=torch.float32, device=dev)
+        det.extract_glyph_crops_masked_device(frames_ptr, n, h, w, glyphs, labels, crops.data_ptr(), params, mask)
+    return glyphs, crops
+
+
+def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None, cc=None, mask=None
                ) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch.
 
@@ -59,6 +89,8 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     polygon_scores: what get_boxes_and_box_scores returned (or its per-image polygon lists); adjust_values: N x 2 as given to it.
     params: capi.SegmentParams, a dict of its fields, or None for the defaults.  cc: None segments by the column rule; capi.CcParams
     or a dict of its fields ({} for the defaults) segments by connected components (ocr_segment_glyphs_cc), which splits kerned letters.
+    mask: None or False cuts every crop from its box alone; True, {} or {"halo": 0} (capi.MaskParams' fields) needs cc and masks every
+    crop by its glyph's components (ocr_segment_glyphs_cc_labelled, ocr_extract_glyph_crops_masked): a kerned neighbour's ink stays out.
     Returns per image, per polygon: (text, probability of every character (f64), glyph boxes k x 4 int32 x0, y0, x1, y1 in frame
     pixels, half-open).  A flat word reads as ""."""
     import torch
@@ -79,13 +111,11 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     n, _, h, w = x.shape
     # the library's calls run on their handles' streams: whatever torch queued to produce x is finished first
     torch.cuda.current_stream(dev).synchronize()
-    glyphs = det.segment_glyphs_device(x.data_ptr(), n, h, w, polys, adjust_values, params, cc)
+    glyphs, crops = _segment_and_crop(det, x.data_ptr(), n, h, w, polys, adjust_values, params, cc, mask, dev)   # blocking
     ng = glyphs.n_glyphs
     labels = np.zeros(0, np.int32)
     probs = np.zeros(0, np.float64)
     if ng:
-        crops = torch.empty((ng, 784), dtype=torch.float32, device=dev)
-        det.extract_glyph_crops_device(x.data_ptr(), n, h, w, glyphs, crops.data_ptr(), params)   # blocking
         lab = torch.empty(ng, dtype=torch.int32, device=dev)
         pr = torch.empty(ng, dtype=torch.float64, device=dev)
         rec.classify_device(crops.data_ptr(), ng, 0, lab.data_ptr(), pr.data_ptr())
@@ -126,12 +156,12 @@ def strip_glyph_quads(strips: "capi.WordStrips", words: np.ndarray, boxes: np.nd
     return np.stack([(q[:, 0:1] + cs * cux) + rs * rvx, (q[:, 1:2] + cs * cuy) + rs * rvy], axis=2)
 
 
-def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None, cc=None
+def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None, cc=None, mask=None
                          ) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch through its upright strip: rotated words are read along their own axis.
 
     Arguments as read_words; strip_params: capi.StripParams, a dict of its fields (strip_height, max_width) or None for the defaults;
-    params and cc: the segmentation parameters and rule as in read_words, applied to the atlas.  Returns per image, per polygon: (text, probability of every character
+    params, cc and mask: the segmentation parameters, rule and crop masking as in read_words, applied to the atlas.  Returns per image, per polygon: (text, probability of every character
     (f64), glyph quads k x 4 x 2 f64: the corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of every glyph box mapped back to frame
     coordinates, strip_glyph_quads).  A flat word reads as ""."""
     import torch
@@ -150,13 +180,11 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     det.extract_word_strips_device(x.data_ptr(), n, h, w, strips, atlas.data_ptr())      # blocking
     hs, tw = strips.height, strips.total_width
     with strips.polygon_block() as rects:
-        glyphs = det.segment_glyphs_device(atlas.data_ptr(), 1, hs, tw, rects, [[1.0, 1.0]], params, cc)
+        glyphs, crops = _segment_and_crop(det, atlas.data_ptr(), 1, hs, tw, rects, [[1.0, 1.0]], params, cc, mask, dev)
     ng = glyphs.n_glyphs
     labels = np.zeros(0, np.int32)
     probs = np.zeros(0, np.float64)
     if ng:
-        crops = torch.empty((ng, 784), dtype=torch.float32, device=dev)
-        det.extract_glyph_crops_device(atlas.data_ptr(), 1, hs, tw, glyphs, crops.data_ptr(), params)
         lab = torch.empty(ng, dtype=torch.int32, device=dev)
         pr = torch.empty(ng, dtype=torch.float64, device=dev)
         rec.classify_device(crops.data_ptr(), ng, 0, lab.data_ptr(), pr.data_ptr())
