@@ -502,7 +502,8 @@ void ocr_glyph_labels_free(ocr_glyph_labels_t* l);
  * sx = ((ox + ((float)c + 0.5f) * ux) + ((float)i + 0.5f) * vx) - 0.5f, sy likewise with (oy, uy, vy), clamped as fminf(fmaxf(s, 0),
  * W - 1 or H - 1) (NaN -> 0), bilinear taps in ocr_extract_crops's operation order, the raw 0..255 value (no / 255): the atlas is a valid
  * frame for ocr_segment_glyphs, with the rectangles of ocr_word_strip_polygons and adj = (1, 1).
- * Out of scope: curved words, pixels inside the rectangle but outside the polygon (not masked), upside-down or vertical text detection.
+ * Out of scope: curved words (ocr_plan_curved_strips below reads those), pixels inside the rectangle but outside the polygon (not masked),
+ * upside-down or vertical text detection.
  * Oracle: tests/strip_oracle.py.  ocr_plan_word_strips needs no GPU (det is not taken).  ocr_extract_word_strips is blocking and runs
  * behind everything queued on the detector's stream, like the glyph calls; frames (N x 1 x H x W f32) and atlas (height x total_width
  * f32, row-major) live in mem_kind memory, the strips block in host memory.  An empty polygon list gives total_width = 0 and launches
@@ -533,6 +534,80 @@ int ocr_extract_word_strips(ocr_det_t* det, const float* frames, int n, int h, i
  * adj = (1, 1) the crop box of rectangle k is exactly word k's columns.  *out: ocr_polygons_free. */
 int ocr_word_strip_polygons(const ocr_word_strips_t* strips, ocr_polygons_t** out);
 void ocr_word_strips_free(ocr_word_strips_t* s);
+
+/* Curved strips: a second planner and sampler beside the word strips, for words whose baseline bends (an arc on a logo, a seal, a
+ * label).  The strip follows the centreline of the polygon's own ring, and every atlas column runs along the centreline's normal, so
+ * the glyphs of an arc come out upright and at full height (BUILD-DEFINED, like the word strips; nothing of those changes).
+ * Geometry (ocr_plan_curved_strips, host C++, f64, every operation separately rounded, no FMA; hypot is libm's as glibc 2.35 computes
+ * it, the restatement the post-processing already uses), for every polygon in polygon order:
+ *  1. rectangle: steps 1-4 of ocr_plan_word_strips unchanged give TL, TR, BR, BL, U = TR - TL, V = BL - TL, |U| and |V|;
+ *     eu = U / |U|, ev = V / |V| per component.  A degenerate word (flag 2) takes the straight fallback of step 9;
+ *  2. ring: all vertices of the polygon in their order (not the hull), each mapped to the frame as P = (x * adj_x, y * adj_y); its
+ *     rectangle coordinates are a = dx * eu_x + dy * eu_y and b = dx * ev_x + dy * ev_y with d = P - TL;
+ *  3. scan lines s = 0..31 at a_s = (|U| * (s + 0.5)) / 32.  An edge A -> B of the closed ring crosses line s when
+ *     (a_A <= a_s) != (a_B <= a_s), at b = b_A + ((a_s - a_A) * (b_B - b_A)) / (a_B - a_A).  top_s = min b and bot_s = max b over the
+ *     crossings (both 0 on a line without one), m_s = (top_s + bot_s) * 0.5, t_s = bot_s - top_s.  More than two crossings on any
+ *     line set flag 4 (folded); the min and max are still used;
+ *  4. valid span: tm = element 16 of the ascending sort of the t_s.  Line s is valid when t_s * 100 >= valid_pct * tm (this excludes
+ *     lines that cross an end cap instead of the two long sides).  lo and hi are the first and the last valid s; the lines between
+ *     them are all used.  tm <= 0 or hi - lo < 1 takes the straight fallback;
+ *  5. centreline: the polyline Q = (0, m_lo - s0 * a_lo), then (a_s, m_s) for s = lo..hi, then (|U|, m_hi + s1 * (|U| - a_hi)), with
+ *     s0 = (m_(lo+1) - m_lo) / (a_(lo+1) - a_lo) and s1 = (m_hi - m_(hi-1)) / (a_hi - a_(hi-1)) the slopes of the first and the last
+ *     segment of the valid span.  len_i = hypot(da, db) of segment i, start_0 = 0, start_(i+1) = start_i + len_i, L = the last start.
+ *     Flag 8 (steep) is set when some segment has |db| * 10 > |da| * 7;
+ *  6. half height: for every s in lo..hi, d = Q_next - Q_prev around that point, c = d_a / hypot(d_a, d_b), hh_s = (t_s * c) * 0.5;
+ *     h = element cnt / 2 (integer division, cnt = hi - lo + 1) of the ascending sort of the hh_s, raised to 0.5 if smaller;
+ *  7. width: Ws = floor((Hs * L) / (2 * h) + 0.5) with Hs = strip_height, clamped to [1, max_width]; above max_width flags the word
+ *     squeezed (flag 1).  tscale = (float)(32.0 / Ws);
+ *  8. knots r = 0..32: P_r is the point of Q at arc length l = (L * r) / 32: on the segment i with the largest index whose start_i <= l,
+ *     P = Q_i + ((l - start_i) * (Q_(i+1) - Q_i)) / len_i per coordinate; P_32 is the last point of Q exactly.
+ *     T_r = P_min(r+1,32) - P_max(r-1,0), each component divided by its hypot; N_r = ((-T_b) * k, T_a * k) with k = (2 * h) / Hs.
+ *     In the frame p = (TL + P_a * eu) + P_b * ev and n = N_a * eu + N_b * ev per component; each of the four values is rounded once
+ *     to f32;
+ *  9. straight fallback (flag 16, alongside flag 2 where it applies): P_r = (TL + U * (r / 32.0)) + V * 0.5, n = V / Hs, h = |V| / 2,
+ *     L = |U|, Ws as in step 5 of the straight rule.
+ * Sampling (ocr_extract_curved_strips, csrc/curved_strips.hip, f32, separately rounded): word k owns atlas columns [col_offsets[k],
+ * col_offsets[k+1]); atlas pixel (i, j) of word k samples frame word_info[2k]: c = j - col_offsets[k], t = ((float)c + 0.5f) * tscale,
+ * r = min((int)t, 31), f = t - (float)r, px = p_r.x + f * (p_(r+1).x - p_r.x) and py, nx, ny likewise, o = ((float)i + 0.5f) -
+ * 0.5f * (float)Hs, sx = (px + o * nx) - 0.5f and sy likewise.  The clamp, the bilinear taps and the blend are exactly those of
+ * ocr_extract_word_strips; the atlas holds raw 0..255 values and, with the rectangles of ocr_curved_strip_polygons and adj = (1, 1),
+ * is a valid frame for every glyph call.
+ * Out of scope: words that turn by more than about 70 degrees in total (their end columns are extended linearly and come out slanted;
+ * flag 8 reports it), folded shapes (flag 4 reports them), a second scan along the centreline's own normals, masking pixels outside
+ * the polygon, vertical or upside-down text.
+ * Oracle: tests/curved_strip_oracle.py.  Memory kinds, blocking, the stream rule and the error cases are those of the word strip
+ * calls: ocr_plan_curved_strips needs no GPU (det is not taken); OCR_ERR_INVALID for a null pointer, a bad mem_kind, n_images != n, a
+ * bad shape, a parameter out of range, a nonzero reserved field, an adjust value that is not finite and > 0, a block whose offsets,
+ * frame indices or tscale values (finite and > 0) do not fit, and an atlas of more than 2^31 elements; the handle stays usable.  An
+ * empty polygon list gives total_width = 0 and launches nothing. */
+#define OCR_CURVE_SCANLINES 32
+#define OCR_CURVE_KNOTS 33 /* K + 1, K = 32 intervals */
+typedef struct ocr_curve_params {
+  int32_t strip_height;  /* 8..128, default 32 */
+  int32_t max_width;     /* 1..8192, default 1024 (per word) */
+  int32_t valid_pct;     /* 1..100, default 80 */
+  int32_t reserved;      /* must be 0 */
+} ocr_curve_params_t;
+typedef struct ocr_curved_strips {
+  int32_t n_images, n_words, height, total_width;
+  const int32_t* img_offsets;  /* [n_images+1] word range per image (= the polygons')                             */
+  const int32_t* col_offsets;  /* [n_words+1]  atlas columns per word                                            */
+  const int32_t* word_info;    /* [2*n_words]  frame, flags (1 squeezed, 2 degenerate, 4 folded, 8 steep, 16 straight fallback) */
+  const float* knots;          /* [4*33*n_words] px, py, nx, ny per knot, as the kernel uses them                */
+  const float* tscale;         /* [n_words]    (float)(32.0 / Ws)                                                */
+  const double* half_heights;  /* [n_words]    h                                                                 */
+  const double* lengths;       /* [n_words]    L                                                                 */
+  const double* scores;        /* [n_words]    the source polygons' scores                                       */
+} ocr_curved_strips_t;
+void ocr_curve_default_params(ocr_curve_params_t* p);
+/* params == NULL -> defaults; h and w are checked only.  *out: ocr_curved_strips_free. */
+int ocr_plan_curved_strips(const ocr_polygons_t* polys, const double* adj_xy, int n, int h, int w, const ocr_curve_params_t* params,
+                           ocr_curved_strips_t** out);
+int ocr_extract_curved_strips(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_curved_strips_t* strips,
+                              float* atlas);
+/* The rule of ocr_word_strip_polygons: one image, n_words rectangles of the atlas with the source scores.  *out: ocr_polygons_free. */
+int ocr_curved_strip_polygons(const ocr_curved_strips_t* strips, ocr_polygons_t** out);
+void ocr_curved_strips_free(ocr_curved_strips_t* s);
 
 /* ---------------------------------------------------------------------------
  * Detection quality metrics (host code; consumers of the polygon lists).  Replaces

@@ -33,6 +33,7 @@ EXPORTS = [
     "ocr_mask_default_params", "ocr_segment_glyphs_cc_labelled", "ocr_glyph_labels_read", "ocr_extract_glyph_crops_masked",
     "ocr_glyph_labels_free",
     "ocr_strip_default_params", "ocr_plan_word_strips", "ocr_extract_word_strips", "ocr_word_strip_polygons", "ocr_word_strips_free",
+    "ocr_curve_default_params", "ocr_plan_curved_strips", "ocr_extract_curved_strips", "ocr_curved_strip_polygons", "ocr_curved_strips_free",
     "ocr_evaluate_image", "ocr_combine_results",
     "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_set_stream", "ocr_rec_set_options", "ocr_rec_synchronize",
     "ocr_rec_forward", "ocr_rec_classify_async", "ocr_rec_classify_profile", "ocr_rec_classify", "ocr_rec_alphabet", "ocr_ctc_greedy_decode",
@@ -103,6 +104,20 @@ class Strips(C.Structure):
                 ("img_offsets", C.POINTER(C.c_int32)), ("col_offsets", C.POINTER(C.c_int32)), ("word_info", C.POINTER(C.c_int32)),
                 ("quads", C.POINTER(C.c_double)), ("maps", C.POINTER(C.c_float)), ("scores", C.POINTER(C.c_double))]
 
+
+class CurveParams(C.Structure):
+    _fields_ = [("strip_height", C.c_int32), ("max_width", C.c_int32), ("valid_pct", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CurvedStripsBlock(C.Structure):
+    """ocr_curved_strips_t."""
+    _fields_ = [("n_images", C.c_int32), ("n_words", C.c_int32), ("height", C.c_int32), ("total_width", C.c_int32),
+                ("img_offsets", C.POINTER(C.c_int32)), ("col_offsets", C.POINTER(C.c_int32)), ("word_info", C.POINTER(C.c_int32)),
+                ("knots", C.POINTER(C.c_float)), ("tscale", C.POINTER(C.c_float)), ("half_heights", C.POINTER(C.c_double)),
+                ("lengths", C.POINTER(C.c_double)), ("scores", C.POINTER(C.c_double))]
+
+
+CURVE_KNOTS = 33
 
 _lib = None
 _hip_shared = False
@@ -228,6 +243,15 @@ def lib() -> C.CDLL:
         L.ocr_word_strip_polygons.argtypes = [C.POINTER(Strips), C.POINTER(C.POINTER(Polygons))]
         L.ocr_word_strips_free.argtypes = [C.POINTER(Strips)]
         L.ocr_word_strips_free.restype = None
+        L.ocr_curve_default_params.argtypes = [C.POINTER(CurveParams)]
+        L.ocr_curve_default_params.restype = None
+        L.ocr_plan_curved_strips.argtypes = [C.POINTER(Polygons), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(CurveParams),
+                                             C.POINTER(C.POINTER(CurvedStripsBlock))]
+        L.ocr_extract_curved_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CurvedStripsBlock),
+                                                C.c_void_p]
+        L.ocr_curved_strip_polygons.argtypes = [C.POINTER(CurvedStripsBlock), C.POINTER(C.POINTER(Polygons))]
+        L.ocr_curved_strips_free.argtypes = [C.POINTER(CurvedStripsBlock)]
+        L.ocr_curved_strips_free.restype = None
         L.ocr_rec_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_rec_destroy.argtypes = [C.c_void_p]
         L.ocr_rec_destroy.restype = None
@@ -612,6 +636,108 @@ def plan_word_strips(polys, adjust_values, h: int, w: int, params=None, scores=N
         lib().ocr_word_strips_free(out)
 
 
+def curve_params(**fields) -> CurveParams:
+    """ocr_curve_default_params with the given fields overridden (strip_height, max_width, valid_pct)."""
+    p = CurveParams()
+    lib().ocr_curve_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k in dict(CurveParams._fields_):
+            setattr(p, k, int(v))
+        else:
+            raise TypeError(f"unknown curve parameter {k!r}")
+    return p
+
+
+def _as_curve_params(params) -> Optional[CurveParams]:
+    if params is None or isinstance(params, CurveParams):
+        return params
+    return curve_params(**params)
+
+
+class CurvedStrips:
+    """The arrays of an ocr_curved_strips_t, copied into numpy: img_offsets [n_images+1], col_offsets [n_words+1], word_info
+    n_words x 2 (frame, flags: 1 squeezed, 2 degenerate, 4 folded, 8 steep, 16 straight fallback), knots n_words x 33 x 4 f32 (px, py,
+    nx, ny), tscale [n_words] f32, half_heights, lengths and scores [n_words] f64; height and total_width of the atlas."""
+
+    def __init__(self, img_offsets, col_offsets, word_info, knots, tscale, half_heights, lengths, scores, height: int):
+        self.img_offsets = np.ascontiguousarray(img_offsets, dtype=np.int32)
+        self.col_offsets = np.ascontiguousarray(col_offsets, dtype=np.int32)
+        self.word_info = np.ascontiguousarray(word_info, dtype=np.int32).reshape(-1, 2)
+        self.knots = np.ascontiguousarray(knots, dtype=np.float32).reshape(-1, CURVE_KNOTS, 4)
+        self.tscale = np.ascontiguousarray(tscale, dtype=np.float32)
+        self.half_heights = np.ascontiguousarray(half_heights, dtype=np.float64)
+        self.lengths = np.ascontiguousarray(lengths, dtype=np.float64)
+        self.scores = np.ascontiguousarray(scores, dtype=np.float64)
+        self.height = int(height)
+
+    @property
+    def n_images(self) -> int:
+        return len(self.img_offsets) - 1
+
+    @property
+    def n_words(self) -> int:
+        return len(self.col_offsets) - 1
+
+    @property
+    def total_width(self) -> int:
+        return int(self.col_offsets[-1])
+
+    @staticmethod
+    def from_block(sp) -> "CurvedStrips":
+        s = sp.contents
+        ni, nw = s.n_images, s.n_words
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return CurvedStrips(arr(s.img_offsets, ni + 1, np.int32), arr(s.col_offsets, nw + 1, np.int32), arr(s.word_info, 2 * nw, np.int32),
+                            arr(s.knots, 4 * CURVE_KNOTS * nw, np.float32), arr(s.tscale, nw, np.float32),
+                            arr(s.half_heights, nw, np.float64), arr(s.lengths, nw, np.float64), arr(s.scores, nw, np.float64), s.height)
+
+    def block(self) -> CurvedStripsBlock:
+        """An ocr_curved_strips_t viewing these arrays (valid while this object lives)."""
+        def p(a, t):
+            return a.ctypes.data_as(C.POINTER(t))
+        return CurvedStripsBlock(self.n_images, self.n_words, self.height, self.total_width, p(self.img_offsets, C.c_int32),
+                                 p(self.col_offsets, C.c_int32), p(self.word_info, C.c_int32), p(self.knots, C.c_float),
+                                 p(self.tscale, C.c_float), p(self.half_heights, C.c_double), p(self.lengths, C.c_double),
+                                 p(self.scores, C.c_double))
+
+    @contextlib.contextmanager
+    def polygon_block(self):
+        """ocr_curved_strip_polygons as the library's own block (a Polygons, valid inside the with statement)."""
+        blk = self.block()
+        out = C.POINTER(Polygons)()
+        check(lib().ocr_curved_strip_polygons(C.byref(blk), C.byref(out)))
+        try:
+            yield out.contents
+        finally:
+            lib().ocr_polygons_free(out)
+
+    def polygons(self):
+        """ocr_curved_strip_polygons: (one image of n_words atlas rectangles, their scores) as postprocess returns polygons."""
+        with self.polygon_block() as p:
+            return polygons_to_python(C.pointer(p))
+
+
+def plan_curved_strips(polys, adjust_values, h: int, w: int, params=None, scores=None) -> CurvedStrips:
+    """ocr_plan_curved_strips (host only, no GPU): arguments as plan_word_strips; params: CurveParams, a dict of its fields (strip_height,
+    max_width, valid_pct), or None (defaults)."""
+    if isinstance(polys, Polygons):
+        st, n = polys, polys.n_images
+    else:
+        st, keep = python_to_polygons(polys, scores if scores is not None else [[0.0] * len(p) for p in polys])
+        n = len(polys)
+    adj = np.ascontiguousarray(adjust_values, dtype=np.float64).reshape(-1, 2)
+    prm = _as_curve_params(params)
+    out = C.POINTER(CurvedStripsBlock)()
+    check(lib().ocr_plan_curved_strips(C.byref(st), adj.ctypes.data_as(C.POINTER(C.c_double)), n, h, w,
+                                       C.byref(prm) if prm is not None else None, C.byref(out)))
+    try:
+        return CurvedStrips.from_block(out)
+    finally:
+        lib().ocr_curved_strips_free(out)
+
+
 class HostBuffer:
     """Pinned host memory from ocr_host_alloc, viewed as a numpy array (frames / maps of the host-memory entry points)."""
 
@@ -886,6 +1012,24 @@ class Detector:
         blk = strips.block()
         check(lib().ocr_extract_word_strips(self._h, _ptr(frames), n, h, w, MEM_HOST, C.byref(blk), _ptr(atlas) if atlas.size else None))
         return atlas
+
+    def plan_curved_strips(self, polys, adjust_values, h: int, w: int, params=None, scores=None) -> CurvedStrips:
+        """capi.plan_curved_strips (host geometry; the handle is not used)."""
+        return plan_curved_strips(polys, adjust_values, h, w, params, scores)
+
+    def extract_curved_strips(self, frames: np.ndarray, strips: CurvedStrips) -> np.ndarray:
+        """The atlas of `strips` from host frames N x 1 x H x W f32 -> height x total_width f32."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        n, _, h, w = frames.shape
+        atlas = np.empty((strips.height, strips.total_width), np.float32)
+        blk = strips.block()
+        check(lib().ocr_extract_curved_strips(self._h, _ptr(frames), n, h, w, MEM_HOST, C.byref(blk), _ptr(atlas) if atlas.size else None))
+        return atlas
+
+    def extract_curved_strips_device(self, frames_ptr: int, n: int, h: int, w: int, strips: CurvedStrips, atlas_ptr: int) -> None:
+        """Device-memory form: frames and atlas are device pointers; blocking."""
+        blk = strips.block()
+        check(lib().ocr_extract_curved_strips(self._h, C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, C.byref(blk), C.c_void_p(atlas_ptr or None)))
 
     def extract_word_strips_device(self, frames_ptr: int, n: int, h: int, w: int, strips: WordStrips, atlas_ptr: int) -> None:
         """The same on device memory: atlas_ptr points at height x total_width f32."""

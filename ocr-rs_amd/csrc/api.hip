@@ -862,6 +862,119 @@ void ocr_word_strips_free(ocr_word_strips_t* s) {
   delete reinterpret_cast<ocr::WordStripsOwned*>(reinterpret_cast<char*>(s) - offsetof(ocr::WordStripsOwned, view));
 }
 
+// ---- curved strips (word_strips.cpp geometry, curved_strips.hip sampling; rule in include/ocr_amd.h, oracle tests/curved_strip_oracle.py)
+void ocr_curve_default_params(ocr_curve_params_t* p) {
+  if (!p) return;
+  p->strip_height = 32;
+  p->max_width = 1024;
+  p->valid_pct = 80;
+  p->reserved = 0;
+}
+
+int ocr_plan_curved_strips(const ocr_polygons_t* polys, const double* adj_xy, int n, int h, int w, const ocr_curve_params_t* params,
+                           ocr_curved_strips_t** out) {
+  return guard([&] {
+    using namespace ocr;
+    if (!polys || !adj_xy || !out) fail(OCR_ERR_INVALID, "plan_curved_strips: null argument");
+    *out = nullptr;
+    if (n < 0 || h < 1 || w < 1) fail(OCR_ERR_INVALID, "plan_curved_strips: N=%d H=%d W=%d", n, h, w);
+    ocr_curve_params_t p;
+    ocr_curve_default_params(&p);
+    if (params) p = *params;
+    if (p.strip_height < 8 || p.strip_height > 128 || p.max_width < 1 || p.max_width > 8192 || p.valid_pct < 1 || p.valid_pct > 100 ||
+        p.reserved)
+      fail(OCR_ERR_INVALID, "plan_curved_strips: params strip_height=%d max_width=%d valid_pct=%d reserved=%d (limits: strip_height "
+           "8..128, max_width 1..8192, valid_pct 1..100, reserved 0)", p.strip_height, p.max_width, p.valid_pct, p.reserved);
+    std::unique_ptr<CurvedStripsOwned> s(new CurvedStripsOwned());
+    plan_curved_strips(*polys, adj_xy, n, p, *s);
+    s->finish();
+    *out = &s.release()->view;
+  });
+}
+
+// a curved strips block from the caller: offsets, frames, knot intervals and size checked before anything reads through it
+static void check_curved_strips(const ocr_curved_strips_t* s, int n, const char* who) {
+  using ocr::fail;
+  if (s->n_images != n) fail(OCR_ERR_INVALID, "%s: strips block holds %d images, frames %d", who, s->n_images, n);
+  const int nw = s->n_words;
+  if (nw < 0 || s->total_width < 0 || s->height < 8 || s->height > 128)
+    fail(OCR_ERR_INVALID, "%s: %d words, height %d, total width %d", who, nw, s->height, s->total_width);
+  if ((int64_t)s->height * s->total_width > ocr::kStripMaxAtlas)
+    fail(OCR_ERR_INVALID, "%s: atlas of %d x %d is more than 2^31 elements", who, s->height, s->total_width);
+  if (!s->col_offsets || (nw > 0 && (!s->word_info || !s->knots || !s->tscale || !s->scores)))
+    fail(OCR_ERR_INVALID, "%s: null array in the strips block", who);
+  if (s->col_offsets[0] != 0 || s->col_offsets[nw] != s->total_width)
+    fail(OCR_ERR_INVALID, "%s: column offsets do not span the %d atlas columns", who, s->total_width);
+  for (int k = 0; k < nw; ++k) {
+    if (s->col_offsets[k + 1] <= s->col_offsets[k]) fail(OCR_ERR_INVALID, "%s: word %d columns [%d, %d)", who, k, s->col_offsets[k], s->col_offsets[k + 1]);
+    if (s->word_info[2 * k] < 0 || s->word_info[2 * k] >= n) fail(OCR_ERR_INVALID, "%s: word %d on frame %d of %d", who, k, s->word_info[2 * k], n);
+    if (!(std::isfinite(s->tscale[k]) && s->tscale[k] > 0)) fail(OCR_ERR_INVALID, "%s: word %d tscale %g (finite and > 0)", who, k, (double)s->tscale[k]);
+  }
+}
+
+int ocr_extract_curved_strips(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_curved_strips_t* strips,
+                              float* atlas) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !frames || !strips) fail(OCR_ERR_INVALID, "extract_curved_strips: null argument");
+    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "extract_curved_strips: mem_kind %d", mem_kind);
+    if (n < 0 || h < 1 || w < 1) fail(OCR_ERR_INVALID, "extract_curved_strips: N=%d H=%d W=%d", n, h, w);
+    check_curved_strips(strips, n, "extract_curved_strips");
+    const int nw = strips->n_words, Hs = strips->height, tw = strips->total_width;
+    if (tw == 0) return;
+    if (!atlas) fail(OCR_ERR_INVALID, "extract_curved_strips: null atlas");
+    std::vector<CurveWord> words(nw);
+    std::vector<int32_t> col_word(tw);
+    for (int k = 0; k < nw; ++k) {
+      const int c0 = strips->col_offsets[k];
+      words[k] = {strips->word_info[2 * k], c0, strips->tscale[k], 0};
+      std::fill(col_word.begin() + c0, col_word.begin() + strips->col_offsets[k + 1], k);
+    }
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    const size_t wd_bytes = words.size() * sizeof(CurveWord), kn_bytes = (size_t)nw * OCR_CURVE_KNOTS * 16, cw_bytes = col_word.size() * 4;
+    const size_t fr_bytes = (size_t)n * h * w * 4, at_bytes = (size_t)Hs * tw * 4;
+    Carve c;
+    const size_t o_wd = c.take(wd_bytes), o_kn = c.take(kn_bytes), o_cw = c.take(cw_bytes);
+    char* sc = static_cast<char*>(det->impl.scratch(1, c.end));
+    OCR_HIP(hipMemcpyAsync(sc + o_wd, words.data(), wd_bytes, hipMemcpyHostToDevice, s));
+    OCR_HIP(hipMemcpyAsync(sc + o_kn, strips->knots, kn_bytes, hipMemcpyHostToDevice, s));
+    OCR_HIP(hipMemcpyAsync(sc + o_cw, col_word.data(), cw_bytes, hipMemcpyHostToDevice, s));
+    const StagedFrames st(det->impl, frames, fr_bytes, atlas, at_bytes, mem_kind, s);
+    launch_curved_strips(st.frames, h, w, at<const CurveWord>(sc, o_wd), at<const float>(sc, o_kn), at<const int32_t>(sc, o_cw), Hs, tw,
+                         st.out, s);
+    st.home(atlas, at_bytes, s);
+  });
+}
+
+int ocr_curved_strip_polygons(const ocr_curved_strips_t* strips, ocr_polygons_t** out) {
+  return guard([&] {
+    using namespace ocr;
+    if (!strips || !out) fail(OCR_ERR_INVALID, "curved_strip_polygons: null argument");
+    *out = nullptr;
+    check_curved_strips(strips, strips->n_images, "curved_strip_polygons");
+    const int nw = strips->n_words;
+    const uint32_t y1 = (uint32_t)strips->height - 1;
+    std::unique_ptr<PolygonsOwned> p(new PolygonsOwned());
+    p->img_offsets = {0, nw};
+    p->poly_offsets.push_back(0);
+    for (int k = 0; k < nw; ++k) {
+      const uint32_t c0 = (uint32_t)strips->col_offsets[k], c1 = (uint32_t)strips->col_offsets[k + 1] - 1;
+      const uint32_t v[8] = {c0, 0, c1, 0, c1, y1, c0, y1};
+      p->xy.insert(p->xy.end(), v, v + 8);
+      p->poly_offsets.push_back(4 * (k + 1));
+      p->scores.push_back(strips->scores[k]);
+    }
+    p->finish();
+    *out = &p.release()->view;
+  });
+}
+
+void ocr_curved_strips_free(ocr_curved_strips_t* s) {
+  if (!s) return;
+  delete reinterpret_cast<ocr::CurvedStripsOwned*>(reinterpret_cast<char*>(s) - offsetof(ocr::CurvedStripsOwned, view));
+}
+
 static std::vector<std::vector<ocr::geom::Pt>> csr_polys(const uint32_t* xy, const int32_t* offsets, int n) {
   std::vector<std::vector<ocr::geom::Pt>> out(n);
   for (int k = 0; k < n; ++k)

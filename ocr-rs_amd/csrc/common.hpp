@@ -255,6 +255,16 @@ struct StripWord {
 void launch_word_strips(const float* frames_dev, int H, int W, const StripWord* words_dev, const int32_t* col_word_dev, int height,
                         int total_width, float* atlas_dev, hipStream_t s);
 
+// curved strips (curved_strips.hip; rule: include/ocr_amd.h ocr_plan_curved_strips, tests/curved_strip_oracle.py).  One record per
+// word: frame, first atlas column and knot intervals per column; knots_dev holds 33 knots (px, py, nx, ny) per word.
+struct CurveWord {
+  int frame, c0;
+  float tscale;
+  int pad;
+};
+void launch_curved_strips(const float* frames_dev, int H, int W, const CurveWord* words_dev, const float* knots_dev,
+                          const int32_t* col_word_dev, int height, int total_width, float* atlas_dev, hipStream_t s);
+
 // recognition net (rec_net.hip): conv1 + pool + conv2 + pool on the matrix cores -> feat [n][1024]; fc1 runs as a
 // conv_igemm 1x1 GEMM over the whole batch; fc2 + softmax(f64) + top-1 in one kernel
 struct RecWeights {

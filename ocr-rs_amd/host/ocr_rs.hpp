@@ -8,8 +8,10 @@
 //   text_detection::metrics::get_boxes_and_box_scores            metrics.rs:37-56
 //   char_recognition::Net::{new_, forward_t}, utils::topk        model.rs:13-39, utils.rs:28-43
 //   read_words: detected words -> glyphs -> text, the pipeline's segmentation step (README.md:20-26), which the reference never built
-//   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words
+//   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words,
+//     or through curved strips (ocr_plan_curved_strips / ocr_extract_curved_strips), for words that bend
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -246,11 +248,13 @@ struct WordReadingRectified {
 // ocr_plan_word_strips -> ocr_extract_word_strips -> ocr_word_strip_polygons -> ocr_segment_glyphs -> ocr_extract_glyph_crops ->
 // ocr_rec_classify over host memory (the atlas is one frame of the glyph calls, adj = (1, 1)); per image, per polygon of `ps`.
 // cc and mask as in read_words: a pointer segments the atlas by connected components / masks every crop by its glyph's components.
+// curved: nullptr takes the straight strips; a pointer (ocr_curve_default_params for the defaults) takes ocr_plan_curved_strips ->
+// ocr_extract_curved_strips -> ocr_curved_strip_polygons instead, strip_params is then not used, and the quads follow the centreline.
 inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
     const text_detection::FuncT& det_net, const char_recognition::Net& rec_net, const Tensor& frames,
     const text_detection::metrics::PolygonScores& ps, const std::vector<double>& adjust_values,
     const ocr_strip_params_t* strip_params = nullptr, const ocr_segment_params_t* params = nullptr,
-    const ocr_cc_params_t* cc = nullptr, const ocr_mask_params_t* mask = nullptr) {
+    const ocr_cc_params_t* cc = nullptr, const ocr_mask_params_t* mask = nullptr, const ocr_curve_params_t* curved = nullptr) {
   if (frames.c != 1) throw Error(OCR_ERR_INVALID, "expected N x 1 x H x W");
   if ((int)ps.polygons.size() != frames.n || (int)adjust_values.size() != 2 * frames.n)
     throw Error(OCR_ERR_INVALID, "polygons / adjust_values do not match the frames");
@@ -271,18 +275,33 @@ inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
   const ocr_polygons_t polys{frames.n, (int32_t)scores.size(), (int32_t)(xy.size() / 2), img_off.data(), poly_off.data(), xy.data(),
                              scores.data()};
   ocr_word_strips_t* st = nullptr;
-  check(ocr_plan_word_strips(&polys, adjust_values.data(), frames.n, frames.h, frames.w, strip_params, &st));
+  ocr_curved_strips_t* cst = nullptr;
   struct FreeStrips {
-    ocr_word_strips_t* s;
-    ~FreeStrips() { ocr_word_strips_free(s); }
-  } free_st{st};
+    ocr_word_strips_t*& s;
+    ocr_curved_strips_t*& c;
+    ~FreeStrips() {
+      ocr_word_strips_free(s);
+      ocr_curved_strips_free(c);
+    }
+  } free_st{st, cst};
+  if (curved)
+    check(ocr_plan_curved_strips(&polys, adjust_values.data(), frames.n, frames.h, frames.w, curved, &cst));
+  else
+    check(ocr_plan_word_strips(&polys, adjust_values.data(), frames.n, frames.h, frames.w, strip_params, &st));
   std::vector<std::vector<WordReadingRectified>> out(frames.n);
-  if (st->total_width == 0) return out;
-  const int hs = st->height, tw = st->total_width;
+  const int hs = curved ? cst->height : st->height, tw = curved ? cst->total_width : st->total_width;
+  const int32_t* st_img = curved ? cst->img_offsets : st->img_offsets;
+  const int32_t* st_col = curved ? cst->col_offsets : st->col_offsets;
+  if (tw == 0) return out;
   std::vector<float> atlas((size_t)hs * tw);
-  check(ocr_extract_word_strips(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, st, atlas.data()));
   ocr_polygons_t* rects = nullptr;
-  check(ocr_word_strip_polygons(st, &rects));
+  if (curved) {
+    check(ocr_extract_curved_strips(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, cst, atlas.data()));
+    check(ocr_curved_strip_polygons(cst, &rects));
+  } else {
+    check(ocr_extract_word_strips(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, st, atlas.data()));
+    check(ocr_word_strip_polygons(st, &rects));
+  }
   struct FreeRects {
     ocr_polygons_t* p;
     ~FreeRects() { ocr_polygons_free(p); }
@@ -302,10 +321,12 @@ inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
     check(ocr_rec_classify(rec_net.handle(), crops.data(), ng, labels.data(), probs.data(), OCR_MEM_HOST));
   }
   for (int b = 0; b < frames.n; ++b) {
-    for (int k = st->img_offsets[b]; k < st->img_offsets[b + 1]; ++k) {
-      const double* q = st->quads + 8 * (size_t)k;
-      const double c0 = st->col_offsets[k], ws = st->col_offsets[k + 1] - st->col_offsets[k];
-      const double cux = (q[2] - q[0]) / ws, cuy = (q[3] - q[1]) / ws, rvx = (q[6] - q[0]) / hs, rvy = (q[7] - q[1]) / hs;
+    for (int k = st_img[b]; k < st_img[b + 1]; ++k) {
+      const double c0 = st_col[k], ws = st_col[k + 1] - st_col[k];
+      const double* q = curved ? nullptr : st->quads + 8 * (size_t)k;
+      const double cux = curved ? 0 : (q[2] - q[0]) / ws, cuy = curved ? 0 : (q[3] - q[1]) / ws;
+      const double rvx = curved ? 0 : (q[6] - q[0]) / hs, rvy = curved ? 0 : (q[7] - q[1]) / hs;
+      const float* kn = curved ? cst->knots + 4 * OCR_CURVE_KNOTS * (size_t)k : nullptr;
       WordReadingRectified r;
       for (int j = g->word_offsets[k]; j < g->word_offsets[k + 1]; ++j) {
         r.text.push_back(utils::VALUES()[labels[j]]);
@@ -314,8 +335,19 @@ inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
         const double cs[4] = {bx[0] - c0, bx[2] - c0, bx[2] - c0, bx[0] - c0}, rs[4] = {(double)bx[1], (double)bx[1], (double)bx[3], (double)bx[3]};
         std::array<double, 8> quad;
         for (int c = 0; c < 4; ++c) {
-          quad[2 * c] = (q[0] + cs[c] * cux) + rs[c] * rvx;
-          quad[2 * c + 1] = (q[1] + cs[c] * cuy) + rs[c] * rvy;
+          if (!curved) {
+            quad[2 * c] = (q[0] + cs[c] * cux) + rs[c] * rvx;
+            quad[2 * c + 1] = (q[1] + cs[c] * cuy) + rs[c] * rvy;
+            continue;
+          }
+          // the sampling map of ocr_extract_curved_strips in f64 from the f32 knots, at t = (x - c0) * (32 / Ws) and row offset y - Hs / 2
+          const double t = cs[c] * (32.0 / ws);
+          const int kr = std::min(std::max((int)t, 0), 31);
+          const double f = t - kr, o = rs[c] - hs / 2.0;
+          double v[4];
+          for (int e = 0; e < 4; ++e) v[e] = (double)kn[4 * kr + e] + f * ((double)kn[4 * kr + 4 + e] - (double)kn[4 * kr + e]);
+          quad[2 * c] = v[0] + o * v[2];
+          quad[2 * c + 1] = v[1] + o * v[3];
         }
         r.quads.push_back(quad);
       }

@@ -13,9 +13,12 @@ recognition -> output text), composed over the C ABI.
         ocr_plan_word_strips      every word -> its minimum-area rectangle, upright      (csrc/word_strips.cpp, host)
         ocr_extract_word_strips   every word -> one strip of the atlas, on the device    (csrc/strips.hip)
         then the three calls above on the atlas, through the rectangles of ocr_word_strip_polygons
+      with curved=True (or a dict of capi.CurveParams' fields), words that bend are read along their own centreline:
+        ocr_plan_curved_strips    every word -> 33 knots of its centreline with normals   (csrc/word_strips.cpp, host)
+        ocr_extract_curved_strips every word -> one strip of the atlas, on the device     (csrc/curved_strips.hip)
 
 The segmentation and strip rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
-tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py and tests/strip_oracle.py.
+tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py, tests/strip_oracle.py and tests/curved_strip_oracle.py.
 """
 from __future__ import annotations
 
@@ -156,9 +159,51 @@ def strip_glyph_quads(strips: "capi.WordStrips", words: np.ndarray, boxes: np.nd
     return np.stack([(q[:, 0:1] + cs * cux) + rs * rvx, (q[:, 1:2] + cs * cuy) + rs * rvy], axis=2)
 
 
-def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None, cc=None, mask=None
-                         ) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
-    """Reads every detected word of a batch through its upright strip: rotated words are read along their own axis.
+def curved_glyph_quads(strips: "capi.CurvedStrips", words: np.ndarray, boxes: np.ndarray) -> np.ndarray:
+    """strip_glyph_quads for curved strips: glyph g of strip words[g] -> k x 4 x 2 f64 frame coordinates of the corners (x0, y0), (x1, y0),
+    (x1, y1), (x0, y1).  The sampling map of ocr_extract_curved_strips in f64 from the f32 knots: t = (x - c0) * (32 / Ws),
+    r = min(int(t), 31), f = t - r, (px, py, nx, ny) = knot_r + f * (knot_(r+1) - knot_r), the point (px + o * nx, py + o * ny) at the
+    row offset o = y - Hs / 2."""
+    words = np.asarray(words, np.int64)
+    c0 = strips.col_offsets[words].astype(np.float64)[:, None]
+    ws = (strips.col_offsets[words + 1] - strips.col_offsets[words]).astype(np.float64)[:, None]
+    hs = float(strips.height)
+    b = np.asarray(boxes, np.int64).reshape(-1, 4)
+    xs = np.stack([b[:, 0], b[:, 2], b[:, 2], b[:, 0]], axis=1).astype(np.float64)
+    ys = np.stack([b[:, 1], b[:, 1], b[:, 3], b[:, 3]], axis=1).astype(np.float64)
+    t = (xs - c0) * (32.0 / ws)
+    r = np.clip(t.astype(np.int64), 0, 31)
+    f = (t - r.astype(np.float64))[..., None]
+    kn = strips.knots.astype(np.float64)
+    k0, k1 = kn[words[:, None], r], kn[words[:, None], r + 1]
+    kv = k0 + f * (k1 - k0)
+    o = ys - hs / 2
+    return np.stack([kv[..., 0] + o * kv[..., 2], kv[..., 1] + o * kv[..., 3]], axis=2)
+
+
+def _curved(curved, strip_params):
+    """curved: None / False -> None (the straight strips); True, {} , a dict of capi.CurveParams' fields or a capi.CurveParams -> the
+    CurveParams, which take strip_height and max_width from strip_params where the dict does not name them."""
+    if curved is None or curved is False:
+        return None
+    if isinstance(curved, capi.CurveParams):
+        return curved
+    fields = {}
+    if isinstance(strip_params, capi.StripParams):
+        fields.update(strip_height=strip_params.strip_height, max_width=strip_params.max_width)
+    elif strip_params:
+        fields.update(strip_params)
+    if curved is not True:
+        fields.update(curved)
+    return capi.curve_params(**fields)
+
+
+def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None, cc=None, mask=None,
+                         curved=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+    """Reads every detected word of a batch through its upright strip: rotated words are read along their own axis, and with
+    curved=True (or {} or a dict of capi.CurveParams' fields: strip_height, max_width, valid_pct) words that bend are read along their
+    own centreline (ocr_plan_curved_strips, ocr_extract_curved_strips; the glyph quads then come from curved_glyph_quads).  curved=None
+    or False takes the straight strips.
 
     Arguments as read_words; strip_params: capi.StripParams, a dict of its fields (strip_height, max_width) or None for the defaults;
     params, cc and mask: the segmentation parameters, rule and crop masking as in read_words, applied to the atlas.  Returns per image, per polygon: (text, probability of every character
@@ -173,11 +218,18 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     x = _device_frames(det, frames)
     dev = x.device
     n, _, h, w = x.shape
-    strips = det.plan_word_strips(polys, adjust_values, h, w, strip_params, scores)
+    cp = _curved(curved, strip_params)
+    if cp is None:
+        strips = det.plan_word_strips(polys, adjust_values, h, w, strip_params, scores)
+    else:
+        strips = det.plan_curved_strips(polys, adjust_values, h, w, cp, scores)
     if strips.total_width == 0:
         return [[] for _ in range(n)]
     atlas = torch.empty((strips.height, strips.total_width), dtype=torch.float32, device=dev)
-    det.extract_word_strips_device(x.data_ptr(), n, h, w, strips, atlas.data_ptr())      # blocking
+    if cp is None:
+        det.extract_word_strips_device(x.data_ptr(), n, h, w, strips, atlas.data_ptr())      # blocking
+    else:
+        det.extract_curved_strips_device(x.data_ptr(), n, h, w, strips, atlas.data_ptr())    # blocking
     hs, tw = strips.height, strips.total_width
     with strips.polygon_block() as rects:
         glyphs, crops = _segment_and_crop(det, atlas.data_ptr(), 1, hs, tw, rects, [[1.0, 1.0]], params, cc, mask, dev)
@@ -190,7 +242,8 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
         rec.classify_device(crops.data_ptr(), ng, 0, lab.data_ptr(), pr.data_ptr())
         rec.synchronize()
         labels, probs = lab.cpu().numpy(), pr.cpu().numpy()
-    quads = strip_glyph_quads(strips, np.repeat(np.arange(glyphs.n_words), np.diff(glyphs.word_offsets)), glyphs.boxes)
+    quads = (strip_glyph_quads if cp is None else curved_glyph_quads)(
+        strips, np.repeat(np.arange(glyphs.n_words), np.diff(glyphs.word_offsets)), glyphs.boxes)
     text = "".join(VALUES[int(c)] for c in labels)
     out = []
     for b in range(n):
