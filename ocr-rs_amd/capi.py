@@ -298,6 +298,8 @@ def test_lib() -> C.CDLL:
         L.ocr_test_min_area_box.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
         L.ocr_test_box_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_void_p]
+        L.ocr_test_box_scores_batch.argtypes = ([C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_double] +
+                                                [C.c_void_p] * 3)
         L.ocr_test_conv_bench.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_float)]
         L.ocr_test_conv_run.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] +
                                         [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 2)
@@ -1293,6 +1295,30 @@ class Detector:
         check(test_lib().ocr_test_box_scores(self._h, _ptr(pred), h, w, _ptr(xy), _ptr(cnt), len(polys), _ptr(sums),
                                         _ptr(counts)))
         return sums, counts
+
+    BOX_SCORE_SENTINEL = -7.0
+
+    def debug_box_scores_batch(self, preds_nhw: np.ndarray, polys, images=None, grid: int = 0, dev_count: Optional[int] = None, slack: int = 0):
+        """Test hook: the box-score kernel on n maps (N x H x W, or one H x W) for polygons with an image index each (default 0).
+        grid == 0 is the plain launch; grid > 0 the counted one with that many workgroups and `dev_count` (default: all polygons) as the
+        job count in device memory.  `slack` more job and result slots lie behind the list (copies of job 0).  Every result slot holds
+        BOX_SCORE_SENTINEL before the launch.  Returns (sums, counts, boxes as (min_x, min_y, bw, bh), slack_sums, slack_counts)."""
+        pred = np.ascontiguousarray(preds_nhw, dtype=np.float32)
+        if pred.ndim == 2:
+            pred = pred[None]
+        n, h, w = pred.shape
+        npoly = len(polys)
+        xy = np.asarray([c for p in polys for pt in p for c in pt] or [0, 0], dtype=np.int32)
+        cnt = np.asarray([len(p) for p in polys] or [0], dtype=np.int32)
+        img = np.zeros(max(npoly, 1), np.int32) if images is None else np.ascontiguousarray(list(images) or [0], dtype=np.int32)
+        assert images is None or len(images) == npoly
+        sums = np.empty(max(npoly + slack, 1), np.float64)
+        counts = np.empty(max(npoly + slack, 1), np.float64)
+        box = np.empty((max(npoly, 1), 4), np.int32)
+        check(test_lib().ocr_test_box_scores_batch(self._h, _ptr(pred), n, h, w, _ptr(xy), _ptr(cnt), _ptr(img), npoly, int(grid),
+                                                   npoly if dev_count is None else int(dev_count), int(slack), self.BOX_SCORE_SENTINEL,
+                                                   _ptr(sums), _ptr(counts), _ptr(box)))
+        return sums[:npoly], counts[:npoly], [tuple(int(v) for v in b) for b in box[:npoly]], sums[npoly:npoly + slack], counts[npoly:npoly + slack]
 
     def detect_pipelined(self, x_ptr: int, n: int, h: int, w: int, prob_ptr: int, adjust_values=None,
                          params: Optional[PostprocParams] = None, convert: bool = True):

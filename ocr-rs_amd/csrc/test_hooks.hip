@@ -244,6 +244,68 @@ int ocr_test_box_scores(ocr_det_t* det, const float* prob_host, int h, int w, co
     OCR_HIP(hipStreamSynchronize(s));
   });
 }
+// the whole box-score kernel on caller data: n maps of h x w, polygons with an image index each, through either launch.  grid == 0:
+// launch_box_scores; grid > 0: launch_box_scores_counted with `grid` workgroups and the job count in device memory (dev_count, 0 ..
+// n_polys - what candidates.hip's totals[0] would hold).  Behind the n_polys jobs lie `slack` more, copies of job 0, which no launch may
+// touch.  EVERY result slot (n_polys + slack sums and counts) holds `sentinel` before the launch and comes back as it is afterwards.
+// Boxes as build_jobs (postprocess.hip) makes them - x clamped by H, y by W - and returned as (min_x, min_y, bw, bh) per polygon.
+int ocr_test_box_scores_batch(ocr_det_t* det, const float* prob_host, int n, int h, int w, const int32_t* xy, const int32_t* counts,
+                              const int32_t* images, int n_polys, int grid, int dev_count, int slack, double sentinel, double* sums_out,
+                              double* counts_out, int32_t* box_out) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !prob_host || !sums_out || !counts_out || !box_out) fail(OCR_ERR_INVALID, "null argument");
+    if (n <= 0 || h <= 0 || w <= 0 || n_polys < 0 || slack < 0 || grid < 0 || grid > 65535 || dev_count < 0 || dev_count > n_polys ||
+        (slack > 0 && n_polys == 0))
+      fail(OCR_ERR_INVALID, "box scores: bad shape");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    std::vector<BoxScoreJob> jobs;
+    int pos = 0;
+    for (int k = 0; k < n_polys; ++k) {
+      if (counts[k] < 1 || counts[k] > kBoxScoreMaxPts) fail(OCR_ERR_INVALID, "polygon with %d vertices (1 .. %d)", counts[k], kBoxScoreMaxPts);
+      if (images[k] < 0 || images[k] >= n) fail(OCR_ERR_INVALID, "polygon %d: image %d of %d", k, images[k], n);
+      int mnx = INT32_MAX, mxx = 0, mny = INT32_MAX, mxy = 0;
+      for (int i = 0; i < counts[k]; ++i) {
+        const int x = xy[2 * (pos + i)], y = xy[2 * (pos + i) + 1];
+        if (x < -65535 || x > 65535 || y < -65535 || y > 65535) fail(OCR_ERR_INVALID, "polygon %d: coordinate out of range", k);
+        mnx = std::min(mnx, x), mxx = std::max(mxx, x);
+        mny = std::min(mny, y), mxy = std::max(mxy, y);
+      }
+      // the reference clamps x by size[-2] (=H) and y by size[-1] (=W): metrics.rs:151-166
+      mnx = std::clamp(mnx, 0, h - 1), mxx = std::clamp(mxx, 0, h - 1);
+      mny = std::clamp(mny, 0, w - 1), mxy = std::clamp(mxy, 0, w - 1);
+      if (mxx >= w || mxy >= h) fail(OCR_ERR_INVALID, "non-square map: box (%d,%d) leaves the %dx%d map (the reference would fail in narrow())", mxx, mxy, w, h);
+      jobs.push_back(BoxScoreJob{images[k], pos, counts[k], mnx, mny, mxx - mnx + 1, mxy - mny + 1});
+      box_out[4 * k] = mnx, box_out[4 * k + 1] = mny, box_out[4 * k + 2] = mxx - mnx + 1, box_out[4 * k + 3] = mxy - mny + 1;
+      pos += counts[k];
+    }
+    for (int k = 0; k < slack; ++k) jobs.push_back(jobs[0]);
+    const size_t slots = (size_t)n_polys + slack, map_bytes = (size_t)n * h * w * 4;
+    for (size_t k = 0; k < slots; ++k) sums_out[k] = counts_out[k] = sentinel;
+    if (slots == 0) return;
+    Carve c;   // the maps first
+    c.take(map_bytes);
+    const size_t o_jobs = c.take(slots * sizeof(BoxScoreJob)), o_pts = c.take((size_t)pos * 8), o_sum = c.take(slots * 8), o_cnt = c.take(slots * 8),
+                 o_n = c.take(4);
+    char* sc = static_cast<char*>(det->impl.scratch(0, c.end));
+    OCR_HIP(hipMemcpyAsync(sc, prob_host, map_bytes, hipMemcpyHostToDevice, s));
+    OCR_HIP(hipMemcpyAsync(sc + o_jobs, jobs.data(), slots * sizeof(BoxScoreJob), hipMemcpyHostToDevice, s));
+    OCR_HIP(hipMemcpyAsync(sc + o_pts, xy, (size_t)pos * 8, hipMemcpyHostToDevice, s));
+    OCR_HIP(hipMemcpyAsync(sc + o_sum, sums_out, slots * 8, hipMemcpyHostToDevice, s));
+    OCR_HIP(hipMemcpyAsync(sc + o_cnt, counts_out, slots * 8, hipMemcpyHostToDevice, s));
+    OCR_HIP(hipMemcpyAsync(sc + o_n, &dev_count, 4, hipMemcpyHostToDevice, s));
+    if (grid == 0)
+      launch_box_scores(at<const float>(sc, 0), h, w, at<const BoxScoreJob>(sc, o_jobs), at<const int32_t>(sc, o_pts), n_polys, at<double>(sc, o_sum),
+                        at<double>(sc, o_cnt), s);
+    else
+      launch_box_scores_counted(at<const float>(sc, 0), h, w, at<const BoxScoreJob>(sc, o_jobs), at<const int32_t>(sc, o_pts), at<const int>(sc, o_n), grid,
+                                at<double>(sc, o_sum), at<double>(sc, o_cnt), s);
+    OCR_HIP(hipMemcpyAsync(sums_out, sc + o_sum, slots * 8, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(counts_out, sc + o_cnt, slots * 8, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipStreamSynchronize(s));
+  });
+}
 // one conv_igemm launch on caller data (kernel-level parity hook).  All host arrays are f32; with in_bf16 /
 // out_bf16 they are rounded to bf16 (nearest even) on the way in and widened on the way out, so the caller
 // compares against a reference computed from the SAME rounded operands.  in: NHWC; cat4: the four pyramid

@@ -73,13 +73,15 @@ def _box(pts, h, w):
 def test_device_douglas_peucker_equals_the_oracle(golden_dir):
     """dp_kernel / cand_count / cand_fill (candidates.hip) against O.arc_length + O.approximate_polygon_dp: on the oracle's contours of
     the four reference fixtures (800 x 800), of text-like and dense pages, and of noise and blobs - hundreds of short contours, straight
-    runs (ties for the farthest point), contours of fewer than four points."""
+    runs (ties for the farthest point), contours of fewer than four points.  The job boxes are the ones O.box_score_fast uses, on wide and
+    tall maps too."""
     rng = np.random.default_rng(17)
     maps = [(n, (_img(golden_dir, n) > 0).astype(np.uint8)) for n in FIXTURES]
     maps.append(("text-like 640", (FX.text_like_maps(1, 640, 5)[0, 0] > 0.6).astype(np.uint8)))
     maps.append(("dense 320", (FX.dense_text_maps(1, 320, 6)[0, 0] > 0.6).astype(np.uint8)))
     for h, w, p in ((96, 96, 0.5), (128, 160, 0.35), (64, 224, 0.65)):
         maps.append((f"noise {h}x{w}", (rng.random((h, w)) < p).astype(np.uint8)))
+    maps.append(("noise 224x64", (np.random.default_rng(18).random((224, 64)) < 0.6).astype(np.uint8)))   # a tall one: y is clamped by W
     m = rng.random((192, 192))
     for _ in range(30):
         m = (m + np.roll(m, 1, 0) + np.roll(m, 1, 1) + np.roll(m, -1, 0) + np.roll(m, -1, 1)) / 5
@@ -94,8 +96,7 @@ def test_device_douglas_peucker_equals_the_oracle(golden_dir):
         want = _oracle_candidates(contours)
         got, boxes = capi.device_candidates(contours, h, w)
         assert got == want, name
-        if h == w:
-            assert boxes == [_box(c, h, w) for c in want], name
+        assert boxes == [_box(c, h, w) for c in want], name   # also where the clamp does something: x by H on wide maps, y by W on tall ones
         total += len(want)
     assert total > 100
 
