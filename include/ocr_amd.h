@@ -609,6 +609,57 @@ int ocr_extract_curved_strips(ocr_det_t* det, const float* frames, int n, int h,
 int ocr_curved_strip_polygons(const ocr_curved_strips_t* strips, ocr_polygons_t** out);
 void ocr_curved_strips_free(ocr_curved_strips_t* s);
 
+/* Line grouping: the words of every page linked into text lines, the lines in reading order (BUILD-DEFINED, like the strips: the
+ * reference's "output text" step was never built).  Input per image is its words as quads, 8 doubles TL, TR, BR, BL each, exactly the
+ * `quads` of ocr_word_strips_t; word_img_offsets [n_images+1] is the word range per image (its img_offsets).  All arithmetic is f64,
+ * every operation separately rounded, no FMA; sqrt and divide are IEEE.
+ * Word k:  U = TR - TL, V = BL - TL; lu = sqrt(Ux*Ux + Uy*Uy), lv likewise from V; C = ((TLx + BRx) * 0.5, (TLy + BRy) * 0.5);
+ *   u = (Ux / lu, Uy / lu), v likewise.  A word with lu == 0 or lv == 0 is isolated (flag 1): it takes part in no link and is a line
+ *   of its own.
+ * Word j is a right candidate of word i when both are non-isolated words of one image, j != i, and with d = Cj - Ci,
+ *   a = dx*uix + dy*uiy, b = dx*vix + dy*viy, hmin = min(lvi, lvj), hmax = max(lvi, lvj):
+ *    1. a > 0;
+ *    2. fabs(b) <= line_tol * hmin;
+ *    3. hmax <= height_ratio * hmin;
+ *    4. uix*ujx + uiy*ujy >= min_cos;
+ *    5. g <= max_gap * hmax, with g = a - (lui + luj) * 0.5.
+ * Links:  right[i] is the candidate j with the smallest a, ties to the smaller j, -1 without one.  left[j] is the i, among all i that
+ *   have j as a right candidate, with the smallest a (the a computed in i's frame), ties to the smaller i.  The link i -> j exists iff
+ *   right[i] == j && left[j] == i.
+ * Links form chains.  A ring of words (a seal) can close a chain into a cycle: it is cut on the link that enters its smallest-index
+ *   word, which gets flag 2.  A line is a chain, head to tail.  The lines of an image are ordered by (Cy, Cx, index) of their head
+ *   word, ascending.  gaps[p] is g / hmax of the link that leads to the word at position p of `order`, 0.0 for a head: callers decide
+ *   from it what is a space and what is a tab.
+ * Out of scope: column detection (two columns closer than max_gap heights merge line by line, and the lines of wider-spaced columns
+ *   interleave by height), right-to-left and vertical scripts, spaces inside a polygon, paragraph structure.
+ * Oracle: tests/line_oracle.py; kernels: csrc/lines.hip (link kernel over all pairs of an image, chain kernel per image).
+ * The call is blocking and runs behind everything queued on the detector's stream, like the glyph calls (no overlap with a pending
+ * pipelined forward is promised).  All pointers are host memory.  OCR_ERR_INVALID for a null pointer (params == NULL -> defaults),
+ * offsets that do not start at 0 or decrease, n_images < 1, a parameter out of range or a nonzero reserved field, a non-finite
+ * coordinate, more than 4096 words in one image; all of it is checked on the host before anything is launched, and the handle stays
+ * usable.  Zero words in the batch launch nothing and return an empty block with valid offsets. */
+#define OCR_LINE_MAX_WORDS 4096 /* per image, the polygon chain's contour limit */
+typedef struct ocr_line_params {
+  double line_tol;      /* (0, 4],  default 0.5   */
+  double height_ratio;  /* [1, 16], default 2.0   */
+  double min_cos;       /* [0, 1],  default 0.866 */
+  double max_gap;       /* [0, 64], default 3.0   */
+  int32_t reserved[2];  /* must be 0 */
+} ocr_line_params_t;
+typedef struct ocr_lines {
+  int32_t n_images, n_words, n_lines;
+  const int32_t* img_offsets;   /* [n_images+1] line range per image              */
+  const int32_t* line_offsets;  /* [n_lines+1]  range of `order` per line         */
+  const int32_t* order;         /* [n_words]    batch-global word indices, reading order */
+  const int32_t* word_flags;    /* [n_words]    by word index: 1 isolated, 2 cycle cut here */
+  const double*  gaps;          /* [n_words]    by position in `order`            */
+} ocr_lines_t;
+void ocr_line_default_params(ocr_line_params_t* p);
+/* *out: ocr_lines_free. */
+int  ocr_group_lines(ocr_det_t* det, const double* quads, const int32_t* word_img_offsets, int n_images,
+                     const ocr_line_params_t* params, ocr_lines_t** out);
+void ocr_lines_free(ocr_lines_t* l);
+
 /* ---------------------------------------------------------------------------
  * Detection quality metrics (host code; consumers of the polygon lists).  Replaces
  *   evaluate_image(gt, ignore_flags, pred) -> Result<MetricsItem>      metrics.rs:255-380

@@ -34,6 +34,7 @@ EXPORTS = [
     "ocr_glyph_labels_free",
     "ocr_strip_default_params", "ocr_plan_word_strips", "ocr_extract_word_strips", "ocr_word_strip_polygons", "ocr_word_strips_free",
     "ocr_curve_default_params", "ocr_plan_curved_strips", "ocr_extract_curved_strips", "ocr_curved_strip_polygons", "ocr_curved_strips_free",
+    "ocr_line_default_params", "ocr_group_lines", "ocr_lines_free",
     "ocr_evaluate_image", "ocr_combine_results",
     "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_set_stream", "ocr_rec_set_options", "ocr_rec_synchronize",
     "ocr_rec_forward", "ocr_rec_classify_async", "ocr_rec_classify_profile", "ocr_rec_classify", "ocr_rec_alphabet", "ocr_ctc_greedy_decode",
@@ -118,6 +119,21 @@ class CurvedStripsBlock(C.Structure):
 
 
 CURVE_KNOTS = 33
+
+
+class LineParams(C.Structure):
+    _fields_ = [("line_tol", C.c_double), ("height_ratio", C.c_double), ("min_cos", C.c_double), ("max_gap", C.c_double),
+                ("reserved", C.c_int32 * 2)]
+
+
+class LinesBlock(C.Structure):
+    """ocr_lines_t."""
+    _fields_ = [("n_images", C.c_int32), ("n_words", C.c_int32), ("n_lines", C.c_int32),
+                ("img_offsets", C.POINTER(C.c_int32)), ("line_offsets", C.POINTER(C.c_int32)), ("order", C.POINTER(C.c_int32)),
+                ("word_flags", C.POINTER(C.c_int32)), ("gaps", C.POINTER(C.c_double))]
+
+
+LINE_MAX_WORDS = 4096
 
 _lib = None
 _hip_shared = False
@@ -252,6 +268,11 @@ def lib() -> C.CDLL:
         L.ocr_curved_strip_polygons.argtypes = [C.POINTER(CurvedStripsBlock), C.POINTER(C.POINTER(Polygons))]
         L.ocr_curved_strips_free.argtypes = [C.POINTER(CurvedStripsBlock)]
         L.ocr_curved_strips_free.restype = None
+        L.ocr_line_default_params.argtypes = [C.POINTER(LineParams)]
+        L.ocr_line_default_params.restype = None
+        L.ocr_group_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LineParams), C.POINTER(C.POINTER(LinesBlock))]
+        L.ocr_lines_free.argtypes = [C.POINTER(LinesBlock)]
+        L.ocr_lines_free.restype = None
         L.ocr_rec_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_rec_destroy.argtypes = [C.c_void_p]
         L.ocr_rec_destroy.restype = None
@@ -740,6 +761,69 @@ def plan_curved_strips(polys, adjust_values, h: int, w: int, params=None, scores
         lib().ocr_curved_strips_free(out)
 
 
+def line_params(**fields) -> LineParams:
+    """ocr_line_default_params with the given fields overridden (line_tol, height_ratio, min_cos, max_gap)."""
+    p = LineParams()
+    lib().ocr_line_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k == "reserved":
+            p.reserved[0], p.reserved[1] = (int(x) for x in v)
+        elif k in dict(LineParams._fields_):
+            setattr(p, k, float(v))
+        else:
+            raise TypeError(f"unknown line parameter {k!r}")
+    return p
+
+
+def _as_line_params(params) -> Optional[LineParams]:
+    if params is None or isinstance(params, LineParams):
+        return params
+    return line_params(**params)
+
+
+class Lines:
+    """The arrays of an ocr_lines_t, copied into numpy: img_offsets [n_images+1] (line range per image), line_offsets [n_lines+1]
+    (range of `order` per line), order [n_words] (batch-global word indices in reading order), word_flags [n_words] by word index
+    (1 isolated, 2 a cycle was cut in front of this word), gaps [n_words] f64 by position in `order` (g / hmax of the link that leads to
+    the word, 0.0 for the head of a line)."""
+
+    def __init__(self, img_offsets, line_offsets, order, word_flags, gaps):
+        self.img_offsets = np.ascontiguousarray(img_offsets, dtype=np.int32)
+        self.line_offsets = np.ascontiguousarray(line_offsets, dtype=np.int32)
+        self.order = np.ascontiguousarray(order, dtype=np.int32)
+        self.word_flags = np.ascontiguousarray(word_flags, dtype=np.int32)
+        self.gaps = np.ascontiguousarray(gaps, dtype=np.float64)
+
+    @property
+    def n_images(self) -> int:
+        return len(self.img_offsets) - 1
+
+    @property
+    def n_lines(self) -> int:
+        return len(self.line_offsets) - 1
+
+    @property
+    def n_words(self) -> int:
+        return len(self.order)
+
+    @staticmethod
+    def from_block(lp) -> "Lines":
+        s = lp.contents
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return Lines(arr(s.img_offsets, s.n_images + 1, np.int32), arr(s.line_offsets, s.n_lines + 1, np.int32),
+                     arr(s.order, s.n_words, np.int32), arr(s.word_flags, s.n_words, np.int32), arr(s.gaps, s.n_words, np.float64))
+
+    def lines(self, b: int) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """image b: per line (batch-global word indices in reading order, their gaps)"""
+        out = []
+        for l in range(int(self.img_offsets[b]), int(self.img_offsets[b + 1])):
+            p0, p1 = int(self.line_offsets[l]), int(self.line_offsets[l + 1])
+            out.append((self.order[p0:p1].copy(), self.gaps[p0:p1].copy()))
+        return out
+
+
 class HostBuffer:
     """Pinned host memory from ocr_host_alloc, viewed as a numpy array (frames / maps of the host-memory entry points)."""
 
@@ -1037,6 +1121,20 @@ class Detector:
         """The same on device memory: atlas_ptr points at height x total_width f32."""
         blk = strips.block()
         check(lib().ocr_extract_word_strips(self._h, C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, C.byref(blk), C.c_void_p(atlas_ptr or None)))
+
+    def group_lines(self, quads, img_offsets, params=None) -> Lines:
+        """ocr_group_lines: quads n_words x 8 f64 (TL, TR, BR, BL, the quads of a WordStrips), img_offsets [n_images+1] the word range
+        per image; params: LineParams, a dict of its fields, or None (defaults).  Blocking, on the handle's stream."""
+        q = np.ascontiguousarray(quads, dtype=np.float64).reshape(-1)
+        off = np.ascontiguousarray(img_offsets, dtype=np.int32).reshape(-1)
+        prm = _as_line_params(params)
+        out = C.POINTER(LinesBlock)()
+        check(lib().ocr_group_lines(self._h, _ptr(q) if q.size else None, _ptr(off) if off.size else None, len(off) - 1,
+                                    C.byref(prm) if prm is not None else None, C.byref(out)))
+        try:
+            return Lines.from_block(out)
+        finally:
+            lib().ocr_lines_free(out)
 
     def debug_stage(self, stage_id: int, shape_nhwc) -> np.ndarray:
         """Test hook: NHWC intermediate of the last forward, returned as NCHW."""

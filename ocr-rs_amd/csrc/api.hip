@@ -975,6 +975,95 @@ void ocr_curved_strips_free(ocr_curved_strips_t* s) {
   delete reinterpret_cast<ocr::CurvedStripsOwned*>(reinterpret_cast<char*>(s) - offsetof(ocr::CurvedStripsOwned, view));
 }
 
+// ---- line grouping (lines.hip; rule in include/ocr_amd.h, oracle tests/line_oracle.py)
+void ocr_line_default_params(ocr_line_params_t* p) {
+  if (!p) return;
+  p->line_tol = 0.5;
+  p->height_ratio = 2.0;
+  p->min_cos = 0.866;
+  p->max_gap = 3.0;
+  p->reserved[0] = p->reserved[1] = 0;
+}
+
+int ocr_group_lines(ocr_det_t* det, const double* quads, const int32_t* word_img_offsets, int n_images, const ocr_line_params_t* params,
+                    ocr_lines_t** out) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !word_img_offsets || !out) fail(OCR_ERR_INVALID, "group_lines: null argument");
+    *out = nullptr;
+    if (n_images < 1) fail(OCR_ERR_INVALID, "group_lines: %d images", n_images);
+    ocr_line_params_t p;
+    ocr_line_default_params(&p);
+    if (params) p = *params;
+    // (written so that a NaN is out of range)
+    if (!(p.line_tol > 0 && p.line_tol <= 4) || !(p.height_ratio >= 1 && p.height_ratio <= 16) || !(p.min_cos >= 0 && p.min_cos <= 1) ||
+        !(p.max_gap >= 0 && p.max_gap <= 64) || p.reserved[0] || p.reserved[1])
+      fail(OCR_ERR_INVALID, "group_lines: params line_tol=%g height_ratio=%g min_cos=%g max_gap=%g reserved=(%d, %d) (limits: line_tol "
+           "(0, 4], height_ratio [1, 16], min_cos [0, 1], max_gap [0, 64], reserved 0)", p.line_tol, p.height_ratio, p.min_cos, p.max_gap,
+           p.reserved[0], p.reserved[1]);
+    if (word_img_offsets[0] != 0) fail(OCR_ERR_INVALID, "group_lines: word offsets start at %d", word_img_offsets[0]);
+    int max_words = 0;
+    for (int b = 0; b < n_images; ++b) {
+      const int64_t cnt = (int64_t)word_img_offsets[b + 1] - word_img_offsets[b];
+      if (cnt < 0) fail(OCR_ERR_INVALID, "group_lines: word offsets decrease at image %d", b);
+      if (cnt > OCR_LINE_MAX_WORDS) fail(OCR_ERR_INVALID, "group_lines: image %d has %lld words (limit %d)", b, (long long)cnt, OCR_LINE_MAX_WORDS);
+      max_words = std::max(max_words, (int)cnt);
+    }
+    const int nw = word_img_offsets[n_images];
+    if (nw > 0 && !quads) fail(OCR_ERR_INVALID, "group_lines: null quads");
+    for (size_t e = 0; e < (size_t)nw * 8; ++e)
+      if (!std::isfinite(quads[e])) fail(OCR_ERR_INVALID, "group_lines: word %zu has a non-finite coordinate", e / 8);
+    std::unique_ptr<LinesOwned> l(new LinesOwned());
+    l->img_offsets.assign(1, 0);
+    l->line_offsets.assign(1, 0);
+    if (nw == 0) {
+      l->img_offsets.assign((size_t)n_images + 1, 0);
+      l->finish();
+      *out = &l.release()->view;
+      return;
+    }
+    static_assert(OCR_LINE_MAX_WORDS == kLineMaxWords, "line grouping limit");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    const size_t q_bytes = (size_t)nw * 64, off_bytes = ((size_t)n_images + 1) * 4, w4 = (size_t)nw * 4;
+    Carve c;
+    const size_t o_q = c.take(q_bytes), o_off = c.take(off_bytes), o_feat = c.take((size_t)nw * kLineFeatBytes), o_link = c.take(2 * w4);
+    const size_t o_ord = c.take(w4), o_fl = c.take(w4), o_gap = c.take((size_t)nw * 8), o_ls = c.take(w4), o_nl = c.take((size_t)n_images * 4);
+    char* sc = static_cast<char*>(det->impl.scratch(1, c.end));
+    OCR_HIP(hipMemcpyAsync(sc + o_q, quads, q_bytes, hipMemcpyHostToDevice, s));
+    OCR_HIP(hipMemcpyAsync(sc + o_off, word_img_offsets, off_bytes, hipMemcpyHostToDevice, s));
+    launch_group_lines(at<const double>(sc, o_q), at<const int32_t>(sc, o_off), n_images, nw, max_words,
+                       LineParams{p.line_tol, p.height_ratio, p.min_cos, p.max_gap}, sc + o_feat, at<int32_t>(sc, o_link),
+                       at<int32_t>(sc, o_ord), at<int32_t>(sc, o_fl), at<double>(sc, o_gap), at<int32_t>(sc, o_ls), at<int32_t>(sc, o_nl), s);
+    std::vector<int32_t> line_start(nw), n_lines(n_images);
+    l->order.resize(nw);
+    l->word_flags.resize(nw);
+    l->gaps.resize(nw);
+    OCR_HIP(hipMemcpyAsync(l->order.data(), sc + o_ord, w4, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(l->word_flags.data(), sc + o_fl, w4, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(l->gaps.data(), sc + o_gap, (size_t)nw * 8, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(line_start.data(), sc + o_ls, w4, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(n_lines.data(), sc + o_nl, (size_t)n_images * 4, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipStreamSynchronize(s));
+    // the kernel leaves the line starts of image b in its own word slice; the CSR over the batch is their concatenation
+    l->line_offsets.clear();
+    for (int b = 0; b < n_images; ++b) {
+      const int w0 = word_img_offsets[b], cnt = word_img_offsets[b + 1] - w0;
+      if (n_lines[b] < 0 || n_lines[b] > cnt || (cnt > 0 && n_lines[b] == 0)) fail(OCR_ERR_INTERNAL, "group_lines: image %d reports %d lines of %d words", b, n_lines[b], cnt);
+      l->line_offsets.insert(l->line_offsets.end(), line_start.begin() + w0, line_start.begin() + w0 + n_lines[b]);
+      l->img_offsets.push_back((int32_t)l->line_offsets.size());
+    }
+    l->line_offsets.push_back(nw);
+    l->finish();
+    *out = &l.release()->view;
+  });
+}
+
+void ocr_lines_free(ocr_lines_t* l) {
+  if (!l) return;
+  delete reinterpret_cast<ocr::LinesOwned*>(reinterpret_cast<char*>(l) - offsetof(ocr::LinesOwned, view));
+}
+
 static std::vector<std::vector<ocr::geom::Pt>> csr_polys(const uint32_t* xy, const int32_t* offsets, int n) {
   std::vector<std::vector<ocr::geom::Pt>> out(n);
   for (int k = 0; k < n; ++k)

@@ -85,6 +85,23 @@ struct PolygonsOwned {
   }
 };
 
+// the library-owned storage behind an ocr_lines_t* (released by ocr_lines_free)
+struct LinesOwned {
+  ocr_lines_t view;
+  std::vector<int32_t> img_offsets, line_offsets, order, word_flags;
+  std::vector<double> gaps;
+  void finish() {
+    view.n_images = (int32_t)img_offsets.size() - 1;
+    view.n_words = (int32_t)order.size();
+    view.n_lines = (int32_t)line_offsets.size() - 1;
+    view.img_offsets = img_offsets.data();
+    view.line_offsets = line_offsets.data();
+    view.order = order.data();
+    view.word_flags = word_flags.data();
+    view.gaps = gaps.data();
+  }
+};
+
 // comm.hip
 class Comm;
 std::vector<uint8_t> pack_shard(const ocr_polygons_t& p);

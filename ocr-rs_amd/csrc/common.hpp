@@ -265,6 +265,19 @@ struct CurveWord {
 void launch_curved_strips(const float* frames_dev, int H, int W, const CurveWord* words_dev, const float* knots_dev,
                           const int32_t* col_word_dev, int height, int total_width, float* atlas_dev, hipStream_t s);
 
+// line grouping (lines.hip; rule: include/ocr_amd.h ocr_group_lines, tests/line_oracle.py).  quads [n_words][8] f64 and img_off
+// [n_images + 1] on the device; no image holds more than kLineMaxWords words (max_words is the largest count).  feat takes
+// kLineFeatBytes per word, link 2 x n_words int32 (right[], left[]).  Results by image slice [img_off[b], img_off[b + 1]): order and
+// gaps by position, flags by word, line_start[img_off[b] + l] the batch-global position where line l of image b starts, n_lines[b].
+constexpr int kLineMaxWords = 4096;
+constexpr size_t kLineFeatBytes = 64;
+struct LineParams {
+  double line_tol, height_ratio, min_cos, max_gap;
+};
+void launch_group_lines(const double* quads_dev, const int32_t* img_off_dev, int n_images, int n_words, int max_words, const LineParams& p,
+                        void* feat_dev, int32_t* link_dev, int32_t* order_dev, int32_t* flags_dev, double* gaps_dev,
+                        int32_t* line_start_dev, int32_t* n_lines_dev, hipStream_t s);
+
 // recognition net (rec_net.hip): conv1 + pool + conv2 + pool on the matrix cores -> feat [n][1024]; fc1 runs as a
 // conv_igemm 1x1 GEMM over the whole batch; fc2 + softmax(f64) + top-1 in one kernel
 struct RecWeights {

@@ -10,6 +10,7 @@
 //   read_words: detected words -> glyphs -> text, the pipeline's segmentation step (README.md:20-26), which the reference never built
 //   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words,
 //     or through curved strips (ocr_plan_curved_strips / ocr_extract_curved_strips), for words that bend
+//   group_lines / read_lines: the words of every page grouped into text lines in reading order (ocr_group_lines), the "output text" step
 #pragma once
 #include <algorithm>
 #include <array>
@@ -355,6 +356,87 @@ inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
     }
   }
   return out;
+}
+
+// ocr_group_lines: quads 8 doubles per word (TL, TR, BR, BL: the quads of ocr_word_strips_t), word_img_offsets [n_images + 1].
+// line l of image b is order[line_offsets[l] .. line_offsets[l + 1]) for l in [img_offsets[b], img_offsets[b + 1]).
+struct Lines {
+  std::vector<int32_t> img_offsets, line_offsets, order, word_flags;
+  std::vector<double> gaps;
+};
+inline Lines group_lines(const text_detection::FuncT& det_net, const std::vector<double>& quads, const std::vector<int32_t>& word_img_offsets,
+                         const ocr_line_params_t* params = nullptr) {
+  if (word_img_offsets.empty() || quads.size() != 8 * (size_t)word_img_offsets.back())
+    throw Error(OCR_ERR_INVALID, "quads do not match the word offsets");
+  ocr_lines_t* l = nullptr;
+  check(ocr_group_lines(det_net.handle(), quads.data(), word_img_offsets.data(), (int)word_img_offsets.size() - 1, params, &l));
+  Lines out;
+  out.img_offsets.assign(l->img_offsets, l->img_offsets + l->n_images + 1);
+  out.line_offsets.assign(l->line_offsets, l->line_offsets + l->n_lines + 1);
+  out.order.assign(l->order, l->order + l->n_words);
+  out.word_flags.assign(l->word_flags, l->word_flags + l->n_words);
+  out.gaps.assign(l->gaps, l->gaps + l->n_words);
+  ocr_lines_free(l);
+  return out;
+}
+
+// One text line: the non-empty word texts joined by one space, the image's polygon indices in reading order, and in front of every
+// word its gap in units of the taller neighbour's height (0 for the first word).
+struct LineReading {
+  std::string text;
+  std::vector<int32_t> word_indices;
+  std::vector<double> gaps;
+};
+// read_words_rectified for the texts, ocr_plan_word_strips for the quads (always: the curved plan carries none, and word order equals
+// polygon order in every reading call), ocr_group_lines for the lines; per image, its lines in reading order.
+inline std::vector<std::vector<LineReading>> read_lines(
+    const text_detection::FuncT& det_net, const char_recognition::Net& rec_net, const Tensor& frames,
+    const text_detection::metrics::PolygonScores& ps, const std::vector<double>& adjust_values,
+    const ocr_line_params_t* line_params = nullptr, const ocr_strip_params_t* strip_params = nullptr,
+    const ocr_segment_params_t* params = nullptr, const ocr_cc_params_t* cc = nullptr, const ocr_mask_params_t* mask = nullptr,
+    const ocr_curve_params_t* curved = nullptr) {
+  const auto words = read_words_rectified(det_net, rec_net, frames, ps, adjust_values, strip_params, params, cc, mask, curved);
+  std::vector<int32_t> img_off{0}, poly_off{0};
+  std::vector<uint32_t> xy;
+  std::vector<double> scores;
+  for (const auto& image : ps.polygons) {
+    for (const auto& poly : image) {
+      for (const auto& v : poly) {
+        xy.push_back(v.first);
+        xy.push_back(v.second);
+      }
+      poly_off.push_back((int32_t)(xy.size() / 2));
+      scores.push_back(0.0);
+    }
+    img_off.push_back((int32_t)scores.size());
+  }
+  const ocr_polygons_t polys{frames.n, (int32_t)scores.size(), (int32_t)(xy.size() / 2), img_off.data(), poly_off.data(), xy.data(),
+                             scores.data()};
+  ocr_word_strips_t* st = nullptr;
+  check(ocr_plan_word_strips(&polys, adjust_values.data(), frames.n, frames.h, frames.w, strip_params, &st));
+  const std::vector<double> quads(st->quads, st->quads + 8 * (size_t)st->n_words);
+  ocr_word_strips_free(st);
+  const Lines lines = group_lines(det_net, quads, img_off, line_params);
+  std::vector<std::vector<LineReading>> out(frames.n);
+  for (int b = 0; b < frames.n; ++b) {
+    for (int l = lines.img_offsets[b]; l < lines.img_offsets[b + 1]; ++l) {
+      LineReading r;
+      for (int p = lines.line_offsets[l]; p < lines.line_offsets[l + 1]; ++p) {
+        const int k = lines.order[p] - img_off[b];
+        const std::string& t = words[b][k].text;
+        if (!t.empty()) r.text += (r.text.empty() ? "" : " ") + t;
+        r.word_indices.push_back(k);
+        r.gaps.push_back(lines.gaps[p]);
+      }
+      out[b].push_back(std::move(r));
+    }
+  }
+  return out;
+}
+inline std::string page_text(const std::vector<LineReading>& lines) {
+  std::string s;
+  for (size_t l = 0; l < lines.size(); ++l) s += (l ? "\n" : "") + lines[l].text;
+  return s;
 }
 
 }  // namespace ocr_rs

@@ -17,8 +17,15 @@ recognition -> output text), composed over the C ABI.
         ocr_plan_curved_strips    every word -> 33 knots of its centreline with normals   (csrc/word_strips.cpp, host)
         ocr_extract_curved_strips every word -> one strip of the atlas, on the device     (csrc/curved_strips.hip)
 
-The segmentation and strip rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
-tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py, tests/strip_oracle.py and tests/curved_strip_oracle.py.
+    read_lines(det_net, rec_net, frames, polygon_scores, adjust_values)
+        read_words_rectified (or read_words) for the texts, then
+        ocr_plan_word_strips      every word -> its oriented rectangle                    (the quads)
+        ocr_group_lines           the words of every page -> text lines in reading order  (csrc/lines.hip)
+    page_text(lines) joins the lines of one image with "\n".
+
+The segmentation, strip and line rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
+tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py, tests/strip_oracle.py, tests/curved_strip_oracle.py and
+tests/line_oracle.py.
 """
 from __future__ import annotations
 
@@ -253,3 +260,45 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
             words.append((text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy()))
         out.append(words)
     return out
+
+
+def read_lines(det_net, rec_net, frames, polygon_scores, adjust_values, line_params=None, rectified=True, **reading_kwargs
+               ) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+    """Reads every detected word of a batch and groups the words of every image into text lines in reading order (ocr_group_lines).
+
+    Arguments as read_words_rectified (rectified=True, the default) or read_words (rectified=False); strip_params, params, cc, mask and
+    curved go to that call unchanged.  line_params: capi.LineParams, a dict of its fields (line_tol, height_ratio, min_cos, max_gap) or
+    None for the defaults.  The quads always come from ocr_plan_word_strips (with strip_params where given): word order equals polygon
+    order in every reading call, and the curved plan carries no quads.
+    Returns per image a list of lines (text, word_indices, gaps): word_indices are the image's polygon indices in reading order (int32),
+    gaps[k] the gap in front of word k of the line in units of the taller neighbour's height (0.0 for the first), text the non-empty
+    word texts joined by one space."""
+    det = _handle(det_net, capi.Detector)
+    if rectified:
+        words = read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, **reading_kwargs)
+    else:
+        if "strip_params" in reading_kwargs or "curved" in reading_kwargs:
+            raise TypeError("read_lines: strip_params and curved belong to rectified=True")
+        words = read_words(det_net, rec_net, frames, polygon_scores, adjust_values, **reading_kwargs)
+    polys = getattr(polygon_scores, "polygons", polygon_scores)
+    n, _, h, w = frames.shape
+    strips = det.plan_word_strips(polys, adjust_values, h, w, reading_kwargs.get("strip_params"), getattr(polygon_scores, "scores", None))
+    lines = det.group_lines(strips.quads, strips.img_offsets, line_params)
+    # one pass over the lines of the batch: slices of the batch's arrays (views), the texts by batch-global word index
+    texts = [t for page in words for t, _, _ in page]
+    order = lines.order.tolist()
+    local = lines.order - np.repeat(strips.img_offsets[:-1], np.diff(strips.img_offsets))[lines.order]
+    img_off, line_off = lines.img_offsets.tolist(), lines.line_offsets.tolist()
+    out = []
+    for b in range(n):
+        page = []
+        for l in range(img_off[b], img_off[b + 1]):
+            p0, p1 = line_off[l], line_off[l + 1]
+            page.append((" ".join(filter(None, [texts[k] for k in order[p0:p1]])), local[p0:p1], lines.gaps[p0:p1]))
+        out.append(page)
+    return out
+
+
+def page_text(lines) -> str:
+    """The lines of one image (an element of read_lines' result) joined with "\n"."""
+    return "\n".join(text for text, _, _ in lines)
