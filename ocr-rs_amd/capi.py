@@ -348,6 +348,8 @@ def test_lib() -> C.CDLL:
         L.ocr_test_winograd43_fragments.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.ocr_test_winograd_run.argtypes = ([C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4 +
                                             [C.c_void_p, C.c_int])
+        L.ocr_test_bf16_trunk_run.argtypes = ([C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] +
+                                              [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 2 + [C.c_int])
         _test_lib = L
     return _test_lib
 
@@ -1381,6 +1383,37 @@ class Detector:
         check(test_lib().ocr_test_winograd_run(self._h, int(form), _ptr(x), n, h, w, cin, _ptr(wg), cout, p(sc), p(bi), p(rs), int(bool(relu)),
                                                int(bool(inplace)), int(num_cus), int(bool(poison)), _ptr(io), int(guard)))
         return io[:px].reshape(n, h, w, cout), io[px:]
+
+    def debug_bf16_trunk_run(self, form, x_nhwc, wgt_ohwi, scale=None, bias=None, residual=None, relu=False, stride=1, up_residual=None, want_out=True,
+                             wgt2=None, scale2=None, bias2=None, num_cus=0, guard=64, poison=False, sentinel=-7.0, claim=None):
+        """One launch of the bf16 precision's trunk on caller data (test hook): form 0 conv3x3_bf16_c64 (grid 2 x num_cus), 1 basic_block_bf16_c64
+        (conv (wgt, scale, bias) + ReLU, conv (wgt2, scale2, bias2), + x, ReLU; grid num_cus), 2 conv_igemm with bf16 operands and results
+        (kernel 1x1 or 3x3 by wgt's shape, stride 1 or 2; with up_residual [N][Ho / 2][Wo / 2][Cout] the second output is value + its nearest
+        upsample, and want_out=False stores that sum only).  Arrays are f32 and are rounded to bf16 on the way in.  poison: the regions around
+        the source inside its allocation hold NaN instead of zeros.  Returns (out or None, out2 or None, guard): N x Ho x Wo x Cout f32 each, and
+        the `guard` rows of Cout elements behind every output, one after the other, which went to the device as `sentinel`.  claim: an (N, H, W)
+        handed to the hook instead of x's own, for shapes the launchers refuse by their arguments alone - the outputs are not allocated."""
+        f = lambda a, shape=None: None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).reshape(shape or np.shape(a)))
+        x, wg = f(x_nhwc), f(wgt_ohwi)
+        n, h, w, cin = x.shape
+        cout, taps = wg.shape[0], wg.shape[1]
+        ks = {1: 1, 9: 3}[taps]
+        assert wg.shape == (cout, taps, cin), wg.shape
+        pad = (ks - 1) // 2
+        ho, wo = (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
+        px = n * ho * wo
+        if claim is not None:
+            n, h, w = claim
+            px = 0
+        io = np.full((px + guard, cout), sentinel, np.float32) if want_out else None
+        io2 = np.full((px + guard, cout), sentinel, np.float32) if up_residual is not None else None
+        p = lambda a: None if a is None else _ptr(a)
+        ops = [f(scale), f(bias), f(residual, (-1, cout)), f(up_residual, (-1, cout)), f(wgt2), f(scale2), f(bias2)]
+        check(test_lib().ocr_test_bf16_trunk_run(self._h, int(form), _ptr(x), n, h, w, cin, _ptr(wg), cout, ks, int(stride), p(ops[0]), p(ops[1]), p(ops[2]),
+                                                 p(ops[3]), int(bool(relu)), p(ops[4]), p(ops[5]), p(ops[6]), int(num_cus), int(bool(poison)), p(io), p(io2),
+                                                 int(guard)))
+        outs = [None if a is None else a[:px].reshape(-1, ho, wo, cout) for a in (io, io2)]
+        return outs[0], outs[1], np.concatenate([a[px:] for a in (io, io2) if a is not None])
 
     def debug_box_scores(self, pred_hw: np.ndarray, polys):
         """Test hook: raw (sum, count) of the GPU box-score kernel for given polygons."""

@@ -1346,3 +1346,100 @@ int ocr_test_winograd_run(ocr_det_t* det, int form, const float* x, int n, int h
 }
 
 }  // extern "C"
+
+// ---- the trunk convs of the bf16 precision: conv3x3_bf16_c64.hip, basic_block_bf16_c64.hip and conv_igemm with bf16 operands ----
+extern "C" {
+
+// one launch of the bf16 trunk on caller data.  form: 0 = launch_conv3x3_bf16_c64 (3x3 s1 64 -> 64; grid 2 x num_cus, 0 = 256 CUs);
+// 1 = launch_basic_block_bf16_c64 (conv (wgt, scale, bias) + ReLU, conv (wgt2, scale2, bias2), + x, ReLU as one launch; grid num_cus);
+// 2 = launch_conv_igemm with in_bf16 = out_bf16 = 1, the descriptor ocr_test_conv_run builds (ks 1 | 3, stride 1 | 2, residual,
+// up_residual [n][ho / 2][wo / 2][cout] with out2 = the lateral's top-down sum; out_io == null stores the sum only).  All host arrays are f32,
+// rounded to bf16 (nearest even) on the way in and widened on the way out.  x: [n][h][w][cin]; wgt: [cout][ks ks][cin].
+// out_io / out2_io: [n ho wo + guard_rows][cout], uploaded before the launch and downloaded whole after it: what the caller put into the guard
+// rows comes back only if no launch wrote there.  The source sits inside one allocation with `lead` >= (w + 1) cin elements in front of it and
+// as many behind it - zeros, or with poison != 0 bf16 quiet NaN: the kernels take their zero padding from buffer offsets outside
+// [0, tensor bytes), so these regions are what a failed mask or a wrapped offset would read.  residual and up_residual are buffers of their own.
+// A tensor of 2^31 bytes or more is handed to the launcher before anything is read or allocated, without operands: it must refuse by its shape
+int ocr_test_bf16_trunk_run(ocr_det_t* det, int form, const float* x, int n, int h, int w, int cin, const float* wgt, int cout, int ks, int stride,
+                            const float* scale, const float* bias, const float* residual, const float* up_residual, int relu, const float* wgt2,
+                            const float* scale2, const float* bias2, int num_cus, int poison, float* out_io, float* out2_io, int guard_rows) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !x || !wgt) fail(OCR_ERR_INVALID, "null argument");
+    if (form < 0 || form > 2 || n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || guard_rows < 0 || num_cus < 0 || (ks != 1 && ks != 3) ||
+        (stride != 1 && stride != 2))
+      fail(OCR_ERR_INVALID, "bf16 trunk hook: bad form, shape, kernel size or stride");
+    if (form != 2 && (cin != 64 || cout != 64 || ks != 3 || stride != 1 || up_residual || out2_io || !out_io))
+      fail(OCR_ERR_INVALID, "bf16 trunk hook: forms 0 and 1 are the 3x3 s1 64 -> 64 kernels with one output");
+    if (form == 1 && (!wgt2 || residual || !relu)) fail(OCR_ERR_INVALID, "bf16 trunk hook: the block takes two convs, adds x itself and always ends in ReLU");
+    if (form != 1 && (wgt2 || scale2 || bias2)) fail(OCR_ERR_INVALID, "bf16 trunk hook: a second conv exists in form 1 only");
+    if (!out_io && !out2_io) fail(OCR_ERR_INVALID, "bf16 trunk hook: no output");
+    if (out2_io && !up_residual) fail(OCR_ERR_INVALID, "bf16 trunk hook: out2 is the sum with up_residual");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    const int pad = (ks - 1) / 2, cus = num_cus > 0 ? num_cus : 256;
+    const int ho = (h + 2 * pad - ks) / stride + 1, wo = (w + 2 * pad - ks) / stride + 1;
+    ConvDesc d{};
+    d.in_bf16 = d.out_bf16 = 1;
+    d.src_mode = SRC_PLAIN;
+    d.N = n; d.Hin = h; d.Win = w; d.Cin = cin; d.Ho = ho; d.Wo = wo; d.Cout = cout;
+    d.ks = ks; d.stride = stride; d.pad = pad;
+    d.relu = relu ? 1 : 0; d.store_mode = STORE_NHWC; d.name = "test_bf16_trunk";
+    const unsigned long long in_bytes = 2ull * (unsigned long long)n * h * w * cin;
+    if (in_bytes >= (1ull << 31)) {
+      if (form == 0) launch_conv3x3_bf16_c64(nullptr, nullptr, nullptr, nullptr, nullptr, d.relu, nullptr, n, h, w, cus, s);
+      else if (form == 1) launch_basic_block_bf16_c64(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, h, w, cus, s);
+      else {
+        d.src_bytes = in_bytes;
+        launch_conv_igemm(d, s);
+      }
+      fail(OCR_ERR_INTERNAL, "bf16 trunk hook: the launcher took a tensor of %llu bytes", in_bytes);
+    }
+    HookBuffers b;
+    const size_t px_out = (size_t)n * ho * wo, in_e = (size_t)n * h * w * cin, out_e = (px_out + guard_rows) * cout;
+    const size_t lead = (((size_t)(w + 1) * cin + 1023) / 1024) * 1024;
+    std::vector<uint16_t> img(lead + in_e + lead, poison ? (uint16_t)0x7fc0 : (uint16_t)0);
+    for (size_t i = 0; i < in_e; ++i) img[lead + i] = hook_bf16_bits(x[i]);
+    const char* d_x = static_cast<const char*>(b.u16(img)) + lead * 2;
+    const float* d_sc = scale ? b.f32(scale, cout) : nullptr;
+    const float* d_bi = bias ? b.f32(bias, cout) : nullptr;
+    void* d_y = out_io ? b.as_bf16(out_io, out_e) : nullptr;
+    void* d_y2 = out2_io ? b.as_bf16(out2_io, out_e) : nullptr;
+    const void* d_res = residual ? b.as_bf16(residual, px_out * cout) : nullptr;
+    if (form == 0) {
+      launch_conv3x3_bf16_c64(d_x, b.u16(conv3x3_bf16_c64_fragments(wgt)), d_sc, d_bi, d_res, d.relu, d_y, n, h, w, cus, s);
+    } else if (form == 1) {
+      const float* d_sc2 = scale2 ? b.f32(scale2, cout) : nullptr;
+      const float* d_bi2 = bias2 ? b.f32(bias2, cout) : nullptr;
+      launch_basic_block_bf16_c64(d_x, b.u16(conv3x3_bf16_c64_fragments(wgt)), d_sc, d_bi, b.u16(conv3x3_bf16_c64_fragments(wgt2)), d_sc2, d_bi2, d_y,
+                                  n, h, w, cus, s);
+    } else {
+      const size_t w_e = (size_t)cout * ks * ks * cin;
+      d.src[0] = d_x;
+      d.src_bytes = in_e * 2;
+      d.wgt = b.as_bf16(wgt, w_e);
+      d.wgt_bytes = w_e * 2;
+      d.scale = d_sc;
+      d.bias = d_bi;
+      d.residual = d_res;
+      d.up_residual = up_residual ? b.as_bf16(up_residual, (size_t)n * (ho / 2) * (wo / 2) * cout) : nullptr;
+      d.out = d_y;
+      d.out2 = d_y2;
+      launch_conv_igemm(d, s);
+    }
+    OCR_HIP(hipStreamSynchronize(s));
+    auto down = [&](float* dst, const void* dev) {
+      if (!dst) return;
+      std::vector<uint16_t> t(out_e);
+      OCR_HIP(hipMemcpy(t.data(), dev, out_e * 2, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < out_e; ++i) {
+        const uint32_t u = (uint32_t)t[i] << 16;
+        std::memcpy(&dst[i], &u, 4);
+      }
+    };
+    down(out_io, d_y);
+    down(out2_io, d_y2);
+  });
+}
+
+}  // extern "C"
