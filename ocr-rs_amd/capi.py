@@ -1882,6 +1882,30 @@ def device_candidates(contours, h: int, w: int, max_pts: int = 1 << 18, max_poly
     return out, boxes
 
 
+def device_candidates_batch(images, h: int, w: int, cap: int, maxc: int, max_jobs: int, max_pts: int, scratch_fill: int = 0, guard: int = 0,
+                            poison: int = 0x5A5AC3C3):
+    """candidates.hip on a batch laid out as the device tracer leaves it, nothing interpreted (ocr_test_candidates_batch).  images: a
+    list of (status, contours), contours lists of (x, y); image i's points sit at i * cap, its starts row is maxc + 1 long.  The whole
+    scratch is filled with the byte scratch_fill, the lists and `guard` jobs / points behind them with the word poison.  Returns
+    (tot [n][2], totals [3], jobs [max_jobs + guard][7], points [max_pts + guard][2]) as int32 arrays."""
+    L = test_lib()
+    L.ocr_test_candidates_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    n = len(images)
+    status = np.asarray([st for st, _ in images] or [0], np.int32)
+    ncs = np.asarray([len(cs) for _, cs in images] or [0], np.int32)
+    lens = np.asarray([len(c) for _, cs in images for c in cs] or [0], np.int32)
+    parts = [np.asarray(c, np.int32).reshape(-1) for _, cs in images for c in cs if len(c)]
+    flat = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(2, np.int32), dtype=np.int32)
+    tot = np.empty((max(n, 1), 2), np.int32)
+    totals = np.empty(3, np.int32)
+    jobs = np.empty((max_jobs + guard, 7), np.int32)
+    pts = np.empty((max_pts + guard, 2), np.int32)
+    check(L.ocr_test_candidates_batch(n, h, w, _ptr(status), _ptr(ncs), _ptr(lens), _ptr(flat), cap, maxc, max_jobs, max_pts, scratch_fill, guard, poison,
+                                      _ptr(tot), _ptr(totals), _ptr(jobs), _ptr(pts)))
+    return tot, totals, jobs, pts
+
+
 def host_expand_polygon(pts: Sequence[Tuple[int, int]], factor: float = 2.0):
     a = np.asarray(pts, dtype=np.int32).reshape(-1)
     out = np.empty(8192, np.int32)

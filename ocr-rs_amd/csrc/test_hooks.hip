@@ -155,6 +155,70 @@ int ocr_test_device_candidates(const int32_t* xy, const int32_t* lens, int nc, i
     *n_polys = totals[0];
   });
 }
+// candidates.hip on a BATCH laid out as the device tracer leaves it, with nothing interpreted: per image the tracer status (header
+// word 2) and its contour count, flat contour lengths and flat (x, y); image i's points at i * cap, its starts row maxc + 1 long with
+// entries 0 .. nc written (the tracer writes no more).  max_jobs / max_pts are the caller's, too small ones included.  Before the one
+// launch the whole candidates scratch is filled with the byte scratch_fill and the job list, the point list, `guard` further jobs and
+// points behind each, tot and totals with the word `poison`.  Out, raw: tot [n][2], totals [3], (max_jobs + guard) jobs of 7 ints,
+// (max_pts + guard) points of 2 ints.
+int ocr_test_candidates_batch(int n, int h, int w, const int32_t* status, const int32_t* ncs, const int32_t* lens, const int32_t* xy, int cap, int maxc,
+                              int max_jobs, int max_pts, int scratch_fill, int guard_n, uint32_t poison, int32_t* tot_out, int32_t* totals_out,
+                              int32_t* jobs_out, int32_t* pts_out) {
+  return guard([&] {
+    static_assert(sizeof(ocr::BoxScoreJob) == 28, "the hook returns a job as 7 ints");
+    if (n <= 0 || n > 65535 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || cap < 64 || maxc < 1 || max_jobs < 0 || max_pts < 0 || guard_n < 0 ||
+        scratch_fill < 0 || scratch_fill > 255 || max_jobs > (1 << 24) || max_pts > (1 << 26) || guard_n > (1 << 20))
+      ocr::fail(OCR_ERR_INVALID, "candidates batch: bad shape");
+    std::vector<uint32_t> pts((size_t)n * cap, 0u);
+    std::vector<int> starts((size_t)n * (maxc + 1), 0), hdr((size_t)n * 4, 0);
+    size_t c_at = 0, p_at = 0;
+    for (int b = 0; b < n; ++b) {
+      const int nc = ncs[b];
+      if (nc < 0 || nc > maxc) ocr::fail(OCR_ERR_INVALID, "candidates batch: image %d has %d contours, maxc %d", b, nc, maxc);
+      size_t at = 0;
+      for (int c = 0; c < nc; ++c, ++c_at) {
+        const int len = lens[c_at];
+        if (len < 0 || at + (size_t)len > (size_t)cap) ocr::fail(OCR_ERR_INVALID, "candidates batch: image %d holds more than cap = %d points", b, cap);
+        starts[(size_t)b * (maxc + 1) + c] = (int)at;
+        for (int i = 0; i < len; ++i, ++at, ++p_at) {
+          const int32_t x = xy[2 * p_at], y = xy[2 * p_at + 1];
+          if (x < 0 || x > 65535 || y < 0 || y > 65535) ocr::fail(OCR_ERR_INVALID, "candidates batch: coordinate outside 0..65535");
+          pts[(size_t)b * cap + at] = ((uint32_t)y << 16) | (uint32_t)x;
+        }
+      }
+      starts[(size_t)b * (maxc + 1) + nc] = (int)at;
+      hdr[4 * (size_t)b] = nc;
+      hdr[4 * (size_t)b + 1] = (int)at;
+      hdr[4 * (size_t)b + 2] = status[b];
+    }
+    const size_t sb = ocr::candidates_scratch_bytes(n, cap, maxc);
+    const size_t n_jobs = (size_t)max_jobs + guard_n, n_pts = (size_t)max_pts + guard_n;
+    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t o_pts = al(hdr.size() * 4), o_st = o_pts + al(pts.size() * 4), o_sc = o_st + al(starts.size() * 4), o_jobs = o_sc + al(sb),
+                 o_xy = o_jobs + al(n_jobs * sizeof(ocr::BoxScoreJob) + 4), o_tot = o_xy + al(n_pts * 8 + 4), o_hd = o_tot + al((size_t)n * 8), end = o_hd + 256;
+    char* d = nullptr;
+    OCR_HIP(hipMalloc(reinterpret_cast<void**>(&d), end));
+    try {
+      OCR_HIP(hipMemcpy(d, hdr.data(), hdr.size() * 4, hipMemcpyHostToDevice));
+      OCR_HIP(hipMemcpy(d + o_pts, pts.data(), pts.size() * 4, hipMemcpyHostToDevice));
+      OCR_HIP(hipMemcpy(d + o_st, starts.data(), starts.size() * 4, hipMemcpyHostToDevice));
+      OCR_HIP(hipMemset(d + o_sc, scratch_fill, al(sb)));
+      OCR_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d + o_jobs), (int)poison, (end - o_jobs) / 4));   // jobs, points, guards, tot, totals
+      ocr::launch_candidates(reinterpret_cast<const int*>(d), reinterpret_cast<const uint32_t*>(d + o_pts), cap, reinterpret_cast<const int*>(d + o_st), maxc, n, h, w,
+                             d + o_sc, reinterpret_cast<ocr::BoxScoreJob*>(d + o_jobs), max_jobs, reinterpret_cast<int32_t*>(d + o_xy), max_pts,
+                             reinterpret_cast<int*>(d + o_tot), reinterpret_cast<int*>(d + o_hd), nullptr);
+      OCR_HIP(hipDeviceSynchronize());
+      OCR_HIP(hipMemcpy(tot_out, d + o_tot, (size_t)n * 8, hipMemcpyDeviceToHost));
+      OCR_HIP(hipMemcpy(totals_out, d + o_hd, 12, hipMemcpyDeviceToHost));
+      if (n_jobs) OCR_HIP(hipMemcpy(jobs_out, d + o_jobs, n_jobs * sizeof(ocr::BoxScoreJob), hipMemcpyDeviceToHost));
+      if (n_pts) OCR_HIP(hipMemcpy(pts_out, d + o_xy, n_pts * 8, hipMemcpyDeviceToHost));
+    } catch (...) {
+      (void)hipFree(d);
+      throw;
+    }
+    (void)hipFree(d);
+  });
+}
 // the host tracer's raw contours, for the same comparison
 int ocr_test_host_contours(const uint8_t* bitmap01, int h, int w, int32_t* xy_out, int32_t* counts_out, int max_pts, int max_polys, int* n_polys) {
   return guard([&] {

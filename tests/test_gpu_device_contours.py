@@ -201,13 +201,16 @@ def test_pipelined_calls_with_pretraced_contours_return_the_same_polygons():
 
 def test_device_chain_overflow_takes_the_host_path():
     """More candidates than the device job list holds (1 024 per image of the batch): the chain reports the overflow with ZERO jobs - so that
-    box scores and unclip, which walk the list by that count, touch nothing - and the host path takes the batch: same polygons."""
+    box scores and unclip, which walk the list by that count, touch nothing - and the host path takes the batch: same polygons.  The
+    boxes are 8 x 7 pixels, 26 contour points each: the 1 200 of a map stay below the tracer's 32 768 points per image (9 x 7 boxes did
+    not, and the TRACER gave the map up before the chain saw it), so that it is the job list that overflows - ocr_det_post_stats says
+    which path ran."""
     m = np.zeros((1, 1, 640, 640), np.float32)
     k = 0
     for gy in range(8, 632, 16):
         for gx in range(8, 632, 20):
             if k < 1200:
-                m[0, 0, gy:gy + 7, gx:gx + 9] = 0.9
+                m[0, 0, gy:gy + 7, gx:gx + 8] = 0.9
                 k += 1
     blob = W.pack_blob(W.make_det_weights(0))
     host = capi.Detector(blob, 0, options="device_contours=0;device_unclip=0")
@@ -215,13 +218,19 @@ def test_device_chain_overflow_takes_the_host_path():
     adj = np.ones((1, 2))
     want = _post(host, m, adj)
     got = _post(dev, m, adj)
+    st1 = dev.post_stats()
     assert len(want[0][0]) == 1200
     assert got[0] == want[0] and got[1] == want[1]
+    assert st1["images_device_chain"] == 0 and st1["images_host_traced"] == 1, st1   # the host path took the image
     # ... and a batch of two such maps with room for both (2 048 jobs) stays on the device and agrees as well
     m2 = np.concatenate([m, m])
     m2[1, 0, 300:, :] = 0.0
     want2 = _post(host, m2, np.ones((2, 2)))
     got2 = _post(dev, m2, np.ones((2, 2)))
+    st2 = dev.post_stats()
     assert got2[0] == want2[0] and got2[1] == want2[1]
+    # the device chain kept both (the counters are cumulative) - so the tracer does take the 1 200-box map, and what handed it to the host
+    # above was the chain's overflow
+    assert st2["images_device_chain"] == 2 and st2["images_host_traced"] == 1, st2
     host.close()
     dev.close()
