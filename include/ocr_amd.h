@@ -746,6 +746,75 @@ int ocr_ctc_greedy_decode(ocr_rec_t* rec, const float* logits, int n, int t, int
 int ocr_ctc_beam_decode(ocr_rec_t* rec, const float* logits, int n, int t, int c, int blank, int beam_width, int mem_kind,
                         int32_t* labels, int32_t* lengths, double* scores);
 
+/* EXTENSION - lexicon matching: the glyphs of a word read as a whole against a word list (BUILD-DEFINED, like the glyph, strip and
+ * line rules; the reference has no counterpart).  Three steps: glyph costs from logits, a lexicon uploaded once, the match.
+ *
+ * Glyph costs.  logits n x 62 f32 (what ocr_rec_forward / ocr_rec_classify_async write) -> costs n x 62 f32, the negative log-softmax
+ * computed in f64: for row i, m = max_c x[c], lse = m + log(sum_c exp((double)x[c] - m)) with the sum taken in class order,
+ * cost[c] = (float)max(lse - (double)x[c], 0.0).  The device's f64 exp and log are within a few ulp of the correctly rounded ones, so a
+ * cost is within one f32 ulp of the exact value (tests/test_gpu_lexicon.py states the bar).  A NaN or +-inf logit is OCR_ERR_INVALID
+ * (the message names the first such row; the costs are then unspecified).  n = 0 does nothing.  On the handle's stream, blocking;
+ * mem_kind covers both buffers.  One wave per row (csrc/lexicon.hip). */
+int ocr_rec_glyph_costs(ocr_rec_t* rec, const float* logits, int n, float* costs, int mem_kind);
+
+/* The lexicon.  Entry k is bytes[offsets[k] .. offsets[k+1]), every byte one of the alphabet (ocr_rec_alphabet), 1..OCR_LEX_MAX_LEN
+ * bytes per entry, 1..OCR_LEX_MAX_ENTRIES entries, offsets [n_entries+1] starting at 0 and not decreasing; duplicates are legal.
+ * Anything else is OCR_ERR_INVALID and the message names the first offending entry.  The entries are uploaded once to the recogniser's
+ * GPU, sorted by (length, index) with the caller's index beside each, four class indices per 32-bit word and the words of one
+ * position of all entries contiguous; results always name the caller's entry index.  The lexicon is bound to that GPU: a match
+ * through a recogniser of another device is OCR_ERR_INVALID.  Destroying waits for the work queued on its GPU. */
+typedef struct ocr_lexicon ocr_lexicon_t;
+#define OCR_LEX_MAX_LEN 32        /* characters per entry, and glyphs per matched word */
+#define OCR_LEX_MAX_ENTRIES (1 << 22)
+int  ocr_lexicon_create(ocr_rec_t* rec, const char* bytes, const int32_t* offsets, int n_entries, ocr_lexicon_t** out);
+int  ocr_lexicon_size(const ocr_lexicon_t* lex, int32_t* n_entries);
+void ocr_lexicon_destroy(ocr_lexicon_t* lex);
+
+/* The match.  costs n_glyphs x 62 f32 in mem_kind memory (ocr_rec_glyph_costs), word_offsets [n_words+1] in host memory (the
+ * word_offsets of an ocr_glyphs_t): word w owns the glyph rows [word_offsets[w], word_offsets[w+1]).
+ * Rule.  All arithmetic is f64, every operation rounded separately, adds and mins only.  For word w with glyph rows r_0..r_(G-1) and
+ * entry e with classes c_0..c_(M-1):
+ *   s(i, j) = (double)cost[r_i][c_j]; with fold_case = 1 the min of that and the same for the other-case twin of c_j (the twin of
+ *     class c < 26 is c + 26, of 26 <= c < 52 it is c - 26, digits have none).
+ *   D[0][0] = 0;  D[i][0] = D[i-1][0] + del_cost;  D[0][j] = D[0][j-1] + ins_cost;
+ *   D[i][j] = min(D[i-1][j-1] + s(i-1, j-1), min(D[i-1][j] + del_cost, D[i][j-1] + ins_cost));  cost(w, e) = D[G][M]: the full table.
+ *   ins_cost pays for a lexicon character with no glyph (a missed glyph), del_cost for a glyph with no lexicon character.
+ * Candidates of w are the entries with |M - G| <= max_len_diff; n_candidates[w] is their number.  word_flags[w]: 1 for G = 0, 2 for
+ * G > OCR_LEX_MAX_LEN - such a word has no candidates and gets no other flag -, else 4 when no entry has an admissible length.
+ * Output of w: the first top_k candidates by (cost ascending, entry index ascending); slots past the candidates hold -1 and +inf.
+ * The key is a total order, so the result does not depend on how the kernel chunks the list.
+ * raw_costs[w] is the cost of the greedy reading: starting from 0.0, min_c (double)cost[r_i][c] added in glyph order (0.0 for a word
+ * without glyphs; a word of more than 32 glyphs is summed like any other).
+ * OCR_ERR_INVALID for a null pointer (params == NULL -> the defaults; costs may be NULL when n_glyphs = 0), a bad mem_kind, offsets
+ * that do not start at 0, decrease or do not end at n_glyphs, a parameter out of range or a nonzero reserved field, a lexicon of
+ * another device, and a cost that is NaN, +-inf or negative (found on the device in the same pass; the message names the first such
+ * word).  The handle stays usable.  n_words = 0 launches nothing and returns an empty block.  The call runs on the recogniser's
+ * stream behind what is queued there, and blocks.  Oracle: tests/lexicon_oracle.py; kernels: csrc/lexicon.hip (grid over word x
+ * lexicon chunk, the word's cost table in LDS, one entry per lane with the DP column in registers, per-lane best-k, workgroup
+ * merge, merge across chunks). */
+typedef struct ocr_lexicon_params {
+  double  ins_cost;      /* >= 0, finite; default 4.0: a lexicon character with no glyph (a missed glyph)  */
+  double  del_cost;      /* >= 0, finite; default 4.0: a glyph with no lexicon character (a spurious glyph) */
+  int32_t max_len_diff;  /* 0..8, default 2 */
+  int32_t fold_case;     /* 0 | 1, default 1 */
+  int32_t top_k;         /* 1..8, default 1 */
+  int32_t reserved[3];   /* must be 0 */
+} ocr_lexicon_params_t;
+typedef struct ocr_lexicon_matches {
+  int32_t n_words, top_k;
+  const int32_t* entries;       /* [n_words*top_k] caller's entry index, -1 past the candidates */
+  const double*  costs;         /* [n_words*top_k] +inf past the candidates                     */
+  const double*  raw_costs;     /* [n_words]                                                    */
+  const int32_t* n_candidates;  /* [n_words]                                                    */
+  const int32_t* word_flags;    /* [n_words] 1 no glyphs, 2 more than 32 glyphs, 4 no entry of an admissible length */
+} ocr_lexicon_matches_t;
+void ocr_lexicon_default_params(ocr_lexicon_params_t* p);
+/* *out: ocr_lexicon_matches_free. */
+int  ocr_lexicon_match(ocr_rec_t* rec, const ocr_lexicon_t* lex, const float* costs, int n_glyphs, int mem_kind,
+                       const int32_t* word_offsets, int n_words, const ocr_lexicon_params_t* params,
+                       ocr_lexicon_matches_t** out);
+void ocr_lexicon_matches_free(ocr_lexicon_matches_t* m);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU exchange.  Frames and crops are independent (eval-mode batch norm), so a batch shards over the GPUs of
  * a node with no data-path collective: one process (or thread) per GPU, each with its own detector / recogniser

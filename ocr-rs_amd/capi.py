@@ -38,6 +38,8 @@ EXPORTS = [
     "ocr_evaluate_image", "ocr_combine_results",
     "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_set_stream", "ocr_rec_set_options", "ocr_rec_synchronize",
     "ocr_rec_forward", "ocr_rec_classify_async", "ocr_rec_classify_profile", "ocr_rec_classify", "ocr_rec_alphabet", "ocr_ctc_greedy_decode",
+    "ocr_rec_glyph_costs", "ocr_lexicon_create", "ocr_lexicon_size", "ocr_lexicon_destroy", "ocr_lexicon_default_params", "ocr_lexicon_match",
+    "ocr_lexicon_matches_free",
     "ocr_ctc_beam_decode",
     "ocr_comm_unique_id", "ocr_comm_rccl_version", "ocr_comm_create", "ocr_comm_destroy",
     "ocr_comm_all_gather_polygons", "ocr_comm_all_gather_labels",
@@ -134,6 +136,23 @@ class LinesBlock(C.Structure):
 
 
 LINE_MAX_WORDS = 4096
+
+
+class LexiconParams(C.Structure):
+    """ocr_lexicon_params_t."""
+    _fields_ = [("ins_cost", C.c_double), ("del_cost", C.c_double), ("max_len_diff", C.c_int32), ("fold_case", C.c_int32),
+                ("top_k", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class LexiconMatchesBlock(C.Structure):
+    """ocr_lexicon_matches_t."""
+    _fields_ = [("n_words", C.c_int32), ("top_k", C.c_int32), ("entries", C.POINTER(C.c_int32)), ("costs", C.POINTER(C.c_double)),
+                ("raw_costs", C.POINTER(C.c_double)), ("n_candidates", C.POINTER(C.c_int32)), ("word_flags", C.POINTER(C.c_int32))]
+
+
+LEX_MAX_LEN = 32
+LEX_MAX_ENTRIES = 1 << 22
+LEX_CHUNK = 256   # entries per pass of a match workgroup (csrc/lexicon_host.hpp kLexChunk): lexicon sizes around it change the grid
 
 _lib = None
 _hip_shared = False
@@ -273,6 +292,17 @@ def lib() -> C.CDLL:
         L.ocr_group_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LineParams), C.POINTER(C.POINTER(LinesBlock))]
         L.ocr_lines_free.argtypes = [C.POINTER(LinesBlock)]
         L.ocr_lines_free.restype = None
+        L.ocr_rec_glyph_costs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.ocr_lexicon_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.ocr_lexicon_size.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.ocr_lexicon_destroy.argtypes = [C.c_void_p]
+        L.ocr_lexicon_destroy.restype = None
+        L.ocr_lexicon_default_params.argtypes = [C.POINTER(LexiconParams)]
+        L.ocr_lexicon_default_params.restype = None
+        L.ocr_lexicon_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(LexiconParams),
+                                        C.POINTER(C.POINTER(LexiconMatchesBlock))]
+        L.ocr_lexicon_matches_free.argtypes = [C.POINTER(LexiconMatchesBlock)]
+        L.ocr_lexicon_matches_free.restype = None
         L.ocr_rec_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_rec_destroy.argtypes = [C.c_void_p]
         L.ocr_rec_destroy.restype = None
@@ -824,6 +854,117 @@ class Lines:
             p0, p1 = int(self.line_offsets[l]), int(self.line_offsets[l + 1])
             out.append((self.order[p0:p1].copy(), self.gaps[p0:p1].copy()))
         return out
+
+
+def lexicon_params(**fields) -> LexiconParams:
+    """ocr_lexicon_default_params with the given fields overridden (ins_cost, del_cost, max_len_diff, fold_case, top_k)."""
+    p = LexiconParams()
+    lib().ocr_lexicon_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k == "reserved":
+            p.reserved[0], p.reserved[1], p.reserved[2] = (int(x) for x in v)
+        elif k in ("ins_cost", "del_cost"):
+            setattr(p, k, float(v))
+        elif k in ("max_len_diff", "fold_case", "top_k"):
+            setattr(p, k, int(v))
+        else:
+            raise TypeError(f"unknown lexicon parameter {k!r}")
+    return p
+
+
+def _as_lexicon_params(params) -> Optional[LexiconParams]:
+    if params is None or isinstance(params, LexiconParams):
+        return params
+    return lexicon_params(**params)
+
+
+class LexiconMatches:
+    """The arrays of an ocr_lexicon_matches_t, copied into numpy: entries n_words x top_k int32 (the caller's entry index, -1 past the
+    candidates), costs n_words x top_k f64 (+inf past the candidates), raw_costs [n_words] f64 (the greedy reading), n_candidates
+    [n_words], word_flags [n_words] (1 no glyphs, 2 more than 32 glyphs, 4 no entry of an admissible length)."""
+
+    def __init__(self, entries, costs, raw_costs, n_candidates, word_flags):
+        self.entries = np.ascontiguousarray(entries, dtype=np.int32)
+        self.costs = np.ascontiguousarray(costs, dtype=np.float64)
+        self.raw_costs = np.ascontiguousarray(raw_costs, dtype=np.float64)
+        self.n_candidates = np.ascontiguousarray(n_candidates, dtype=np.int32)
+        self.word_flags = np.ascontiguousarray(word_flags, dtype=np.int32)
+
+    @property
+    def n_words(self) -> int:
+        return self.entries.shape[0]
+
+    @property
+    def top_k(self) -> int:
+        return self.entries.shape[1]
+
+    @staticmethod
+    def from_block(mp) -> "LexiconMatches":
+        s = mp.contents
+        nw, k = s.n_words, s.top_k
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return LexiconMatches(arr(s.entries, nw * k, np.int32).reshape(nw, k), arr(s.costs, nw * k, np.float64).reshape(nw, k),
+                              arr(s.raw_costs, nw, np.float64), arr(s.n_candidates, nw, np.int32), arr(s.word_flags, nw, np.int32))
+
+
+class Lexicon:
+    """Owner of an ocr_lexicon_t: a word list over the recogniser's alphabet, uploaded once to the recogniser's GPU and resident there
+    until close() (or the end of a `with` block).  words keeps the caller's list: results name its indices."""
+
+    def __init__(self, rec: "Recognizer", words: Sequence[str]):
+        self._h = C.c_void_p()
+        self.words = list(words)
+        raw = [w.encode("latin-1", "replace") if isinstance(w, str) else bytes(w) for w in self.words]
+        offsets = np.zeros(len(raw) + 1, np.int64)
+        offsets[1:] = np.cumsum(np.array([len(b) for b in raw], np.int64))
+        if offsets[-1] > 0x7FFFFFFF:
+            raise OcrError(1, "lexicon: more than 2^31 bytes")
+        self._create(rec, b"".join(raw), offsets.astype(np.int32), len(raw))
+
+    def _create(self, rec, blob: bytes, offsets: np.ndarray, n: int) -> None:
+        buf = np.frombuffer(blob, np.uint8) if blob else np.zeros(1, np.uint8)
+        check(lib().ocr_lexicon_create(rec._h, _ptr(buf), _ptr(offsets), n, C.byref(self._h)))
+
+    @classmethod
+    def from_bytes(cls, rec: "Recognizer", blob: bytes, offsets, n_entries: Optional[int] = None) -> "Lexicon":
+        """The C call's own arguments: entry k is blob[offsets[k]:offsets[k + 1]] (nothing is checked here)."""
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        n = len(off) - 1 if n_entries is None else int(n_entries)
+        self.words = [blob[int(off[k]):int(off[k + 1])].decode("latin-1") for k in range(max(min(n, len(off) - 1), 0))]
+        self._create(rec, blob, off, n)
+        return self
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise OcrError(1, "lexicon already closed")
+        return self._h
+
+    def __len__(self) -> int:
+        n = C.c_int32(0)
+        check(lib().ocr_lexicon_size(self.handle, C.byref(n)))
+        return n.value
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().ocr_lexicon_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class HostBuffer:
@@ -1661,6 +1802,37 @@ class Recognizer:
     def classify_device(self, crops_ptr: int, n: int, logits_ptr: int, labels_ptr: int, probs_ptr: int) -> None:
         check(lib().ocr_rec_classify_async(self._h, crops_ptr, n, logits_ptr or None, labels_ptr or None,
                                            probs_ptr or None))
+
+    def glyph_costs(self, logits: np.ndarray) -> np.ndarray:
+        """ocr_rec_glyph_costs: logits n x 62 f32 in host memory -> costs n x 62 f32, the negative log-softmax computed in f64."""
+        x = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, 62)
+        costs = np.empty_like(x)
+        if x.shape[0]:
+            check(lib().ocr_rec_glyph_costs(self._h, _ptr(x), x.shape[0], _ptr(costs), MEM_HOST))
+        return costs
+
+    def glyph_costs_device(self, logits_ptr: int, n: int, costs_ptr: int) -> None:
+        check(lib().ocr_rec_glyph_costs(self._h, C.c_void_p(logits_ptr or None), n, C.c_void_p(costs_ptr or None), MEM_DEVICE))
+
+    def _lexicon_match(self, lex, costs_ptr, n_glyphs: int, mem_kind: int, word_offsets, params) -> LexiconMatches:
+        off = np.ascontiguousarray(word_offsets, dtype=np.int32).reshape(-1)
+        prm = _as_lexicon_params(params)
+        out = C.POINTER(LexiconMatchesBlock)()
+        check(lib().ocr_lexicon_match(self._h, lex.handle if isinstance(lex, Lexicon) else lex, costs_ptr, n_glyphs, mem_kind,
+                                      _ptr(off) if off.size else None, len(off) - 1, C.byref(prm) if prm is not None else None, C.byref(out)))
+        try:
+            return LexiconMatches.from_block(out)
+        finally:
+            lib().ocr_lexicon_matches_free(out)
+
+    def lexicon_match(self, lex: "Lexicon", costs: np.ndarray, word_offsets, params=None) -> LexiconMatches:
+        """ocr_lexicon_match: costs n_glyphs x 62 f32 in host memory (glyph_costs), word_offsets [n_words+1] the glyph range per word
+        (GlyphSet.word_offsets); params: LexiconParams, a dict of its fields, or None (defaults).  Blocking, on the handle's stream."""
+        x = np.ascontiguousarray(costs, dtype=np.float32).reshape(-1, 62)
+        return self._lexicon_match(lex, _ptr(x) if x.size else None, x.shape[0], MEM_HOST, word_offsets, params)
+
+    def lexicon_match_device(self, lex: "Lexicon", costs_ptr: int, n_glyphs: int, word_offsets, params=None) -> LexiconMatches:
+        return self._lexicon_match(lex, C.c_void_p(costs_ptr or None), n_glyphs, MEM_DEVICE, word_offsets, params)
 
 
 def python_to_polygons(polys, scores):

@@ -15,9 +15,12 @@ struct ocr_det {
 struct ocr_rec {
   ocr::Recognizer impl;
   int32_t* ctc_bad_crop = nullptr;   // device int of ocr_ctc_beam_decode: the lowest crop with a non-finite logit (allocated on first use)
+  void* lex_ws = nullptr;            // device workspace of the lexicon calls (lexicon.hip): grown on demand
+  size_t lex_ws_bytes = 0;
   ocr_rec(const void* b, size_t n, int d) : impl(b, n, d) {}
   ~ocr_rec() {
     if (ctc_bad_crop) (void)hipFree(ctc_bad_crop);
+    if (lex_ws) (void)hipFree(lex_ws);
   }
 };
 

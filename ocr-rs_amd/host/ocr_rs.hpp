@@ -8,6 +8,7 @@
 //   text_detection::metrics::get_boxes_and_box_scores            metrics.rs:37-56
 //   char_recognition::Net::{new_, forward_t}, utils::topk        model.rs:13-39, utils.rs:28-43
 //   read_words: detected words -> glyphs -> text, the pipeline's segmentation step (README.md:20-26), which the reference never built
+//   Lexicon / glyph_costs / lexicon_match / read_words(.., lexicon): words read as a whole against a word list (ocr_lexicon_match)
 //   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words,
 //     or through curved strips (ocr_plan_curved_strips / ocr_extract_curved_strips), for words that bend
 //   group_lines / read_lines: the words of every page grouped into text lines in reading order (ocr_group_lines), the "output text" step
@@ -234,6 +235,122 @@ inline std::vector<std::vector<WordReading>> read_words(const text_detection::Fu
         r.boxes.push_back({g->boxes[4 * j], g->boxes[4 * j + 1], g->boxes[4 * j + 2], g->boxes[4 * j + 3]});
       }
       out[b].push_back(std::move(r));
+    }
+  }
+  return out;
+}
+
+// ---- lexicon matching (ocr_rec_glyph_costs, ocr_lexicon_create, ocr_lexicon_match; the rule is stated in ocr_amd.h)
+// A word list over VALUES, uploaded once to the recogniser's GPU; results name the indices of `words`.
+class Lexicon {
+ public:
+  Lexicon(const char_recognition::Net& rec_net, std::vector<std::string> words) : words_(std::move(words)) {
+    std::string bytes;
+    std::vector<int32_t> offsets{0};
+    for (const auto& w : words_) {
+      bytes += w;
+      offsets.push_back((int32_t)bytes.size());
+    }
+    check(ocr_lexicon_create(rec_net.handle(), bytes.data(), offsets.data(), (int)words_.size(), &h_));
+  }
+  ~Lexicon() { ocr_lexicon_destroy(h_); }
+  Lexicon(const Lexicon&) = delete;
+  Lexicon& operator=(const Lexicon&) = delete;
+  const std::vector<std::string>& words() const { return words_; }
+  const ocr_lexicon_t* handle() const { return h_; }
+
+ private:
+  std::vector<std::string> words_;
+  ocr_lexicon_t* h_ = nullptr;
+};
+// logits n x 62 (forward_t) -> costs n x 62: the negative log-softmax, computed in f64
+inline std::vector<float> glyph_costs(const char_recognition::Net& rec_net, const std::vector<float>& logits) {
+  if (logits.size() % 62 != 0) throw Error(OCR_ERR_INVALID, "logits are not n x 62");
+  std::vector<float> costs(logits.size());
+  if (!logits.empty()) check(ocr_rec_glyph_costs(rec_net.handle(), logits.data(), (int)(logits.size() / 62), costs.data(), OCR_MEM_HOST));
+  return costs;
+}
+// entries / costs are n_words x top_k (-1 / +inf past the candidates); the other three are per word
+struct LexiconMatches {
+  int top_k = 1;
+  std::vector<int32_t> entries, n_candidates, word_flags;
+  std::vector<double> costs, raw_costs;
+};
+inline LexiconMatches lexicon_match(const char_recognition::Net& rec_net, const Lexicon& lex, const std::vector<float>& costs,
+                                    const std::vector<int32_t>& word_offsets, const ocr_lexicon_params_t* params = nullptr) {
+  if (word_offsets.empty() || costs.size() != 62 * (size_t)word_offsets.back()) throw Error(OCR_ERR_INVALID, "costs do not match the word offsets");
+  ocr_lexicon_matches_t* m = nullptr;
+  check(ocr_lexicon_match(rec_net.handle(), lex.handle(), costs.empty() ? nullptr : costs.data(), (int)(costs.size() / 62), OCR_MEM_HOST,
+                          word_offsets.data(), (int)word_offsets.size() - 1, params, &m));
+  LexiconMatches out;
+  const size_t nw = (size_t)m->n_words, k = (size_t)m->top_k;
+  out.top_k = m->top_k;
+  out.entries.assign(m->entries, m->entries + nw * k);
+  out.costs.assign(m->costs, m->costs + nw * k);
+  out.raw_costs.assign(m->raw_costs, m->raw_costs + nw);
+  out.n_candidates.assign(m->n_candidates, m->n_candidates + nw);
+  out.word_flags.assign(m->word_flags, m->word_flags + nw);
+  ocr_lexicon_matches_free(m);
+  return out;
+}
+// A word read against a lexicon: text is the best entry's string when a candidate exists and cost - raw_cost <= max_penalty * G for
+// its G glyphs, otherwise the raw reading; entry is the best candidate's index (-1 without one) with its cost, whether taken or not.
+struct WordReadingLexicon : WordReading {
+  int32_t entry = -1;
+  double cost = 0, raw_cost = 0;
+  std::string raw_text;
+};
+// read_words with a lexicon.  Over host memory the plain overload runs first and the glyph calls and the recogniser run a second
+// time for the logits (ocr_rec_forward); callers with device-resident crops use ocr_rec_classify_async, which writes labels and
+// logits in one pass, as reading.py does.
+inline std::vector<std::vector<WordReadingLexicon>> read_words(const text_detection::FuncT& det_net, const char_recognition::Net& rec_net,
+                                                               const Tensor& frames, const text_detection::metrics::PolygonScores& ps,
+                                                               const std::vector<double>& adjust_values, const Lexicon& lexicon,
+                                                               const ocr_lexicon_params_t* lexicon_params = nullptr, double max_penalty = 1.5,
+                                                               const ocr_segment_params_t* params = nullptr,
+                                                               const ocr_cc_params_t* cc = nullptr, const ocr_mask_params_t* mask = nullptr) {
+  const auto plain = read_words(det_net, rec_net, frames, ps, adjust_values, params, cc, mask);
+  std::vector<float> crops_flat;
+  std::vector<int32_t> word_offsets{0};
+  // the two glyph calls again for the crops and the word offsets, which the plain overload does not return
+  std::vector<int32_t> img_off{0}, poly_off{0};
+  std::vector<uint32_t> xy;
+  std::vector<double> scores;
+  for (const auto& mp : ps.polygons) {
+    for (const auto& p : mp) {
+      for (const auto& v : p) {
+        xy.push_back(v.first);
+        xy.push_back(v.second);
+      }
+      poly_off.push_back((int32_t)(xy.size() / 2));
+      scores.push_back(0.0);
+    }
+    img_off.push_back((int32_t)scores.size());
+  }
+  const ocr_polygons_t polys{frames.n, (int32_t)scores.size(), (int32_t)(xy.size() / 2), img_off.data(), poly_off.data(), xy.data(),
+                             scores.data()};
+  ocr_glyphs_t* g = nullptr;
+  struct Free {
+    ocr_glyphs_t*& g;
+    ~Free() { ocr_glyphs_free(g); }
+  } free_g{g};
+  segment_and_crop(det_net, frames.data.data(), frames.n, frames.h, frames.w, &polys, adjust_values.data(), params, cc, mask, &g, crops_flat);
+  word_offsets.assign(g->word_offsets, g->word_offsets + g->n_words + 1);
+  const std::vector<float> logits = g->n_glyphs ? rec_net.forward_t(crops_flat, false) : std::vector<float>();
+  const LexiconMatches m = lexicon_match(rec_net, lexicon, glyph_costs(rec_net, logits), word_offsets, lexicon_params);
+  std::vector<std::vector<WordReadingLexicon>> out(frames.n);
+  size_t k = 0;
+  for (int b = 0; b < frames.n; ++b) {
+    for (const auto& w : plain[b]) {
+      WordReadingLexicon r;
+      static_cast<WordReading&>(r) = w;
+      r.raw_text = w.text;
+      r.entry = m.entries[k * m.top_k];
+      r.cost = m.costs[k * m.top_k];
+      r.raw_cost = m.raw_costs[k];
+      if (r.entry >= 0 && r.cost - r.raw_cost <= max_penalty * (double)w.text.size()) r.text = lexicon.words()[r.entry];
+      out[b].push_back(std::move(r));
+      ++k;
     }
   }
   return out;

@@ -23,9 +23,14 @@ recognition -> output text), composed over the C ABI.
         ocr_group_lines           the words of every page -> text lines in reading order  (csrc/lines.hip)
     page_text(lines) joins the lines of one image with "\n".
 
+    Every reading call takes lexicon=capi.Lexicon (with lexicon_params and max_penalty): the glyph posteriors of every word are then
+    matched against the word list on the device, between the classify call and the texts:
+        ocr_rec_glyph_costs       the classify call's logits -> negative log-softmax costs (csrc/lexicon.hip)
+        ocr_lexicon_match         every word against every entry of an admissible length  (csrc/lexicon.hip)
+
 The segmentation, strip and line rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
 tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py, tests/strip_oracle.py, tests/curved_strip_oracle.py and
-tests/line_oracle.py.
+tests/line_oracle.py; the lexicon rule likewise, restated in tests/lexicon_oracle.py.
 """
 from __future__ import annotations
 
@@ -90,8 +95,45 @@ def _segment_and_crop(det, frames_ptr, n, h, w, polys, adjust_values, params, cc
     return glyphs, crops
 
 
-def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None, cc=None, mask=None
-               ) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+def _classify(rec, crops, ng: int, dev, word_offsets, lexicon, lexicon_params):
+    """classify on device crops -> (labels, probs, LexiconMatches or None); with a lexicon the same call also writes the logits, and
+    the costs and the match stay on the device."""
+    import torch
+    if lexicon is not None and not isinstance(lexicon, capi.Lexicon):
+        raise TypeError(f"lexicon: expected a capi.Lexicon, got {type(lexicon).__name__}")
+    labels = np.zeros(0, np.int32)
+    probs = np.zeros(0, np.float64)
+    costs_ptr = 0
+    if ng:
+        lab = torch.empty(ng, dtype=torch.int32, device=dev)
+        pr = torch.empty(ng, dtype=torch.float64, device=dev)
+        logits = torch.empty((ng, 62), dtype=torch.float32, device=dev) if lexicon is not None else None
+        rec.classify_device(crops.data_ptr(), ng, logits.data_ptr() if logits is not None else 0, lab.data_ptr(), pr.data_ptr())
+        if lexicon is not None:
+            costs = torch.empty((ng, 62), dtype=torch.float32, device=dev)
+            rec.glyph_costs_device(logits.data_ptr(), ng, costs.data_ptr())   # blocking, behind the classify call
+            costs_ptr = costs.data_ptr()
+        else:
+            rec.synchronize()
+        labels, probs = lab.cpu().numpy(), pr.cpu().numpy()
+    matches = None
+    if lexicon is not None:
+        matches = rec.lexicon_match_device(lexicon, costs_ptr, ng, word_offsets, lexicon_params)
+    return labels, probs, matches
+
+
+def _word(text: str, probs, where, k: int, n_glyphs: int, matches, lexicon, max_penalty: float):
+    """The tuple of word k: without a lexicon (text, probs, where); with one the text is the best entry's string when a candidate
+    exists and cost - raw_cost <= max_penalty * G (f64), and (entry index or -1, cost, raw_cost, raw text) is appended."""
+    if matches is None:
+        return (text, probs, where)
+    e, c, r = int(matches.entries[k, 0]), float(matches.costs[k, 0]), float(matches.raw_costs[k])
+    take = e >= 0 and c - r <= float(max_penalty) * n_glyphs
+    return (lexicon.words[e] if take else text, probs, where, (e, c, r, text))
+
+
+def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None, cc=None, mask=None, lexicon=None,
+               lexicon_params=None, max_penalty=1.5) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch.
 
     det_net: text_detection.FuncT or capi.Detector (supplies the GPU and stream of the segmentation); rec_net: char_recognition.Net
@@ -102,7 +144,11 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     mask: None or False cuts every crop from its box alone; True, {} or {"halo": 0} (capi.MaskParams' fields) needs cc and masks every
     crop by its glyph's components (ocr_segment_glyphs_cc_labelled, ocr_extract_glyph_crops_masked): a kerned neighbour's ink stays out.
     Returns per image, per polygon: (text, probability of every character (f64), glyph boxes k x 4 int32 x0, y0, x1, y1 in frame
-    pixels, half-open).  A flat word reads as ""."""
+    pixels, half-open).  A flat word reads as "".
+    lexicon: None, or a capi.Lexicon on the recogniser's GPU: every word is matched against it (ocr_lexicon_match with lexicon_params:
+    capi.LexiconParams, a dict of its fields or None) and its tuple gains a fourth element (entry index or -1, cost, raw_cost, raw
+    text); the text becomes the entry's string when a candidate exists and cost - raw_cost <= max_penalty * G for the word's G glyphs,
+    otherwise the raw text stays.  With lexicon=None nothing changes."""
     import torch
 
     det = _handle(det_net, capi.Detector)
@@ -123,20 +169,14 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     torch.cuda.current_stream(dev).synchronize()
     glyphs, crops = _segment_and_crop(det, x.data_ptr(), n, h, w, polys, adjust_values, params, cc, mask, dev)   # blocking
     ng = glyphs.n_glyphs
-    labels = np.zeros(0, np.int32)
-    probs = np.zeros(0, np.float64)
-    if ng:
-        lab = torch.empty(ng, dtype=torch.int32, device=dev)
-        pr = torch.empty(ng, dtype=torch.float64, device=dev)
-        rec.classify_device(crops.data_ptr(), ng, 0, lab.data_ptr(), pr.data_ptr())
-        rec.synchronize()
-        labels, probs = lab.cpu().numpy(), pr.cpu().numpy()
+    labels, probs, matches = _classify(rec, crops, ng, dev, glyphs.word_offsets, lexicon, lexicon_params)
     out = []
     for b in range(n):
         words = []
         for k in range(int(glyphs.img_offsets[b]), int(glyphs.img_offsets[b + 1])):
             g0, g1 = int(glyphs.word_offsets[k]), int(glyphs.word_offsets[k + 1])
-            words.append(("".join(VALUES[int(c)] for c in labels[g0:g1]), probs[g0:g1].copy(), glyphs.boxes[g0:g1].copy()))
+            words.append(_word("".join(VALUES[int(c)] for c in labels[g0:g1]), probs[g0:g1].copy(), glyphs.boxes[g0:g1].copy(), k, g1 - g0,
+                               matches, lexicon, max_penalty))
         out.append(words)
     return out
 
@@ -206,7 +246,7 @@ def _curved(curved, strip_params):
 
 
 def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None, cc=None, mask=None,
-                         curved=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+                         curved=None, lexicon=None, lexicon_params=None, max_penalty=1.5) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch through its upright strip: rotated words are read along their own axis, and with
     curved=True (or {} or a dict of capi.CurveParams' fields: strip_height, max_width, valid_pct) words that bend are read along their
     own centreline (ocr_plan_curved_strips, ocr_extract_curved_strips; the glyph quads then come from curved_glyph_quads).  curved=None
@@ -215,7 +255,7 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     Arguments as read_words; strip_params: capi.StripParams, a dict of its fields (strip_height, max_width) or None for the defaults;
     params, cc and mask: the segmentation parameters, rule and crop masking as in read_words, applied to the atlas.  Returns per image, per polygon: (text, probability of every character
     (f64), glyph quads k x 4 x 2 f64: the corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of every glyph box mapped back to frame
-    coordinates, strip_glyph_quads).  A flat word reads as ""."""
+    coordinates, strip_glyph_quads).  A flat word reads as "".  lexicon, lexicon_params and max_penalty as in read_words."""
     import torch
 
     det = _handle(det_net, capi.Detector)
@@ -241,14 +281,7 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     with strips.polygon_block() as rects:
         glyphs, crops = _segment_and_crop(det, atlas.data_ptr(), 1, hs, tw, rects, [[1.0, 1.0]], params, cc, mask, dev)
     ng = glyphs.n_glyphs
-    labels = np.zeros(0, np.int32)
-    probs = np.zeros(0, np.float64)
-    if ng:
-        lab = torch.empty(ng, dtype=torch.int32, device=dev)
-        pr = torch.empty(ng, dtype=torch.float64, device=dev)
-        rec.classify_device(crops.data_ptr(), ng, 0, lab.data_ptr(), pr.data_ptr())
-        rec.synchronize()
-        labels, probs = lab.cpu().numpy(), pr.cpu().numpy()
+    labels, probs, matches = _classify(rec, crops, ng, dev, glyphs.word_offsets, lexicon, lexicon_params)
     quads = (strip_glyph_quads if cp is None else curved_glyph_quads)(
         strips, np.repeat(np.arange(glyphs.n_words), np.diff(glyphs.word_offsets)), glyphs.boxes)
     text = "".join(VALUES[int(c)] for c in labels)
@@ -257,7 +290,7 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
         words = []
         for k in range(int(strips.img_offsets[b]), int(strips.img_offsets[b + 1])):
             g0, g1 = int(glyphs.word_offsets[k]), int(glyphs.word_offsets[k + 1])
-            words.append((text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy()))
+            words.append(_word(text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy(), k, g1 - g0, matches, lexicon, max_penalty))
         out.append(words)
     return out
 
@@ -267,7 +300,7 @@ def read_lines(det_net, rec_net, frames, polygon_scores, adjust_values, line_par
     """Reads every detected word of a batch and groups the words of every image into text lines in reading order (ocr_group_lines).
 
     Arguments as read_words_rectified (rectified=True, the default) or read_words (rectified=False); strip_params, params, cc, mask and
-    curved go to that call unchanged.  line_params: capi.LineParams, a dict of its fields (line_tol, height_ratio, min_cos, max_gap) or
+    curved go to that call unchanged, and so do lexicon, lexicon_params and max_penalty (the lines then join the matched texts).  line_params: capi.LineParams, a dict of its fields (line_tol, height_ratio, min_cos, max_gap) or
     None for the defaults.  The quads always come from ocr_plan_word_strips (with strip_params where given): word order equals polygon
     order in every reading call, and the curved plan carries no quads.
     Returns per image a list of lines (text, word_indices, gaps): word_indices are the image's polygon indices in reading order (int32),
@@ -285,7 +318,7 @@ def read_lines(det_net, rec_net, frames, polygon_scores, adjust_values, line_par
     strips = det.plan_word_strips(polys, adjust_values, h, w, reading_kwargs.get("strip_params"), getattr(polygon_scores, "scores", None))
     lines = det.group_lines(strips.quads, strips.img_offsets, line_params)
     # one pass over the lines of the batch: slices of the batch's arrays (views), the texts by batch-global word index
-    texts = [t for page in words for t, _, _ in page]
+    texts = [wd[0] for page in words for wd in page]
     order = lines.order.tolist()
     local = lines.order - np.repeat(strips.img_offsets[:-1], np.diff(strips.img_offsets))[lines.order]
     img_off, line_off = lines.img_offsets.tolist(), lines.line_offsets.tolist()
