@@ -660,6 +660,75 @@ int  ocr_group_lines(ocr_det_t* det, const double* quads, const int32_t* word_im
                      const ocr_line_params_t* params, ocr_lines_t** out);
 void ocr_lines_free(ocr_lines_t* l);
 
+/* Column-aware reading order: the words of every page as blocks (columns, paragraphs) in reading order, every block its lines top to
+ * bottom, every line its words left to right (BUILD-DEFINED; the reference has no counterpart).  Input, arithmetic (f64, every
+ * operation separately rounded, no FMA, IEEE sqrt and divide; a dot product is dx*ux + dy*uy in that order) and the word features C,
+ * u, v, lu, lv and "isolated" are those of ocr_group_lines.  L = C - u * (lu * 0.5) is the midpoint of a word's left edge, R = C +
+ * u * (lu * 0.5) of its right edge.  min(a, b) is b < a ? b : a and max(a, b) is b > a ? b : a; a min or max over a sequence starts
+ * with its first value and replaces on a strict improvement.  Every scan ascends over indices and replaces on a strict improvement
+ * only (ties go to the smaller index).  "Mutual nearest" links: next[p] is the candidate of p with the smallest a; prev[q] is the p
+ * with the smallest a among those that have q as a candidate, a measured in p's frame; the link p -> q exists iff next[p] == q &&
+ * prev[q] == p.
+ * A. Rows: the links of ocr_group_lines with row_gap in place of max_gap, its mutual links and its cycle cut (flag 2).  A link i -> j
+ *    carries g = a - (lui + luj) * 0.5 and hmax = max(lvi, lvj) of the pair test in i's frame.
+ * B. Gutters: every link of A is a gap element, indexed by its right word j: centre G = (Ri + Lj) * 0.5, frame (ui, vi), half width
+ *    w = g * 0.5, height h = hmax.  It is wide when g > max_gap * h and eligible when g >= min_gutter * h.  Element q is a below
+ *    candidate of p when both are eligible and, with d = Gq - Gp: a = d . vp > 0; fabs(d . up) < wp + wq; a <= gutter_reach *
+ *    max(hp, hq); up . uq >= min_cos.  Mutual nearest links give chains of stacked gaps; the size of an element is the number of
+ *    elements of its chain (of its cycle, if the chain closes).  The link into word j is cut when the element is wide, or when it is
+ *    eligible and its size is >= min_rows; the second case, alone or with the first, sets flag 4 on word j.
+ * C. Lines: the chains of A after the cuts, indexed by their head word: frame (u, v) of the head word, S = L(head), E = R(tail),
+ *    M = (S + E) * 0.5, len = (E - S) . u, h = max of lv over its words from head to tail.  The line of an isolated word is isolated.
+ * D. Blocks: line t is a below candidate of line s when both are not isolated and, with x0 = (St - Ss) . us, x1 = (Et - Ss) . us,
+ *    lo = min(x0, x1), hi = max(x0, x1), ov = min(hi, len_s) - max(lo, 0), a = (Mt - Ms) . vs, hmax = max(hs, ht), hmin = min(hs, ht):
+ *    a > 0; ov > 0 and ov >= min_overlap * min(len_s, hi - lo); a <= block_reach * hmax; hmax <= height_ratio * hmin; us . ut >=
+ *    min_cos.  Mutual nearest links give chains; a cycle is cut on the link into its smallest-index line (line flag 1).  A chain, head
+ *    to tail, is a block, indexed by the head word of its head line.
+ * E. Block order: a block has the frame (u, v) and the origin O = S of its head line.  Over its lines t from head to tail: X0 = min and
+ *    X1 = max of (St - O) . u, (Et - O) . u (in that order per line); with m = (Mt - O) . v, Y0 = min of m - ht * 0.5 and Y1 = max of
+ *    m + ht * 0.5.  Its quad is (Ox + ux * X) + vx * Y, (Oy + uy * X) + vy * Y at (X0, Y0), (X1, Y0), (X1, Y1), (X0, Y1); W = X1 - X0,
+ *    H = Y1 - Y0.  The block of an isolated word is the axis-aligned bounding box of its quad (min / max over TL, TR, BR, BL) with
+ *    u = (1, 0), v = (0, 1), W and H its differences.  Block X precedes Y (X != Y) when, with Y's four corners minus X's TL projected
+ *    on X's u and v into [ax0, ax1] x [ay0, ay1] (min / max over TL, TR, BR, BL): ax0 >= W and min(ay1, H) - max(ay0, 0) > 0 (left
+ *    of), or ay0 >= H and min(ax1, W) - max(ax0, 0) > 0 (above).  Levels start at 0; one round sets level[Y] = min(max_levels - 1,
+ *    max over X that precede Y of level[X] + 1), or 0 when nothing precedes Y, reading all old values before writing any new one;
+ *    max_levels - 1 rounds run (a round that changes nothing ends them: the result is the same).  The relation can hold cycles; the
+ *    cap defines the result anyway.  The blocks of an image are ordered by (level, TL.y, TL.x, index), ascending.
+ * Consequences (documented, not handled): a full-width heading within block_reach of the columns joins the column whose first line is
+ *   nearest below it; a regular grid of words whose gaps reach min_gutter is a table and is read column by column.  Out of scope:
+ *   tables, nested layouts (no recursive XY-cut), right-to-left and vertical scripts, spaces inside a polygon.
+ * Oracle: tests/column_oracle.py; kernels: csrc/columns.hip (stage A is the launch of ocr_group_lines).  Blocking, on the detector's
+ * stream, host pointers, and the error cases of ocr_group_lines (OCR_ERR_INVALID before any launch, the handle stays usable); zero
+ * words launch nothing and return valid offsets; at most OCR_LINE_MAX_WORDS words an image. */
+typedef struct ocr_column_params {
+  ocr_line_params_t line;  /* line_tol, height_ratio, min_cos, max_gap as in ocr_group_lines */
+  double row_gap;          /* [line.max_gap, 64], default 16   */
+  double min_gutter;       /* [0, 64],            default 1.5  */
+  double gutter_reach;     /* (0, 16],            default 2.5  */
+  double min_overlap;      /* [0, 1],             default 0.25 */
+  double block_reach;      /* (0, 16],            default 2.5  */
+  int32_t min_rows;        /* [1, 4096],          default 3    */
+  int32_t max_levels;      /* [1, 256],           default 64   */
+  int32_t reserved[2];     /* must be 0 */
+} ocr_column_params_t;
+typedef struct ocr_columns {
+  int32_t n_images, n_words, n_lines, n_blocks;
+  const int32_t* img_offsets;    /* [n_images+1] block range per image             */
+  const int32_t* block_offsets;  /* [n_blocks+1] line range per block              */
+  const int32_t* line_offsets;   /* [n_lines+1]  range of `order` per line         */
+  const int32_t* order;          /* [n_words]    batch-global word indices, reading order */
+  const int32_t* word_flags;     /* [n_words]    by word index: 1 isolated, 2 cycle cut here, 4 a gutter in front of this word */
+  const double*  gaps;           /* [n_words]    by position: g / hmax of the link into the word, 0.0 for a line's head */
+  const int32_t* line_flags;     /* [n_lines]    1: a cycle of lines was cut in front of this line */
+  const int32_t* block_levels;   /* [n_blocks]                                      */
+  const double*  block_quads;    /* [n_blocks*8] TL, TR, BR, BL                     */
+} ocr_columns_t;
+void ocr_column_default_params(ocr_column_params_t* p);
+/* *out: ocr_columns_free. */
+int  ocr_group_columns(ocr_det_t* det, const double* quads, const int32_t* word_img_offsets, int n_images,
+                       const ocr_column_params_t* params, ocr_columns_t** out);
+void ocr_columns_free(ocr_columns_t* c);
+
 /* ---------------------------------------------------------------------------
  * Detection quality metrics (host code; consumers of the polygon lists).  Replaces
  *   evaluate_image(gt, ignore_flags, pred) -> Result<MetricsItem>      metrics.rs:255-380

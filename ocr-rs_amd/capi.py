@@ -35,6 +35,7 @@ EXPORTS = [
     "ocr_strip_default_params", "ocr_plan_word_strips", "ocr_extract_word_strips", "ocr_word_strip_polygons", "ocr_word_strips_free",
     "ocr_curve_default_params", "ocr_plan_curved_strips", "ocr_extract_curved_strips", "ocr_curved_strip_polygons", "ocr_curved_strips_free",
     "ocr_line_default_params", "ocr_group_lines", "ocr_lines_free",
+    "ocr_column_default_params", "ocr_group_columns", "ocr_columns_free",
     "ocr_evaluate_image", "ocr_combine_results",
     "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_set_stream", "ocr_rec_set_options", "ocr_rec_synchronize",
     "ocr_rec_forward", "ocr_rec_classify_async", "ocr_rec_classify_profile", "ocr_rec_classify", "ocr_rec_alphabet", "ocr_ctc_greedy_decode",
@@ -136,6 +137,21 @@ class LinesBlock(C.Structure):
 
 
 LINE_MAX_WORDS = 4096
+
+
+class ColumnParams(C.Structure):
+    """ocr_column_params_t."""
+    _fields_ = [("line", LineParams), ("row_gap", C.c_double), ("min_gutter", C.c_double), ("gutter_reach", C.c_double),
+                ("min_overlap", C.c_double), ("block_reach", C.c_double), ("min_rows", C.c_int32), ("max_levels", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class ColumnsBlock(C.Structure):
+    """ocr_columns_t."""
+    _fields_ = [("n_images", C.c_int32), ("n_words", C.c_int32), ("n_lines", C.c_int32), ("n_blocks", C.c_int32),
+                ("img_offsets", C.POINTER(C.c_int32)), ("block_offsets", C.POINTER(C.c_int32)), ("line_offsets", C.POINTER(C.c_int32)),
+                ("order", C.POINTER(C.c_int32)), ("word_flags", C.POINTER(C.c_int32)), ("gaps", C.POINTER(C.c_double)),
+                ("line_flags", C.POINTER(C.c_int32)), ("block_levels", C.POINTER(C.c_int32)), ("block_quads", C.POINTER(C.c_double))]
 
 
 class LexiconParams(C.Structure):
@@ -292,6 +308,12 @@ def lib() -> C.CDLL:
         L.ocr_group_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LineParams), C.POINTER(C.POINTER(LinesBlock))]
         L.ocr_lines_free.argtypes = [C.POINTER(LinesBlock)]
         L.ocr_lines_free.restype = None
+        L.ocr_column_default_params.argtypes = [C.POINTER(ColumnParams)]
+        L.ocr_column_default_params.restype = None
+        L.ocr_group_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ColumnParams),
+                                        C.POINTER(C.POINTER(ColumnsBlock))]
+        L.ocr_columns_free.argtypes = [C.POINTER(ColumnsBlock)]
+        L.ocr_columns_free.restype = None
         L.ocr_rec_glyph_costs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.ocr_lexicon_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_lexicon_size.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
@@ -856,6 +878,86 @@ class Lines:
         return out
 
 
+def column_params(**fields) -> ColumnParams:
+    """ocr_column_default_params with the given fields overridden: the line fields (line_tol, height_ratio, min_cos, max_gap), row_gap,
+    min_gutter, gutter_reach, min_overlap, block_reach, min_rows, max_levels; `reserved` is the column block's, `line_reserved` the
+    embedded line block's."""
+    p = ColumnParams()
+    lib().ocr_column_default_params(C.byref(p))
+    own = dict(ColumnParams._fields_)
+    for k, v in fields.items():
+        if k == "reserved":
+            p.reserved[0], p.reserved[1] = (int(x) for x in v)
+        elif k == "line_reserved":
+            p.line.reserved[0], p.line.reserved[1] = (int(x) for x in v)
+        elif k in ("min_rows", "max_levels"):
+            setattr(p, k, int(v))
+        elif k in own and k != "line":
+            setattr(p, k, float(v))
+        elif k in dict(LineParams._fields_):
+            setattr(p.line, k, float(v))
+        else:
+            raise TypeError(f"unknown column parameter {k!r}")
+    return p
+
+
+def _as_column_params(params) -> Optional[ColumnParams]:
+    if params is None or isinstance(params, ColumnParams):
+        return params
+    return column_params(**params)
+
+
+class Columns:
+    """The arrays of an ocr_columns_t, copied into numpy: img_offsets [n_images+1] (block range per image), block_offsets [n_blocks+1]
+    (line range per block), line_offsets [n_lines+1] (range of `order` per line), order [n_words], word_flags [n_words] by word index
+    (1 isolated, 2 cycle cut, 4 gutter cut), gaps [n_words] by position, line_flags [n_lines], block_levels [n_blocks], block_quads
+    [n_blocks, 8] (TL, TR, BR, BL)."""
+    FIELDS = (("img_offsets", np.int32), ("block_offsets", np.int32), ("line_offsets", np.int32), ("order", np.int32),
+              ("word_flags", np.int32), ("gaps", np.float64), ("line_flags", np.int32), ("block_levels", np.int32),
+              ("block_quads", np.float64))
+
+    def __init__(self, **arrays):
+        for name, dt in self.FIELDS:
+            setattr(self, name, np.ascontiguousarray(arrays[name], dtype=dt))
+        self.block_quads = self.block_quads.reshape(-1, 8)
+
+    @property
+    def n_images(self) -> int:
+        return len(self.img_offsets) - 1
+
+    @property
+    def n_blocks(self) -> int:
+        return len(self.block_offsets) - 1
+
+    @property
+    def n_lines(self) -> int:
+        return len(self.line_offsets) - 1
+
+    @property
+    def n_words(self) -> int:
+        return len(self.order)
+
+    @staticmethod
+    def from_block(cp) -> "Columns":
+        s = cp.contents
+        sizes = {"img_offsets": s.n_images + 1, "block_offsets": s.n_blocks + 1, "line_offsets": s.n_lines + 1, "order": s.n_words,
+                 "word_flags": s.n_words, "gaps": s.n_words, "line_flags": s.n_lines, "block_levels": s.n_blocks,
+                 "block_quads": s.n_blocks * 8}
+        return Columns(**{name: (np.ctypeslib.as_array(getattr(s, name), shape=(sizes[name],)).copy() if sizes[name] else np.zeros(0, dt))
+                          for name, dt in Columns.FIELDS})
+
+    def blocks(self, b: int) -> List[List[Tuple[np.ndarray, np.ndarray]]]:
+        """image b: per block, per line (batch-global word indices in reading order, their gaps)"""
+        out = []
+        for k in range(int(self.img_offsets[b]), int(self.img_offsets[b + 1])):
+            lines = []
+            for l in range(int(self.block_offsets[k]), int(self.block_offsets[k + 1])):
+                p0, p1 = int(self.line_offsets[l]), int(self.line_offsets[l + 1])
+                lines.append((self.order[p0:p1].copy(), self.gaps[p0:p1].copy()))
+            out.append(lines)
+        return out
+
+
 def lexicon_params(**fields) -> LexiconParams:
     """ocr_lexicon_default_params with the given fields overridden (ins_cost, del_cost, max_len_diff, fold_case, top_k)."""
     p = LexiconParams()
@@ -1278,6 +1380,20 @@ class Detector:
             return Lines.from_block(out)
         finally:
             lib().ocr_lines_free(out)
+
+    def group_columns(self, quads, img_offsets, params=None) -> Columns:
+        """ocr_group_columns: the arguments of group_lines; params: ColumnParams, a dict of its fields and the line fields, or None
+        (defaults).  Blocking, on the handle's stream."""
+        q = np.ascontiguousarray(quads, dtype=np.float64).reshape(-1)
+        off = np.ascontiguousarray(img_offsets, dtype=np.int32).reshape(-1)
+        prm = _as_column_params(params)
+        out = C.POINTER(ColumnsBlock)()
+        check(lib().ocr_group_columns(self._h, _ptr(q) if q.size else None, _ptr(off) if off.size else None, len(off) - 1,
+                                      C.byref(prm) if prm is not None else None, C.byref(out)))
+        try:
+            return Columns.from_block(out)
+        finally:
+            lib().ocr_columns_free(out)
 
     def debug_stage(self, stage_id: int, shape_nhwc) -> np.ndarray:
         """Test hook: NHWC intermediate of the last forward, returned as NCHW."""

@@ -1064,6 +1064,156 @@ void ocr_lines_free(ocr_lines_t* l) {
   delete reinterpret_cast<ocr::LinesOwned*>(reinterpret_cast<char*>(l) - offsetof(ocr::LinesOwned, view));
 }
 
+// ---- column-aware reading order (columns.hip; rule in include/ocr_amd.h, oracle tests/column_oracle.py)
+void ocr_column_default_params(ocr_column_params_t* p) {
+  if (!p) return;
+  ocr_line_default_params(&p->line);
+  p->row_gap = 16.0;
+  p->min_gutter = 1.5;
+  p->gutter_reach = 2.5;
+  p->min_overlap = 0.25;
+  p->block_reach = 2.5;
+  p->min_rows = 3;
+  p->max_levels = 64;
+  p->reserved[0] = p->reserved[1] = 0;
+}
+
+int ocr_group_columns(ocr_det_t* det, const double* quads, const int32_t* word_img_offsets, int n_images, const ocr_column_params_t* params,
+                      ocr_columns_t** out) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !word_img_offsets || !out) fail(OCR_ERR_INVALID, "group_columns: null argument");
+    *out = nullptr;
+    if (n_images < 1) fail(OCR_ERR_INVALID, "group_columns: %d images", n_images);
+    ocr_column_params_t p;
+    ocr_column_default_params(&p);
+    if (params) p = *params;
+    const ocr_line_params_t& lp = p.line;
+    // (written so that a NaN is out of range)
+    if (!(lp.line_tol > 0 && lp.line_tol <= 4) || !(lp.height_ratio >= 1 && lp.height_ratio <= 16) || !(lp.min_cos >= 0 && lp.min_cos <= 1) ||
+        !(lp.max_gap >= 0 && lp.max_gap <= 64) || lp.reserved[0] || lp.reserved[1])
+      fail(OCR_ERR_INVALID, "group_columns: line params line_tol=%g height_ratio=%g min_cos=%g max_gap=%g reserved=(%d, %d) (limits: line_tol "
+           "(0, 4], height_ratio [1, 16], min_cos [0, 1], max_gap [0, 64], reserved 0)", lp.line_tol, lp.height_ratio, lp.min_cos, lp.max_gap,
+           lp.reserved[0], lp.reserved[1]);
+    if (!(p.row_gap >= lp.max_gap && p.row_gap <= 64) || !(p.min_gutter >= 0 && p.min_gutter <= 64) ||
+        !(p.gutter_reach > 0 && p.gutter_reach <= 16) || !(p.min_overlap >= 0 && p.min_overlap <= 1) ||
+        !(p.block_reach > 0 && p.block_reach <= 16) || p.min_rows < 1 || p.min_rows > 4096 || p.max_levels < 1 || p.max_levels > 256 ||
+        p.reserved[0] || p.reserved[1])
+      fail(OCR_ERR_INVALID, "group_columns: params row_gap=%g min_gutter=%g gutter_reach=%g min_overlap=%g block_reach=%g min_rows=%d "
+           "max_levels=%d reserved=(%d, %d) (limits: row_gap [max_gap, 64], min_gutter [0, 64], gutter_reach (0, 16], min_overlap [0, 1], "
+           "block_reach (0, 16], min_rows [1, 4096], max_levels [1, 256], reserved 0)", p.row_gap, p.min_gutter, p.gutter_reach,
+           p.min_overlap, p.block_reach, p.min_rows, p.max_levels, p.reserved[0], p.reserved[1]);
+    if (word_img_offsets[0] != 0) fail(OCR_ERR_INVALID, "group_columns: word offsets start at %d", word_img_offsets[0]);
+    int max_words = 0;
+    for (int b = 0; b < n_images; ++b) {
+      const int64_t cnt = (int64_t)word_img_offsets[b + 1] - word_img_offsets[b];
+      if (cnt < 0) fail(OCR_ERR_INVALID, "group_columns: word offsets decrease at image %d", b);
+      if (cnt > OCR_LINE_MAX_WORDS) fail(OCR_ERR_INVALID, "group_columns: image %d has %lld words (limit %d)", b, (long long)cnt, OCR_LINE_MAX_WORDS);
+      max_words = std::max(max_words, (int)cnt);
+    }
+    const int nw = word_img_offsets[n_images];
+    if (nw > 0 && !quads) fail(OCR_ERR_INVALID, "group_columns: null quads");
+    for (size_t e = 0; e < (size_t)nw * 8; ++e)
+      if (!std::isfinite(quads[e])) fail(OCR_ERR_INVALID, "group_columns: word %zu has a non-finite coordinate", e / 8);
+    std::unique_ptr<ColumnsOwned> c(new ColumnsOwned());
+    c->img_offsets.assign(1, 0);
+    c->block_offsets.assign(1, 0);
+    c->line_offsets.assign(1, 0);
+    if (nw == 0) {
+      c->img_offsets.assign((size_t)n_images + 1, 0);
+      c->finish();
+      *out = &c.release()->view;
+      return;
+    }
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    const size_t q_bytes = (size_t)nw * 64, off_bytes = ((size_t)n_images + 1) * 4, w4 = (size_t)nw * 4, w8 = (size_t)nw * 8;
+    Carve cv;
+    const size_t o_q = cv.take(q_bytes), o_off = cv.take(off_bytes);
+    ColumnBuffers b;
+    // (offsets first: the scratch block is fetched once the carve is complete)
+    struct Slot { void** p; size_t off; };
+    std::vector<Slot> slots;
+    auto want = [&](auto*& ptr, size_t bytes) { slots.push_back({reinterpret_cast<void**>(&ptr), cv.take(bytes)}); };
+    want(b.feat, (size_t)nw * kLineFeatBytes);
+    want(b.link, 2 * w4);
+    want(b.row_order, w4);
+    want(b.flags, w4);
+    want(b.row_start, w4);
+    want(b.n_rows, (size_t)n_images * 4);
+    want(b.row_gaps, w8);
+    want(b.row_prev, w4);
+    want(b.row_pos, w4);
+    want(b.gap_state, w4);
+    want(b.line_state, w4);
+    want(b.line_head, w4);
+    want(b.line_len, w4);
+    want(b.line_cut, w4);
+    want(b.gap_by_word, w8);
+    want(b.gap_rec, (size_t)nw * kColumnGapBytes);
+    want(b.line_rec, (size_t)nw * kColumnLineBytes);
+    want(b.block_rec, (size_t)nw * kColumnBlockBytes);
+    want(b.block_quads_by_slot, 8 * w8);
+    want(b.pred_bits, (size_t)nw * ((max_words + 31) / 32) * 4);
+    want(b.order, w4);
+    want(b.line_start, w4);
+    want(b.line_flags, w4);
+    want(b.block_start, w4);
+    want(b.block_levels, w4);
+    want(b.counts, (size_t)n_images * 8);
+    want(b.gaps, w8);
+    want(b.block_quads, 8 * w8);
+    char* sc = static_cast<char*>(det->impl.scratch(1, cv.end));
+    for (const Slot& sl : slots) *sl.p = sc + sl.off;
+    OCR_HIP(hipMemcpyAsync(sc + o_q, quads, q_bytes, hipMemcpyHostToDevice, s));
+    OCR_HIP(hipMemcpyAsync(sc + o_off, word_img_offsets, off_bytes, hipMemcpyHostToDevice, s));
+    launch_group_columns(at<const double>(sc, o_q), at<const int32_t>(sc, o_off), n_images, nw, max_words,
+                         LineParams{lp.line_tol, lp.height_ratio, lp.min_cos, p.row_gap},
+                         ColumnParams{lp.height_ratio, lp.min_cos, lp.max_gap, p.min_gutter, p.gutter_reach, p.min_overlap, p.block_reach,
+                                      p.min_rows, p.max_levels}, b, s);
+    std::vector<int32_t> line_start(nw), line_flags(nw), block_start(nw), block_levels(nw), counts(2 * (size_t)n_images);
+    std::vector<double> block_quads(8 * (size_t)nw);
+    c->order.resize(nw);
+    c->word_flags.resize(nw);
+    c->gaps.resize(nw);
+    OCR_HIP(hipMemcpyAsync(c->order.data(), b.order, w4, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(c->word_flags.data(), b.flags, w4, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(c->gaps.data(), b.gaps, w8, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(line_start.data(), b.line_start, w4, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(line_flags.data(), b.line_flags, w4, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(block_start.data(), b.block_start, w4, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(block_levels.data(), b.block_levels, w4, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(block_quads.data(), b.block_quads, 8 * w8, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipMemcpyAsync(counts.data(), b.counts, (size_t)n_images * 8, hipMemcpyDeviceToHost, s));
+    OCR_HIP(hipStreamSynchronize(s));
+    // the kernels leave the lines and blocks of image b at the front of its own word slice; the CSRs over the batch are their
+    // concatenation (block starts are image-local line numbers)
+    c->line_offsets.clear();
+    c->block_offsets.clear();
+    for (int i = 0; i < n_images; ++i) {
+      const int w0 = word_img_offsets[i], cnt = word_img_offsets[i + 1] - w0, nl = counts[2 * i], nb = counts[2 * i + 1];
+      if (nl < 0 || nl > cnt || nb < 0 || nb > nl || (cnt > 0 && nb == 0))
+        fail(OCR_ERR_INTERNAL, "group_columns: image %d reports %d lines in %d blocks of %d words", i, nl, nb, cnt);
+      const int32_t l0 = (int32_t)c->line_offsets.size();
+      for (int k = 0; k < nb; ++k) c->block_offsets.push_back(l0 + block_start[w0 + k]);
+      c->line_offsets.insert(c->line_offsets.end(), line_start.begin() + w0, line_start.begin() + w0 + nl);
+      c->line_flags.insert(c->line_flags.end(), line_flags.begin() + w0, line_flags.begin() + w0 + nl);
+      c->block_levels.insert(c->block_levels.end(), block_levels.begin() + w0, block_levels.begin() + w0 + nb);
+      c->block_quads.insert(c->block_quads.end(), block_quads.begin() + 8 * (size_t)w0, block_quads.begin() + 8 * ((size_t)w0 + nb));
+      c->img_offsets.push_back((int32_t)c->block_offsets.size());
+    }
+    c->block_offsets.push_back((int32_t)c->line_offsets.size());
+    c->line_offsets.push_back(nw);
+    c->finish();
+    *out = &c.release()->view;
+  });
+}
+
+void ocr_columns_free(ocr_columns_t* c) {
+  if (!c) return;
+  delete reinterpret_cast<ocr::ColumnsOwned*>(reinterpret_cast<char*>(c) - offsetof(ocr::ColumnsOwned, view));
+}
+
 static std::vector<std::vector<ocr::geom::Pt>> csr_polys(const uint32_t* xy, const int32_t* offsets, int n) {
   std::vector<std::vector<ocr::geom::Pt>> out(n);
   for (int k = 0; k < n; ++k)

@@ -105,6 +105,28 @@ struct LinesOwned {
   }
 };
 
+// the library-owned storage behind an ocr_columns_t* (released by ocr_columns_free)
+struct ColumnsOwned {
+  ocr_columns_t view;
+  std::vector<int32_t> img_offsets, block_offsets, line_offsets, order, word_flags, line_flags, block_levels;
+  std::vector<double> gaps, block_quads;
+  void finish() {
+    view.n_images = (int32_t)img_offsets.size() - 1;
+    view.n_words = (int32_t)order.size();
+    view.n_lines = (int32_t)line_offsets.size() - 1;
+    view.n_blocks = (int32_t)block_offsets.size() - 1;
+    view.img_offsets = img_offsets.data();
+    view.block_offsets = block_offsets.data();
+    view.line_offsets = line_offsets.data();
+    view.order = order.data();
+    view.word_flags = word_flags.data();
+    view.gaps = gaps.data();
+    view.line_flags = line_flags.data();
+    view.block_levels = block_levels.data();
+    view.block_quads = block_quads.data();
+  }
+};
+
 // comm.hip
 class Comm;
 std::vector<uint8_t> pack_shard(const ocr_polygons_t& p);

@@ -278,6 +278,30 @@ void launch_group_lines(const double* quads_dev, const int32_t* img_off_dev, int
                         void* feat_dev, int32_t* link_dev, int32_t* order_dev, int32_t* flags_dev, double* gaps_dev,
                         int32_t* line_start_dev, int32_t* n_lines_dev, hipStream_t s);
 
+// column-aware reading order (columns.hip; rule: include/ocr_amd.h ocr_group_columns, tests/column_oracle.py).  Stage A is
+// launch_group_lines with row_gap as max_gap, into the first seven buffers; everything else is indexed by batch-global word (image
+// slice + image-local index).  Results by image slice: order / gaps by position, line_start[l] batch-global positions, line_flags[l],
+// block_start[k] image-local line numbers, block_levels[k], block_quads[k][8], counts[2 b] lines and counts[2 b + 1] blocks of image b.
+constexpr size_t kColumnGapBytes = 72, kColumnLineBytes = 104, kColumnBlockBytes = 64;
+struct ColumnParams {
+  double height_ratio, min_cos, max_gap, min_gutter, gutter_reach, min_overlap, block_reach;
+  int32_t min_rows, max_levels;
+};
+struct ColumnBuffers {
+  void* feat;                                                // kLineFeatBytes per word
+  int32_t *link, *row_order, *flags, *row_start, *n_rows;    // stage A (link: 2 x n_words, reused by stages B and D)
+  double* row_gaps;
+  int32_t *row_prev, *row_pos, *gap_state, *line_state, *line_head, *line_len, *line_cut;
+  double* gap_by_word;
+  void *gap_rec, *line_rec, *block_rec;                      // kColumnGapBytes / kColumnLineBytes / kColumnBlockBytes per word
+  double* block_quads_by_slot;                               // 8 per word
+  uint32_t* pred_bits;                                       // ceil(max_words / 32) words per word: the "precedes" bit matrices
+  int32_t *order, *line_start, *line_flags, *block_start, *block_levels, *counts;
+  double *gaps, *block_quads;
+};
+void launch_group_columns(const double* quads_dev, const int32_t* img_off_dev, int n_images, int n_words, int max_words,
+                          const LineParams& row_params, const ColumnParams& p, const ColumnBuffers& b, hipStream_t s);
+
 // recognition net (rec_net.hip): conv1 + pool + conv2 + pool on the matrix cores -> feat [n][1024]; fc1 runs as a
 // conv_igemm 1x1 GEMM over the whole batch; fc2 + softmax(f64) + top-1 in one kernel
 struct RecWeights {

@@ -12,6 +12,7 @@
 //   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words,
 //     or through curved strips (ocr_plan_curved_strips / ocr_extract_curved_strips), for words that bend
 //   group_lines / read_lines: the words of every page grouped into text lines in reading order (ocr_group_lines), the "output text" step
+//   group_columns / read_columns: the same with columns: blocks in reading order, their lines top to bottom (ocr_group_columns)
 #pragma once
 #include <algorithm>
 #include <array>
@@ -504,18 +505,15 @@ struct LineReading {
   std::vector<int32_t> word_indices;
   std::vector<double> gaps;
 };
-// read_words_rectified for the texts, ocr_plan_word_strips for the quads (always: the curved plan carries none, and word order equals
-// polygon order in every reading call), ocr_group_lines for the lines; per image, its lines in reading order.
-inline std::vector<std::vector<LineReading>> read_lines(
-    const text_detection::FuncT& det_net, const char_recognition::Net& rec_net, const Tensor& frames,
-    const text_detection::metrics::PolygonScores& ps, const std::vector<double>& adjust_values,
-    const ocr_line_params_t* line_params = nullptr, const ocr_strip_params_t* strip_params = nullptr,
-    const ocr_segment_params_t* params = nullptr, const ocr_cc_params_t* cc = nullptr, const ocr_mask_params_t* mask = nullptr,
-    const ocr_curve_params_t* curved = nullptr) {
-  const auto words = read_words_rectified(det_net, rec_net, frames, ps, adjust_values, strip_params, params, cc, mask, curved);
-  std::vector<int32_t> img_off{0}, poly_off{0};
+// The quads of every detected word (ocr_plan_word_strips; always: the curved plan carries none, and word order equals polygon order in
+// every reading call) and the word range of every image.
+inline std::vector<double> word_quads(const Tensor& frames, const text_detection::metrics::PolygonScores& ps,
+                                      const std::vector<double>& adjust_values, const ocr_strip_params_t* strip_params,
+                                      std::vector<int32_t>& img_off) {
+  std::vector<int32_t> poly_off{0};
   std::vector<uint32_t> xy;
   std::vector<double> scores;
+  img_off.assign(1, 0);
   for (const auto& image : ps.polygons) {
     for (const auto& poly : image) {
       for (const auto& v : poly) {
@@ -533,6 +531,18 @@ inline std::vector<std::vector<LineReading>> read_lines(
   check(ocr_plan_word_strips(&polys, adjust_values.data(), frames.n, frames.h, frames.w, strip_params, &st));
   const std::vector<double> quads(st->quads, st->quads + 8 * (size_t)st->n_words);
   ocr_word_strips_free(st);
+  return quads;
+}
+// read_words_rectified for the texts, word_quads for the quads, ocr_group_lines for the lines; per image, its lines in reading order.
+inline std::vector<std::vector<LineReading>> read_lines(
+    const text_detection::FuncT& det_net, const char_recognition::Net& rec_net, const Tensor& frames,
+    const text_detection::metrics::PolygonScores& ps, const std::vector<double>& adjust_values,
+    const ocr_line_params_t* line_params = nullptr, const ocr_strip_params_t* strip_params = nullptr,
+    const ocr_segment_params_t* params = nullptr, const ocr_cc_params_t* cc = nullptr, const ocr_mask_params_t* mask = nullptr,
+    const ocr_curve_params_t* curved = nullptr) {
+  const auto words = read_words_rectified(det_net, rec_net, frames, ps, adjust_values, strip_params, params, cc, mask, curved);
+  std::vector<int32_t> img_off;
+  const std::vector<double> quads = word_quads(frames, ps, adjust_values, strip_params, img_off);
   const Lines lines = group_lines(det_net, quads, img_off, line_params);
   std::vector<std::vector<LineReading>> out(frames.n);
   for (int b = 0; b < frames.n; ++b) {
@@ -553,6 +563,69 @@ inline std::vector<std::vector<LineReading>> read_lines(
 inline std::string page_text(const std::vector<LineReading>& lines) {
   std::string s;
   for (size_t l = 0; l < lines.size(); ++l) s += (l ? "\n" : "") + lines[l].text;
+  return s;
+}
+
+// ocr_group_columns: the arguments of group_lines.  Block k of image b, for k in [img_offsets[b], img_offsets[b + 1]), is the lines
+// [block_offsets[k], block_offsets[k + 1]); line l is order[line_offsets[l] .. line_offsets[l + 1]).
+struct Columns {
+  std::vector<int32_t> img_offsets, block_offsets, line_offsets, order, word_flags, line_flags, block_levels;
+  std::vector<double> gaps, block_quads;
+};
+inline Columns group_columns(const text_detection::FuncT& det_net, const std::vector<double>& quads,
+                             const std::vector<int32_t>& word_img_offsets, const ocr_column_params_t* params = nullptr) {
+  if (word_img_offsets.empty() || quads.size() != 8 * (size_t)word_img_offsets.back())
+    throw Error(OCR_ERR_INVALID, "quads do not match the word offsets");
+  ocr_columns_t* c = nullptr;
+  check(ocr_group_columns(det_net.handle(), quads.data(), word_img_offsets.data(), (int)word_img_offsets.size() - 1, params, &c));
+  Columns out;
+  out.img_offsets.assign(c->img_offsets, c->img_offsets + c->n_images + 1);
+  out.block_offsets.assign(c->block_offsets, c->block_offsets + c->n_blocks + 1);
+  out.line_offsets.assign(c->line_offsets, c->line_offsets + c->n_lines + 1);
+  out.order.assign(c->order, c->order + c->n_words);
+  out.word_flags.assign(c->word_flags, c->word_flags + c->n_words);
+  out.gaps.assign(c->gaps, c->gaps + c->n_words);
+  out.line_flags.assign(c->line_flags, c->line_flags + c->n_lines);
+  out.block_levels.assign(c->block_levels, c->block_levels + c->n_blocks);
+  out.block_quads.assign(c->block_quads, c->block_quads + 8 * (size_t)c->n_blocks);
+  ocr_columns_free(c);
+  return out;
+}
+// read_lines with columns (ocr_group_columns): per image its blocks in reading order, per block its lines top to bottom.
+inline std::vector<std::vector<std::vector<LineReading>>> read_columns(
+    const text_detection::FuncT& det_net, const char_recognition::Net& rec_net, const Tensor& frames,
+    const text_detection::metrics::PolygonScores& ps, const std::vector<double>& adjust_values,
+    const ocr_column_params_t* column_params = nullptr, const ocr_strip_params_t* strip_params = nullptr,
+    const ocr_segment_params_t* params = nullptr, const ocr_cc_params_t* cc = nullptr, const ocr_mask_params_t* mask = nullptr,
+    const ocr_curve_params_t* curved = nullptr) {
+  const auto words = read_words_rectified(det_net, rec_net, frames, ps, adjust_values, strip_params, params, cc, mask, curved);
+  std::vector<int32_t> img_off;
+  const std::vector<double> quads = word_quads(frames, ps, adjust_values, strip_params, img_off);
+  const Columns cols = group_columns(det_net, quads, img_off, column_params);
+  std::vector<std::vector<std::vector<LineReading>>> out(frames.n);
+  for (int b = 0; b < frames.n; ++b) {
+    for (int k = cols.img_offsets[b]; k < cols.img_offsets[b + 1]; ++k) {
+      std::vector<LineReading> block;
+      for (int l = cols.block_offsets[k]; l < cols.block_offsets[k + 1]; ++l) {
+        LineReading r;
+        for (int p = cols.line_offsets[l]; p < cols.line_offsets[l + 1]; ++p) {
+          const int w = cols.order[p] - img_off[b];
+          const std::string& t = words[b][w].text;
+          if (!t.empty()) r.text += (r.text.empty() ? "" : " ") + t;
+          r.word_indices.push_back(w);
+          r.gaps.push_back(cols.gaps[p]);
+        }
+        block.push_back(std::move(r));
+      }
+      out[b].push_back(std::move(block));
+    }
+  }
+  return out;
+}
+// the lines of every block joined with "\n", the blocks separated by an empty line
+inline std::string page_text(const std::vector<std::vector<LineReading>>& blocks) {
+  std::string s;
+  for (size_t k = 0; k < blocks.size(); ++k) s += (k ? "\n\n" : "") + page_text(blocks[k]);
   return s;
 }
 

@@ -21,7 +21,9 @@ recognition -> output text), composed over the C ABI.
         read_words_rectified (or read_words) for the texts, then
         ocr_plan_word_strips      every word -> its oriented rectangle                    (the quads)
         ocr_group_lines           the words of every page -> text lines in reading order  (csrc/lines.hip)
-    page_text(lines) joins the lines of one image with "\n".
+    read_columns(det_net, rec_net, frames, polygon_scores, adjust_values)
+        the same with ocr_group_columns in place of ocr_group_lines: blocks (columns) in reading order, lines within (csrc/columns.hip)
+    page_text(lines) joins the lines of one image with "\n"; page_text(blocks, columns=True) separates blocks by an empty line.
 
     Every reading call takes lexicon=capi.Lexicon (with lexicon_params and max_penalty): the glyph posteriors of every word are then
     matched against the word list on the device, between the classify call and the texts:
@@ -295,6 +297,21 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     return out
 
 
+def _words_and_strips(who, det_net, rec_net, frames, polygon_scores, adjust_values, rectified, reading_kwargs):
+    """the words of a batch read (rectified or not) and the word strips planned for their quads -> (detector handle, words, strips)"""
+    det = _handle(det_net, capi.Detector)
+    if rectified:
+        words = read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, **reading_kwargs)
+    else:
+        if "strip_params" in reading_kwargs or "curved" in reading_kwargs:
+            raise TypeError(f"{who}: strip_params and curved belong to rectified=True")
+        words = read_words(det_net, rec_net, frames, polygon_scores, adjust_values, **reading_kwargs)
+    polys = getattr(polygon_scores, "polygons", polygon_scores)
+    _, _, h, w = frames.shape
+    strips = det.plan_word_strips(polys, adjust_values, h, w, reading_kwargs.get("strip_params"), getattr(polygon_scores, "scores", None))
+    return det, words, strips
+
+
 def read_lines(det_net, rec_net, frames, polygon_scores, adjust_values, line_params=None, rectified=True, **reading_kwargs
                ) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch and groups the words of every image into text lines in reading order (ocr_group_lines).
@@ -306,16 +323,8 @@ def read_lines(det_net, rec_net, frames, polygon_scores, adjust_values, line_par
     Returns per image a list of lines (text, word_indices, gaps): word_indices are the image's polygon indices in reading order (int32),
     gaps[k] the gap in front of word k of the line in units of the taller neighbour's height (0.0 for the first), text the non-empty
     word texts joined by one space."""
-    det = _handle(det_net, capi.Detector)
-    if rectified:
-        words = read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, **reading_kwargs)
-    else:
-        if "strip_params" in reading_kwargs or "curved" in reading_kwargs:
-            raise TypeError("read_lines: strip_params and curved belong to rectified=True")
-        words = read_words(det_net, rec_net, frames, polygon_scores, adjust_values, **reading_kwargs)
-    polys = getattr(polygon_scores, "polygons", polygon_scores)
-    n, _, h, w = frames.shape
-    strips = det.plan_word_strips(polys, adjust_values, h, w, reading_kwargs.get("strip_params"), getattr(polygon_scores, "scores", None))
+    det, words, strips = _words_and_strips("read_lines", det_net, rec_net, frames, polygon_scores, adjust_values, rectified, reading_kwargs)
+    n = frames.shape[0]
     lines = det.group_lines(strips.quads, strips.img_offsets, line_params)
     # one pass over the lines of the batch: slices of the batch's arrays (views), the texts by batch-global word index
     texts = [wd[0] for page in words for wd in page]
@@ -332,6 +341,36 @@ def read_lines(det_net, rec_net, frames, polygon_scores, adjust_values, line_par
     return out
 
 
-def page_text(lines) -> str:
-    """The lines of one image (an element of read_lines' result) joined with "\n"."""
+def read_columns(det_net, rec_net, frames, polygon_scores, adjust_values, column_params=None, rectified=True, **reading_kwargs
+                 ) -> List[List[List[Tuple[str, np.ndarray, np.ndarray]]]]:
+    """read_lines with columns: the words of every image as blocks (columns, paragraphs) in reading order (ocr_group_columns), so that a
+    two-column page reads down its left column before its right one.
+
+    Arguments as read_lines; column_params: capi.ColumnParams, a dict of its fields (the line fields among them) or None for the
+    defaults.  Returns per image a list of blocks, each a list of lines (text, word_indices, gaps) as read_lines returns them, top to
+    bottom."""
+    det, words, strips = _words_and_strips("read_columns", det_net, rec_net, frames, polygon_scores, adjust_values, rectified, reading_kwargs)
+    cols = det.group_columns(strips.quads, strips.img_offsets, column_params)
+    texts = [wd[0] for page in words for wd in page]
+    order = cols.order.tolist()
+    local = cols.order - np.repeat(strips.img_offsets[:-1], np.diff(strips.img_offsets))[cols.order]
+    img_off, blk_off, line_off = cols.img_offsets.tolist(), cols.block_offsets.tolist(), cols.line_offsets.tolist()
+    out = []
+    for b in range(frames.shape[0]):
+        page = []
+        for k in range(img_off[b], img_off[b + 1]):
+            block = []
+            for l in range(blk_off[k], blk_off[k + 1]):
+                p0, p1 = line_off[l], line_off[l + 1]
+                block.append((" ".join(filter(None, [texts[w] for w in order[p0:p1]])), local[p0:p1], cols.gaps[p0:p1]))
+            page.append(block)
+        out.append(page)
+    return out
+
+
+def page_text(lines, columns=False) -> str:
+    """The lines of one image (an element of read_lines' result) joined with "\n".  columns=True takes an element of read_columns'
+    result: the lines of every block joined with "\n", the blocks separated by an empty line."""
+    if columns:
+        return "\n\n".join("\n".join(text for text, _, _ in block) for block in lines)
     return "\n".join(text for text, _, _ in lines)
