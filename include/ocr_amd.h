@@ -884,6 +884,60 @@ int  ocr_lexicon_match(ocr_rec_t* rec, const ocr_lexicon_t* lex, const float* co
                        ocr_lexicon_matches_t** out);
 void ocr_lexicon_matches_free(ocr_lexicon_matches_t* m);
 
+/* EXTENSION - character language model: the glyphs of a word decoded as the cheapest paths through their classes under glyph cost
+ * plus character-to-character transition cost (BUILD-DEFINED, like the lexicon rule; the reference has no counterpart).  It reads words
+ * that no list contains and returns the k best readings with their costs.
+ *
+ * The model T: 64 x 64 f32, row-major, T[p*64 + c] the cost of class c behind class p.  Rows and columns 0..61 are the classes of
+ * ocr_rec_alphabet, row 62 is begin-of-word, column 62 is end-of-word.  Every used value is finite and >= 0; row 63, column 63 and the
+ * cell [62][62] are unused and must be 0.  Anything else is OCR_ERR_INVALID at create, and the message names the first offending cell.
+ * The model is uploaded once to the recogniser's GPU and bound to it: a decode through a recogniser of another device is
+ * OCR_ERR_INVALID.  Destroying waits for the work queued on its GPU. */
+#define OCR_LM_MAX_LEN 32         /* glyphs per decoded word */
+typedef struct ocr_char_lm ocr_char_lm_t;
+int  ocr_char_lm_create(ocr_rec_t* rec, const float* trans /* 64*64 */, ocr_char_lm_t** out);
+void ocr_char_lm_destroy(ocr_char_lm_t* lm);
+
+/* The decode.  costs n_glyphs x 62 f32 in mem_kind memory (ocr_rec_glyph_costs), word_offsets [n_words+1] in host memory: word w owns
+ * the glyph rows [word_offsets[w], word_offsets[w+1]).
+ * Rule.  All arithmetic is f64 on the f32 values widened, every operation rounded on its own, adds and mins only.  For a word with glyph
+ * rows r_0..r_(G-1), 1 <= G <= OCR_LM_MAX_LEN:
+ *   D_0[c]   = T[62][c] + cost[r_0][c]
+ *   D_i[c]   = min_p (D_(i-1)[p] + T[p][c])  +  cost[r_i][c]       (the transition is added first, the glyph cost second)
+ *   total[c] = D_(G-1)[c] + T[c][62]
+ * With top_k = K > 1 every state keeps a list: L_0[c] holds D_0[c] alone.  The candidates of state (i, c) are L_(i-1)[p][r] + T[p][c]
+ * over all p < 62 and r < the length of L_(i-1)[p]; they are ordered by (value, p, r) ascending, cut to the first K, and then
+ * cost[r_i][c] is added to each: that is L_i[c].  The word's outputs are the first K of L_(G-1)[c][r] + T[c][62] by (value, c, r), and
+ * the classes of hypothesis k are read back along the (p, r) links.  The key is a total order, so the result does not depend on how
+ * the kernel lays anything out; a rounded add is monotone, so the K costs are the K smallest path costs, each summed left to right in
+ * the association above.  Since 62^G > 8 every decoded word has top_k hypotheses, and they are distinct strings.
+ * Outputs: costs[w*top_k + k]; labels[k*n_glyphs + row] the class of glyph `row` in hypothesis k (-1 in the rows of words that were not
+ * decoded); raw_costs[w] the model cost of the greedy reading - the first minimum class of every glyph, the same association, begin
+ * and end transitions included, so costs[w*top_k] <= raw_costs[w]; word_flags[w]: 1 for G = 0 (costs +inf, raw cost 0.0), 2 for
+ * G > OCR_LM_MAX_LEN (not decoded: costs +inf, labels -1; its raw cost is summed like any other word's).
+ * OCR_ERR_INVALID for a null pointer (params == NULL -> the defaults; costs may be NULL when n_glyphs = 0), a bad mem_kind, offsets
+ * that do not start at 0, decrease or do not end at n_glyphs, top_k out of range or a nonzero reserved field, a model of another
+ * device, and a cost that is NaN, +-inf or negative (found on the device in the same pass; the message names the first such word).
+ * The handle stays usable.  n_words = 0 launches nothing and returns an empty block.  The call runs on the recogniser's stream behind
+ * what is queued there, and blocks.  Oracle: tests/char_lm_oracle.py; kernel: csrc/char_lm.hip (one wave per word, class c in lane
+ * c, the model in LDS, the lists in registers, back-pointers in a per-call device buffer). */
+typedef struct ocr_lm_params {
+  int32_t top_k;         /* 1..8, default 1 */
+  int32_t reserved[3];   /* must be 0 */
+} ocr_lm_params_t;
+typedef struct ocr_lm_paths {
+  int32_t n_words, top_k, n_glyphs;
+  const int32_t* labels;       /* [top_k*n_glyphs] class per hypothesis and glyph row, -1 where the word was not decoded */
+  const double*  costs;        /* [n_words*top_k] ascending per word, +inf where the word was not decoded                */
+  const double*  raw_costs;    /* [n_words] the greedy reading under the model                                           */
+  const int32_t* word_flags;   /* [n_words] 1 no glyphs, 2 more than 32 glyphs                                           */
+} ocr_lm_paths_t;
+void ocr_lm_default_params(ocr_lm_params_t* p);
+/* *out: ocr_lm_paths_free. */
+int  ocr_lm_decode(ocr_rec_t* rec, const ocr_char_lm_t* lm, const float* costs, int n_glyphs, int mem_kind,
+                   const int32_t* word_offsets, int n_words, const ocr_lm_params_t* params, ocr_lm_paths_t** out);
+void ocr_lm_paths_free(ocr_lm_paths_t* p);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU exchange.  Frames and crops are independent (eval-mode batch norm), so a batch shards over the GPUs of
  * a node with no data-path collective: one process (or thread) per GPU, each with its own detector / recogniser

@@ -41,6 +41,7 @@ EXPORTS = [
     "ocr_rec_forward", "ocr_rec_classify_async", "ocr_rec_classify_profile", "ocr_rec_classify", "ocr_rec_alphabet", "ocr_ctc_greedy_decode",
     "ocr_rec_glyph_costs", "ocr_lexicon_create", "ocr_lexicon_size", "ocr_lexicon_destroy", "ocr_lexicon_default_params", "ocr_lexicon_match",
     "ocr_lexicon_matches_free",
+    "ocr_char_lm_create", "ocr_char_lm_destroy", "ocr_lm_default_params", "ocr_lm_decode", "ocr_lm_paths_free",
     "ocr_ctc_beam_decode",
     "ocr_comm_unique_id", "ocr_comm_rccl_version", "ocr_comm_create", "ocr_comm_destroy",
     "ocr_comm_all_gather_polygons", "ocr_comm_all_gather_labels",
@@ -166,9 +167,25 @@ class LexiconMatchesBlock(C.Structure):
                 ("raw_costs", C.POINTER(C.c_double)), ("n_candidates", C.POINTER(C.c_int32)), ("word_flags", C.POINTER(C.c_int32))]
 
 
+class LmParams(C.Structure):
+    """ocr_lm_params_t."""
+    _fields_ = [("top_k", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class LmPathsBlock(C.Structure):
+    """ocr_lm_paths_t."""
+    _fields_ = [("n_words", C.c_int32), ("top_k", C.c_int32), ("n_glyphs", C.c_int32), ("labels", C.POINTER(C.c_int32)),
+                ("costs", C.POINTER(C.c_double)), ("raw_costs", C.POINTER(C.c_double)), ("word_flags", C.POINTER(C.c_int32))]
+
+
 LEX_MAX_LEN = 32
 LEX_MAX_ENTRIES = 1 << 22
 LEX_CHUNK = 256   # entries per pass of a match workgroup (csrc/lexicon_host.hpp kLexChunk): lexicon sizes around it change the grid
+
+LM_MAX_LEN = 32
+LM_WORDS = 4      # words per workgroup of the decode kernel (csrc/char_lm_host.hpp kLmWords): word counts around it change the grid
+LM_BEGIN = 62     # the model's row of begin-of-word
+LM_END = 62       # ... and its column of end-of-word
 
 _lib = None
 _hip_shared = False
@@ -325,6 +342,15 @@ def lib() -> C.CDLL:
                                         C.POINTER(C.POINTER(LexiconMatchesBlock))]
         L.ocr_lexicon_matches_free.argtypes = [C.POINTER(LexiconMatchesBlock)]
         L.ocr_lexicon_matches_free.restype = None
+        L.ocr_char_lm_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.ocr_char_lm_destroy.argtypes = [C.c_void_p]
+        L.ocr_char_lm_destroy.restype = None
+        L.ocr_lm_default_params.argtypes = [C.POINTER(LmParams)]
+        L.ocr_lm_default_params.restype = None
+        L.ocr_lm_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(LmParams),
+                                    C.POINTER(C.POINTER(LmPathsBlock))]
+        L.ocr_lm_paths_free.argtypes = [C.POINTER(LmPathsBlock)]
+        L.ocr_lm_paths_free.restype = None
         L.ocr_rec_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_rec_destroy.argtypes = [C.c_void_p]
         L.ocr_rec_destroy.restype = None
@@ -1054,6 +1080,148 @@ class Lexicon:
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
             lib().ocr_lexicon_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_ALPHABET = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789"
+
+
+def char_lm_table(words, counts=None, alpha: float = 0.5, weight: float = 1.0) -> np.ndarray:
+    """A bigram model for ocr_char_lm_create from a word list, on the host: 64 x 64 f32, [p, c] the cost of class c behind class p, row 62
+    begin-of-word, column 62 end-of-word.  Every word contributes its bigrams (begin, c_0), (c_0, c_1) .. (c_last, end), counts[k] times
+    (once without counts); a row's 63 successors - the 62 classes and end-of-word, for the begin row the 62 classes - are smoothed by
+    adding alpha to each count, and the cost is -log(probability) in f64 times weight, rounded to f32.  An empty word adds nothing.  A
+    character outside the alphabet is OcrError."""
+    if not (alpha > 0 and np.isfinite(alpha)) or not (weight >= 0 and np.isfinite(weight)):
+        raise OcrError(1, f"char_lm_table: alpha={alpha} weight={weight} (alpha > 0, weight >= 0, both finite)")
+    words = list(words)
+    cnt = np.ones(len(words), np.float64) if counts is None else np.asarray(counts, np.float64).reshape(-1)
+    if len(cnt) != len(words) or not np.all(np.isfinite(cnt)) or np.any(cnt < 0):
+        raise OcrError(1, "char_lm_table: counts must be finite, >= 0 and one per word")
+    cls = {ch: k for k, ch in enumerate(_ALPHABET)}
+    n = np.zeros((64, 64), np.float64)
+    for k, w in enumerate(words):
+        if isinstance(w, bytes):
+            w = w.decode("latin-1")
+        prev = LM_BEGIN
+        for ch in w:
+            c = cls.get(ch)
+            if c is None:
+                raise OcrError(1, f"char_lm_table: word {k} holds {ch!r}, which is not in the alphabet")
+            n[prev, c] += cnt[k]
+            prev = c
+        if w:
+            n[prev, LM_END] += cnt[k]
+    used = np.zeros((64, 64), bool)
+    used[:63, :63] = True
+    used[LM_BEGIN, LM_END] = False
+    sm = np.where(used, n + float(alpha), 0.0)
+    prob = sm / np.maximum(sm.sum(axis=1, keepdims=True), np.finfo(np.float64).tiny)
+    with np.errstate(divide="ignore"):
+        cost = np.where(used, -np.log(np.where(used, prob, 1.0)) * float(weight), 0.0)
+    return np.where(used, np.maximum(cost, 0.0), 0.0).astype(np.float32)
+
+
+def lm_params(**fields) -> LmParams:
+    """ocr_lm_default_params with the given fields overridden (top_k)."""
+    p = LmParams()
+    lib().ocr_lm_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k == "reserved":
+            p.reserved[0], p.reserved[1], p.reserved[2] = (int(x) for x in v)
+        elif k == "top_k":
+            p.top_k = int(v)
+        else:
+            raise TypeError(f"unknown language-model parameter {k!r}")
+    return p
+
+
+def _as_lm_params(params) -> Optional[LmParams]:
+    if params is None or isinstance(params, LmParams):
+        return params
+    return lm_params(**params)
+
+
+class LmPaths:
+    """The arrays of an ocr_lm_paths_t, copied into numpy: labels top_k x n_glyphs int32 (the class of every glyph row per hypothesis, -1
+    where the word was not decoded), costs n_words x top_k f64 (+inf where it was not), raw_costs [n_words] f64 (the greedy reading under
+    the model), word_flags [n_words] (1 no glyphs, 2 more than 32 glyphs)."""
+
+    def __init__(self, labels, costs, raw_costs, word_flags):
+        self.labels = np.ascontiguousarray(labels, dtype=np.int32)
+        self.costs = np.ascontiguousarray(costs, dtype=np.float64)
+        self.raw_costs = np.ascontiguousarray(raw_costs, dtype=np.float64)
+        self.word_flags = np.ascontiguousarray(word_flags, dtype=np.int32)
+
+    @property
+    def n_words(self) -> int:
+        return self.costs.shape[0]
+
+    @property
+    def top_k(self) -> int:
+        return self.costs.shape[1]
+
+    def text(self, word_offsets, w: int, k: int = 0) -> str:
+        """hypothesis k of word w as a string ("" for a word that was not decoded)"""
+        g0, g1 = int(word_offsets[w]), int(word_offsets[w + 1])
+        lab = self.labels[k, g0:g1]
+        return "".join(_ALPHABET[int(c)] for c in lab) if len(lab) and lab[0] >= 0 else ""
+
+    def texts(self, word_offsets, k: int = 0) -> list:
+        """hypothesis k of every word as a string ("" for a word that was not decoded), in one pass over the labels"""
+        off = np.asarray(word_offsets, np.int64)
+        lab = self.labels[k] if self.labels.shape[1] else np.zeros(0, np.int32)
+        flat = np.frombuffer((_ALPHABET + "?").encode(), np.uint8)[np.where(lab >= 0, lab, 62)].tobytes().decode()
+        return [flat[int(off[w]):int(off[w + 1])] if self.word_flags[w] == 0 else "" for w in range(len(off) - 1)]
+
+    @staticmethod
+    def from_block(mp) -> "LmPaths":
+        s = mp.contents
+        nw, k, ng = s.n_words, s.top_k, s.n_glyphs
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return LmPaths(arr(s.labels, k * ng, np.int32).reshape(k, ng), arr(s.costs, nw * k, np.float64).reshape(nw, k),
+                       arr(s.raw_costs, nw, np.float64), arr(s.word_flags, nw, np.int32))
+
+
+class CharLm:
+    """Owner of an ocr_char_lm_t: a 64 x 64 bigram cost table (char_lm_table), uploaded once to the recogniser's GPU and resident there
+    until close() (or the end of a `with` block)."""
+
+    def __init__(self, rec: "Recognizer", table):
+        self._h = C.c_void_p()
+        t = np.ascontiguousarray(table, dtype=np.float32)
+        if t.size != 64 * 64:
+            raise OcrError(1, f"char lm: expected a 64 x 64 table, got shape {tuple(t.shape)}")
+        self.table = t.reshape(64, 64).copy()
+        check(lib().ocr_char_lm_create(rec._h, _ptr(self.table), C.byref(self._h)))
+
+    @classmethod
+    def from_words(cls, rec: "Recognizer", words, counts=None, alpha: float = 0.5, weight: float = 1.0) -> "CharLm":
+        return cls(rec, char_lm_table(words, counts, alpha, weight))
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise OcrError(1, "char lm already closed")
+        return self._h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().ocr_char_lm_destroy(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -1949,6 +2117,26 @@ class Recognizer:
 
     def lexicon_match_device(self, lex: "Lexicon", costs_ptr: int, n_glyphs: int, word_offsets, params=None) -> LexiconMatches:
         return self._lexicon_match(lex, C.c_void_p(costs_ptr or None), n_glyphs, MEM_DEVICE, word_offsets, params)
+
+    def _lm_decode(self, lm, costs_ptr, n_glyphs: int, mem_kind: int, word_offsets, params) -> LmPaths:
+        off = np.ascontiguousarray(word_offsets, dtype=np.int32).reshape(-1)
+        prm = _as_lm_params(params)
+        out = C.POINTER(LmPathsBlock)()
+        check(lib().ocr_lm_decode(self._h, lm.handle if isinstance(lm, CharLm) else lm, costs_ptr, n_glyphs, mem_kind,
+                                  _ptr(off) if off.size else None, len(off) - 1, C.byref(prm) if prm is not None else None, C.byref(out)))
+        try:
+            return LmPaths.from_block(out)
+        finally:
+            lib().ocr_lm_paths_free(out)
+
+    def lm_decode(self, lm: "CharLm", costs: np.ndarray, word_offsets, params=None) -> LmPaths:
+        """ocr_lm_decode: costs n_glyphs x 62 f32 in host memory (glyph_costs), word_offsets [n_words+1] the glyph range per word
+        (GlyphSet.word_offsets); params: LmParams, a dict of its fields, or None (defaults).  Blocking, on the handle's stream."""
+        x = np.ascontiguousarray(costs, dtype=np.float32).reshape(-1, 62)
+        return self._lm_decode(lm, _ptr(x) if x.size else None, x.shape[0], MEM_HOST, word_offsets, params)
+
+    def lm_decode_device(self, lm: "CharLm", costs_ptr: int, n_glyphs: int, word_offsets, params=None) -> LmPaths:
+        return self._lm_decode(lm, C.c_void_p(costs_ptr or None), n_glyphs, MEM_DEVICE, word_offsets, params)
 
 
 def python_to_polygons(polys, scores):

@@ -15,7 +15,7 @@ struct ocr_det {
 struct ocr_rec {
   ocr::Recognizer impl;
   int32_t* ctc_bad_crop = nullptr;   // device int of ocr_ctc_beam_decode: the lowest crop with a non-finite logit (allocated on first use)
-  void* lex_ws = nullptr;            // device workspace of the lexicon calls (lexicon.hip): grown on demand
+  void* lex_ws = nullptr;            // device workspace of the lexicon and language-model calls: grown on demand
   size_t lex_ws_bytes = 0;
   ocr_rec(const void* b, size_t n, int d) : impl(b, n, d) {}
   ~ocr_rec() {
@@ -64,6 +64,20 @@ struct Carve {
 };
 template <typename T>
 T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+
+// the recogniser's workspace of the lexicon and language-model calls (lexicon.hip, char_lm.hip): grown on demand, released with the handle
+inline char* lex_workspace(ocr_rec* rec, size_t bytes) {
+  if (bytes > rec->lex_ws_bytes) {
+    OCR_HIP(hipStreamSynchronize(rec->impl.stream()));
+    if (rec->lex_ws) OCR_HIP(hipFree(rec->lex_ws));
+    rec->lex_ws = nullptr;
+    rec->lex_ws_bytes = 0;
+    const size_t want = bytes + bytes / 4;
+    OCR_HIP(hipMalloc(&rec->lex_ws, want));
+    rec->lex_ws_bytes = want;
+  }
+  return static_cast<char*>(rec->lex_ws);
+}
 
 // ctc_beam.hip (extension, no reference counterpart): CTC prefix beam search, one workgroup per crop; logits [n][t][c] f32 ->
 // labels [n][beam][t] (-1 padded), lengths [n][beam] (-1: unused slot), scores [n][beam] f64.  *bad_crop_dev is lowered (atomicMin) to

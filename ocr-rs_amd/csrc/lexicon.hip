@@ -279,19 +279,6 @@ struct MatchesOwned {   // the library-owned storage behind an ocr_lexicon_match
   }
 };
 
-// the recogniser's workspace of the lexicon calls: grown on demand, released with the handle
-char* lex_workspace(ocr_rec* rec, size_t bytes) {
-  if (bytes > rec->lex_ws_bytes) {
-    OCR_HIP(hipStreamSynchronize(rec->impl.stream()));
-    if (rec->lex_ws) OCR_HIP(hipFree(rec->lex_ws));
-    rec->lex_ws = nullptr;
-    rec->lex_ws_bytes = 0;
-    const size_t want = bytes + bytes / 4;
-    OCR_HIP(hipMalloc(&rec->lex_ws, want));
-    rec->lex_ws_bytes = want;
-  }
-  return static_cast<char*>(rec->lex_ws);
-}
 constexpr int32_t kNone = 0x7F7F7F7F;   // what a byte memset of 0x7F leaves: above every row and word index
 }  // namespace
 
@@ -309,7 +296,7 @@ int ocr_rec_glyph_costs(ocr_rec_t* rec, const float* logits, int n, float* costs
     const size_t bytes = (size_t)n * kLexClasses * 4;
     Carve c;
     const size_t o_bad = c.take(4), o_in = c.take(mem_kind == OCR_MEM_HOST ? bytes : 0), o_out = c.take(mem_kind == OCR_MEM_HOST ? bytes : 0);
-    char* ws = lex_workspace(rec, c.end);
+    char* ws = ocr::lex_workspace(rec, c.end);
     int32_t* bad_dev = at<int32_t>(ws, o_bad);
     OCR_HIP(hipMemsetAsync(bad_dev, 0x7F, 4, s));
     const float* in = logits;
@@ -412,7 +399,7 @@ int ocr_lexicon_match(ocr_rec_t* rec, const ocr_lexicon_t* lex, const float* cos
     const size_t o_bad = c.take(4), o_cost = c.take(mem_kind == OCR_MEM_HOST ? cost_bytes : 0), o_off = c.take((nw + 1) * 4);
     const size_t o_jobs = c.take(nw * sizeof(LexWordJob)), o_raw = c.take(nw * 8), o_ent = c.take(nw * k * 4), o_oc = c.take(nw * k * 8);
     const size_t o_pc = c.take(slots * 8), o_pi = c.take(slots * 4);
-    char* ws = lex_workspace(rec, c.end);
+    char* ws = ocr::lex_workspace(rec, c.end);
     int32_t* bad_dev = at<int32_t>(ws, o_bad);
     OCR_HIP(hipMemsetAsync(bad_dev, 0x7F, 4, s));
     const float* cost_dev = costs;

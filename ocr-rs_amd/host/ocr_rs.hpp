@@ -9,6 +9,7 @@
 //   char_recognition::Net::{new_, forward_t}, utils::topk        model.rs:13-39, utils.rs:28-43
 //   read_words: detected words -> glyphs -> text, the pipeline's segmentation step (README.md:20-26), which the reference never built
 //   Lexicon / glyph_costs / lexicon_match / read_words(.., lexicon): words read as a whole against a word list (ocr_lexicon_match)
+//   CharLm / lm_decode: words decoded under a character-bigram model from the same glyph costs, k best readings (ocr_lm_decode)
 //   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words,
 //     or through curved strips (ocr_plan_curved_strips / ocr_extract_curved_strips), for words that bend
 //   group_lines / read_lines: the words of every page grouped into text lines in reading order (ocr_group_lines), the "output text" step
@@ -354,6 +355,57 @@ inline std::vector<std::vector<WordReadingLexicon>> read_words(const text_detect
       ++k;
     }
   }
+  return out;
+}
+
+// ---- character language model (ocr_char_lm_create, ocr_lm_decode; the rule is stated in ocr_amd.h)
+// A 64 x 64 table of transition costs over VALUES (row 62 begin-of-word, column 62 end-of-word), uploaded once to the recogniser's GPU.
+class CharLm {
+ public:
+  CharLm(const char_recognition::Net& rec_net, const std::vector<float>& table) {
+    if (table.size() != 64 * 64) throw Error(OCR_ERR_INVALID, "the model is not 64 x 64");
+    check(ocr_char_lm_create(rec_net.handle(), table.data(), &h_));
+  }
+  ~CharLm() { ocr_char_lm_destroy(h_); }
+  CharLm(const CharLm&) = delete;
+  CharLm& operator=(const CharLm&) = delete;
+  const ocr_char_lm_t* handle() const { return h_; }
+
+ private:
+  ocr_char_lm_t* h_ = nullptr;
+};
+// labels are top_k x n_glyphs (-1 in the rows of words that were not decoded), costs n_words x top_k (+inf for such words); the
+// other two are per word
+struct LmPaths {
+  int top_k = 1, n_glyphs = 0;
+  std::vector<int32_t> labels, word_flags;
+  std::vector<double> costs, raw_costs;
+  // hypothesis k of the word with glyph rows [g0, g1): "" when it was not decoded
+  std::string text(int32_t g0, int32_t g1, int k = 0) const {
+    std::string t;
+    for (int32_t j = g0; j < g1; ++j) {
+      const int32_t c = labels[(size_t)k * n_glyphs + j];
+      if (c < 0) return std::string();
+      t.push_back(utils::VALUES()[c]);
+    }
+    return t;
+  }
+};
+inline LmPaths lm_decode(const char_recognition::Net& rec_net, const CharLm& lm, const std::vector<float>& costs,
+                         const std::vector<int32_t>& word_offsets, const ocr_lm_params_t* params = nullptr) {
+  if (word_offsets.empty() || costs.size() != 62 * (size_t)word_offsets.back()) throw Error(OCR_ERR_INVALID, "costs do not match the word offsets");
+  ocr_lm_paths_t* m = nullptr;
+  check(ocr_lm_decode(rec_net.handle(), lm.handle(), costs.empty() ? nullptr : costs.data(), (int)(costs.size() / 62), OCR_MEM_HOST,
+                      word_offsets.data(), (int)word_offsets.size() - 1, params, &m));
+  LmPaths out;
+  const size_t nw = (size_t)m->n_words, k = (size_t)m->top_k, ng = (size_t)m->n_glyphs;
+  out.top_k = m->top_k;
+  out.n_glyphs = m->n_glyphs;
+  out.labels.assign(m->labels, m->labels + k * ng);
+  out.costs.assign(m->costs, m->costs + nw * k);
+  out.raw_costs.assign(m->raw_costs, m->raw_costs + nw);
+  out.word_flags.assign(m->word_flags, m->word_flags + nw);
+  ocr_lm_paths_free(m);
   return out;
 }
 

@@ -29,10 +29,13 @@ recognition -> output text), composed over the C ABI.
     matched against the word list on the device, between the classify call and the texts:
         ocr_rec_glyph_costs       the classify call's logits -> negative log-softmax costs (csrc/lexicon.hip)
         ocr_lexicon_match         every word against every entry of an admissible length  (csrc/lexicon.hip)
+    ... and lm=capi.CharLm (with lm_params): every word is decoded under a character-bigram model from the same costs, which reads
+    words that no list contains:
+        ocr_lm_decode             every word -> its k cheapest readings under glyph + transition cost  (csrc/char_lm.hip)
 
 The segmentation, strip and line rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
 tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py, tests/strip_oracle.py, tests/curved_strip_oracle.py and
-tests/line_oracle.py; the lexicon rule likewise, restated in tests/lexicon_oracle.py.
+tests/line_oracle.py; the lexicon rule likewise, restated in tests/lexicon_oracle.py, and the language model's in tests/char_lm_oracle.py.
 """
 from __future__ import annotations
 
@@ -97,21 +100,24 @@ def _segment_and_crop(det, frames_ptr, n, h, w, polys, adjust_values, params, cc
     return glyphs, crops
 
 
-def _classify(rec, crops, ng: int, dev, word_offsets, lexicon, lexicon_params):
-    """classify on device crops -> (labels, probs, LexiconMatches or None); with a lexicon the same call also writes the logits, and
-    the costs and the match stay on the device."""
+def _classify(rec, crops, ng: int, dev, word_offsets, lexicon, lexicon_params, lm=None, lm_params=None):
+    """classify on device crops -> (labels, probs, LexiconMatches or None, LmPaths or None); with a lexicon or a language model the
+    same call also writes the logits, and the costs, the match and the decode stay on the device."""
     import torch
     if lexicon is not None and not isinstance(lexicon, capi.Lexicon):
         raise TypeError(f"lexicon: expected a capi.Lexicon, got {type(lexicon).__name__}")
+    if lm is not None and not isinstance(lm, capi.CharLm):
+        raise TypeError(f"lm: expected a capi.CharLm, got {type(lm).__name__}")
+    want_costs = lexicon is not None or lm is not None
     labels = np.zeros(0, np.int32)
     probs = np.zeros(0, np.float64)
     costs_ptr = 0
     if ng:
         lab = torch.empty(ng, dtype=torch.int32, device=dev)
         pr = torch.empty(ng, dtype=torch.float64, device=dev)
-        logits = torch.empty((ng, 62), dtype=torch.float32, device=dev) if lexicon is not None else None
+        logits = torch.empty((ng, 62), dtype=torch.float32, device=dev) if want_costs else None
         rec.classify_device(crops.data_ptr(), ng, logits.data_ptr() if logits is not None else 0, lab.data_ptr(), pr.data_ptr())
-        if lexicon is not None:
+        if want_costs:
             costs = torch.empty((ng, 62), dtype=torch.float32, device=dev)
             rec.glyph_costs_device(logits.data_ptr(), ng, costs.data_ptr())   # blocking, behind the classify call
             costs_ptr = costs.data_ptr()
@@ -121,21 +127,36 @@ def _classify(rec, crops, ng: int, dev, word_offsets, lexicon, lexicon_params):
     matches = None
     if lexicon is not None:
         matches = rec.lexicon_match_device(lexicon, costs_ptr, ng, word_offsets, lexicon_params)
-    return labels, probs, matches
+    paths = None
+    if lm is not None:
+        paths = rec.lm_decode_device(lm, costs_ptr, ng, word_offsets, lm_params)
+        paths.best = paths.texts(word_offsets)   # hypothesis 0 of every word, for _word
+    return labels, probs, matches, paths
 
 
-def _word(text: str, probs, where, k: int, n_glyphs: int, matches, lexicon, max_penalty: float):
+def _word(text: str, probs, where, k: int, n_glyphs: int, matches, lexicon, max_penalty: float, paths=None):
     """The tuple of word k: without a lexicon (text, probs, where); with one the text is the best entry's string when a candidate
-    exists and cost - raw_cost <= max_penalty * G (f64), and (entry index or -1, cost, raw_cost, raw text) is appended."""
-    if matches is None:
+    exists and cost - raw_cost <= max_penalty * G (f64), and (entry index or -1, cost, raw_cost, raw text) is appended.  With a
+    language model the text of a decoded word that the lexicon did not take is hypothesis 0's string, and (cost of hypothesis 0, the
+    greedy reading's cost under the model, raw text) is appended last."""
+    if matches is None and paths is None:
         return (text, probs, where)
-    e, c, r = int(matches.entries[k, 0]), float(matches.costs[k, 0]), float(matches.raw_costs[k])
-    take = e >= 0 and c - r <= float(max_penalty) * n_glyphs
-    return (lexicon.words[e] if take else text, probs, where, (e, c, r, text))
+    out, extra, take = text, [], False
+    if matches is not None:
+        e, c, r = int(matches.entries[k, 0]), float(matches.costs[k, 0]), float(matches.raw_costs[k])
+        take = e >= 0 and c - r <= float(max_penalty) * n_glyphs
+        if take:
+            out = lexicon.words[e]
+        extra.append((e, c, r, text))
+    if paths is not None:
+        if not take and int(paths.word_flags[k]) == 0:
+            out = paths.best[k]
+        extra.append((float(paths.costs[k, 0]), float(paths.raw_costs[k]), text))
+    return (out, probs, where, *extra)
 
 
 def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None, cc=None, mask=None, lexicon=None,
-               lexicon_params=None, max_penalty=1.5) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+               lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch.
 
     det_net: text_detection.FuncT or capi.Detector (supplies the GPU and stream of the segmentation); rec_net: char_recognition.Net
@@ -150,7 +171,12 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     lexicon: None, or a capi.Lexicon on the recogniser's GPU: every word is matched against it (ocr_lexicon_match with lexicon_params:
     capi.LexiconParams, a dict of its fields or None) and its tuple gains a fourth element (entry index or -1, cost, raw_cost, raw
     text); the text becomes the entry's string when a candidate exists and cost - raw_cost <= max_penalty * G for the word's G glyphs,
-    otherwise the raw text stays.  With lexicon=None nothing changes."""
+    otherwise the raw text stays.  With lexicon=None nothing changes.
+    lm: None, or a capi.CharLm on the recogniser's GPU: every word is decoded under it (ocr_lm_decode with lm_params: capi.LmParams, a
+    dict of its fields or None), the text of a decoded word becomes hypothesis 0's string, and the tuple gains (lm_cost, raw_cost,
+    raw_text) as its last element: the cost of hypothesis 0, the cost of the greedy reading under the model, the greedy text.  With
+    both lexicon and lm a word the lexicon accepted keeps the entry's string, the others take the model's, and the lexicon's element
+    comes first.  With lm=None nothing changes."""
     import torch
 
     det = _handle(det_net, capi.Detector)
@@ -171,14 +197,14 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     torch.cuda.current_stream(dev).synchronize()
     glyphs, crops = _segment_and_crop(det, x.data_ptr(), n, h, w, polys, adjust_values, params, cc, mask, dev)   # blocking
     ng = glyphs.n_glyphs
-    labels, probs, matches = _classify(rec, crops, ng, dev, glyphs.word_offsets, lexicon, lexicon_params)
+    labels, probs, matches, paths = _classify(rec, crops, ng, dev, glyphs.word_offsets, lexicon, lexicon_params, lm, lm_params)
     out = []
     for b in range(n):
         words = []
         for k in range(int(glyphs.img_offsets[b]), int(glyphs.img_offsets[b + 1])):
             g0, g1 = int(glyphs.word_offsets[k]), int(glyphs.word_offsets[k + 1])
             words.append(_word("".join(VALUES[int(c)] for c in labels[g0:g1]), probs[g0:g1].copy(), glyphs.boxes[g0:g1].copy(), k, g1 - g0,
-                               matches, lexicon, max_penalty))
+                               matches, lexicon, max_penalty, paths))
         out.append(words)
     return out
 
@@ -248,7 +274,7 @@ def _curved(curved, strip_params):
 
 
 def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None, cc=None, mask=None,
-                         curved=None, lexicon=None, lexicon_params=None, max_penalty=1.5) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+                         curved=None, lexicon=None, lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch through its upright strip: rotated words are read along their own axis, and with
     curved=True (or {} or a dict of capi.CurveParams' fields: strip_height, max_width, valid_pct) words that bend are read along their
     own centreline (ocr_plan_curved_strips, ocr_extract_curved_strips; the glyph quads then come from curved_glyph_quads).  curved=None
@@ -257,7 +283,7 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     Arguments as read_words; strip_params: capi.StripParams, a dict of its fields (strip_height, max_width) or None for the defaults;
     params, cc and mask: the segmentation parameters, rule and crop masking as in read_words, applied to the atlas.  Returns per image, per polygon: (text, probability of every character
     (f64), glyph quads k x 4 x 2 f64: the corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of every glyph box mapped back to frame
-    coordinates, strip_glyph_quads).  A flat word reads as "".  lexicon, lexicon_params and max_penalty as in read_words."""
+    coordinates, strip_glyph_quads).  A flat word reads as "".  lexicon, lexicon_params, max_penalty, lm and lm_params as in read_words."""
     import torch
 
     det = _handle(det_net, capi.Detector)
@@ -283,7 +309,7 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     with strips.polygon_block() as rects:
         glyphs, crops = _segment_and_crop(det, atlas.data_ptr(), 1, hs, tw, rects, [[1.0, 1.0]], params, cc, mask, dev)
     ng = glyphs.n_glyphs
-    labels, probs, matches = _classify(rec, crops, ng, dev, glyphs.word_offsets, lexicon, lexicon_params)
+    labels, probs, matches, paths = _classify(rec, crops, ng, dev, glyphs.word_offsets, lexicon, lexicon_params, lm, lm_params)
     quads = (strip_glyph_quads if cp is None else curved_glyph_quads)(
         strips, np.repeat(np.arange(glyphs.n_words), np.diff(glyphs.word_offsets)), glyphs.boxes)
     text = "".join(VALUES[int(c)] for c in labels)
@@ -292,7 +318,7 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
         words = []
         for k in range(int(strips.img_offsets[b]), int(strips.img_offsets[b + 1])):
             g0, g1 = int(glyphs.word_offsets[k]), int(glyphs.word_offsets[k + 1])
-            words.append(_word(text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy(), k, g1 - g0, matches, lexicon, max_penalty))
+            words.append(_word(text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy(), k, g1 - g0, matches, lexicon, max_penalty, paths))
         out.append(words)
     return out
 
@@ -317,7 +343,7 @@ def read_lines(det_net, rec_net, frames, polygon_scores, adjust_values, line_par
     """Reads every detected word of a batch and groups the words of every image into text lines in reading order (ocr_group_lines).
 
     Arguments as read_words_rectified (rectified=True, the default) or read_words (rectified=False); strip_params, params, cc, mask and
-    curved go to that call unchanged, and so do lexicon, lexicon_params and max_penalty (the lines then join the matched texts).  line_params: capi.LineParams, a dict of its fields (line_tol, height_ratio, min_cos, max_gap) or
+    curved go to that call unchanged, and so do lexicon, lexicon_params, max_penalty, lm and lm_params (the lines then join the matched or decoded texts).  line_params: capi.LineParams, a dict of its fields (line_tol, height_ratio, min_cos, max_gap) or
     None for the defaults.  The quads always come from ocr_plan_word_strips (with strip_params where given): word order equals polygon
     order in every reading call, and the curved plan carries no quads.
     Returns per image a list of lines (text, word_indices, gaps): word_indices are the image's polygon indices in reading order (int32),
