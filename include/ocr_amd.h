@@ -406,7 +406,8 @@ void ocr_glyphs_free(ocr_glyphs_t* g);
  * 12. min_col_ink is checked and unused, except by the fallback of step 5.
  * The result is an ordinary glyph block, released with ocr_glyphs_free and taken by ocr_extract_glyph_crops unchanged, except that
  * word_info[4k+3] is a bit set for this call: 1 = truncated, 2 = fell back to the column rule.
- * Still out of scope: letters that actually touch (one component, one glyph); one threshold per word (a word that is one blob under
+ * Still out of scope here: letters that actually touch (one component, one glyph - ocr_split_glyphs and ocr_lattice_decode, below,
+ * cut such a glyph at ink minima and let the decode choose); one threshold per word (a word that is one blob under
  * its Otsu threshold stays one glyph).  ocr_extract_glyph_crops cuts a crop from its box alone, so a kerned neighbour's ink inside a
  * glyph's box shows in its crop: ocr_segment_glyphs_cc_labelled and ocr_extract_glyph_crops_masked, below, keep it out.
  * Oracle: tests/glyph_cc_oracle.py; kernel: csrc/glyph_cc.hip.
@@ -937,6 +938,111 @@ void ocr_lm_default_params(ocr_lm_params_t* p);
 int  ocr_lm_decode(ocr_rec_t* rec, const ocr_char_lm_t* lm, const float* costs, int n_glyphs, int mem_kind,
                    const int32_t* word_offsets, int n_words, const ocr_lm_params_t* params, ocr_lm_paths_t** out);
 void ocr_lm_paths_free(ocr_lm_paths_t* p);
+
+/* EXTENSION - segmentation lattice (BUILD-DEFINED, like the rules above; the reference has no counterpart): wide glyphs are cut into
+ * pieces, every run of 1..M consecutive pieces (a span) is recognised, and glyph cost plus model cost choose the segmentation and the
+ * classes together.  Three calls: ocr_split_glyphs (detector), ocr_glyph_spans (host), ocr_lattice_decode (recogniser); the chain is
+ * segment -> split -> spans -> ocr_extract_glyph_crops of the span block -> ocr_rec_glyph_costs -> decode.
+ *
+ * 1. ocr_split_glyphs.  `glyphs` is any glyph block (column or component rule) of the same frames; *pieces is an ordinary glyph block
+ * (ocr_glyphs_free, every crop call takes it), *map holds per piece the index of its source glyph in `glyphs` and its rank in it
+ * (ocr_piece_map_free).  All integer.  For word k, hw = the largest y1 - y0 of its glyphs; ink is step 2 of ocr_segment_glyphs (the
+ * same q) against the word's t and polarity used from word_info: polarity 1 means q <= t, 2 means q > t (a word with t = -1 has no
+ * glyphs).  For glyph g with box [x0, x1) x [y0, y1), gw = x1 - x0:
+ *   n = (200*gw + hw*aspect_pct) / (2*hw*aspect_pct)   (integer division: the rounded ratio gw*100 / (hw*aspect_pct)),
+ *   n = max(1, min(n, max_pieces, gw / min_piece_w)).
+ * n = 1: the glyph passes through as one piece, its box unchanged.  Otherwise cnt[x] = ink pixels of column x over [y0, y1),
+ * r = max(1, gw / (4*n)), and for j = 1..n-1 with c_j = x0 + (j*gw)/n cut j is the column x in [max(c_j - r, x0 + 1),
+ * min(c_j + r, x1 - 1)] that minimises (cnt[x], |x - c_j|, x).  Since min_piece_w >= 3 gives gw >= 3n, the windows of neighbouring
+ * cuts are disjoint (c_(j+1) - c_j >= gw/n in integer division, which is >= 3 and > 2r), so the cuts increase strictly and every piece is at least one column wide.
+ * Piece i covers the columns [cut_i, cut_(i+1)) with cut_0 = x0 and cut_n = x1; its x range is kept as cut, its y range is first ink
+ * row .. last ink row + 1 inside those columns; a piece without an ink pixel is dropped.  If a word would hold more than max_word_pieces
+ * pieces (counted after the drops), all its glyphs pass through unsplit and word_info[4k+3] gains bit 4.  Every other field of the block is copied.
+ * Blocking, on the detector's stream behind what is queued there; frames in mem_kind memory, everything else host memory.
+ * OCR_ERR_INVALID for a null pointer (params == NULL -> defaults), a bad mem_kind, glyphs->n_images != n, a glyph box outside its
+ * frame, a word's frame index out of range, a polarity outside 1..2 or a t outside 0..254 in a word that has glyphs, offsets that do
+ * not span the glyphs, a parameter out of range or a nonzero reserved field; the handle stays usable.
+ * Oracle: tests/glyph_split_oracle.py; kernel: csrc/glyph_split.hip (one wave per glyph, count pass and write pass). */
+typedef struct ocr_split_params {
+  int32_t aspect_pct;        /* 25..400, default 100: the width of one letter in percent of the word's glyph height */
+  int32_t max_pieces;        /* 1..4, default 3 (per glyph)                                                          */
+  int32_t min_piece_w;       /* 3..64, default 3                                                                     */
+  int32_t max_word_pieces;   /* 1..256, default 32                                                                   */
+  int32_t reserved[4];       /* must be 0                                                                            */
+} ocr_split_params_t;
+typedef struct ocr_piece_map {
+  int32_t n_pieces;
+  const int32_t* glyph;      /* [n_pieces] index of the source glyph in the input block */
+  const int32_t* rank;       /* [n_pieces] 0.. within that glyph, left to right (dropped pieces are not counted) */
+} ocr_piece_map_t;
+void ocr_split_default_params(ocr_split_params_t* p);
+int  ocr_split_glyphs(ocr_det_t* det, const float* frames, int n, int h, int w, int mem_kind, const ocr_glyphs_t* glyphs,
+                      const ocr_split_params_t* params, ocr_glyphs_t** pieces, ocr_piece_map_t** map);
+void ocr_piece_map_free(ocr_piece_map_t* m);
+
+/* 2. ocr_glyph_spans (host only, no device call).  For a word of G pieces the spans are [e-m, e) for e = 1..G and m = 1..min(M, e),
+ * ordered by (e, m) ascending: sum_e min(M, e) per word.  A span's box is the union of its pieces' boxes.  *spans is an ordinary glyph
+ * block whose word_offsets are the span ranges (word_info, word_levels and img_offsets copied), so ocr_extract_glyph_crops cuts the
+ * span crops unchanged; M = 1 returns the piece block array for array.  *table (ocr_span_table_free) holds per span its word, end e
+ * and length m, and the piece offsets.  OCR_ERR_INVALID: null pointer, max_span outside 1..OCR_LATTICE_MAX_SPAN, a broken block. */
+#define OCR_LATTICE_MAX_SPAN 4
+#define OCR_LATTICE_MAX_PIECES 32   /* pieces per decoded word */
+typedef struct ocr_span_table {
+  int32_t n_words, n_spans, n_pieces, max_span;
+  const int32_t* span_word;      /* [n_spans] */
+  const int32_t* span_end;       /* [n_spans] e, 1..G */
+  const int32_t* span_len;       /* [n_spans] m, 1..min(M, e) */
+  const int32_t* piece_offsets;  /* [n_words+1] the piece block's word_offsets */
+} ocr_span_table_t;
+int  ocr_glyph_spans(const ocr_glyphs_t* pieces, int max_span, ocr_glyphs_t** spans, ocr_span_table_t** table);
+void ocr_span_table_free(ocr_span_table_t* t);
+
+/* 3. ocr_lattice_decode.  costs: n_spans x 62 f32 in mem_kind memory (ocr_rec_glyph_costs of the span crops); span_offsets and
+ * piece_offsets [n_words+1] in host memory; the model is ocr_char_lm_create's.
+ * Rule.  f64 on the f32 values widened, every operation rounded on its own, adds and mins only.  Word w has G pieces,
+ * 1 <= G <= OCR_LATTICE_MAX_PIECES, M = max_span, K = top_k, and row(e, m) is its span row in the order above.
+ *   A_0[c] is the one-element list {T[62][c]} with link (p = 62, r = 0).
+ *   A_j[c], j >= 1: the first K of L_j[p][r] + T[p][c] over p < 62 and r, by (value, p, r).
+ *   L_e[c]: the first K by (value, m, a) of (A_(e-m)[c][a] + span_cost[m-1]) + cost[row(e, m)][c] over m = 1..min(M, e) and ranks a.
+ *   Outputs: the first K of L_G[c][r] + T[c][62] by (value, c, r); segments and classes are read back along the links.
+ * The keys are total orders, and a rounded add is monotone, so the K costs are the K smallest path costs over all (segmentation,
+ * classes) pairs, each summed in the association above.  Hypotheses are distinct PAIRS: the same string may appear twice through two
+ * segmentations.  span_cost[m-1] is added once per segment of m pieces: the caller's knob against the bias toward few segments.
+ * With max_span = 1 and span_cost 0 the result is ocr_lm_decode's bit for bit (x + 0.0 = x for x >= 0; a sum that is -0.0 there is
+ * +0.0 here).
+ * Outputs: costs[w*top_k + k]; n_chars[w*top_k + k] the segments of hypothesis k (0 where not decoded); labels[k*n_pieces + piece] the
+ * class at the first piece of a segment, -1 elsewhere; seg_len[k*n_pieces + piece] m at the first piece of a segment, 0 elsewhere;
+ * raw_costs[w] the all-singletons path with the first-minimum class of every piece's own span row, in the same association,
+ * span_cost[0] included, so costs[w*top_k] <= raw_costs[w]; word_flags[w]: 1 for G = 0 (costs +inf, raw cost 0.0), 2 for
+ * G > OCR_LATTICE_MAX_PIECES (not decoded: costs +inf, labels -1; its raw cost is summed like any other word's).
+ * OCR_ERR_INVALID: the cases of ocr_lm_decode (null pointer - params == NULL -> defaults, costs may be NULL when n_spans = 0 -, a bad
+ * mem_kind, offsets that do not start at 0 or decrease, a model of another device, a cost that is NaN, +-inf or negative - found on
+ * the device in the same pass, the message names the first such word), span offsets that are not exactly the count the rule gives
+ * for (G, M) or do not end at n_spans, max_span or top_k out of range, a span_cost that is not finite and >= 0, a nonzero reserved
+ * field.  The handle stays usable.  n_words = 0 launches nothing.  Runs on the recogniser's stream behind what is queued there, and
+ * blocks.  Oracle: tests/lattice_oracle.py; kernel: csrc/lattice.hip (one wave per word, class c in lane c, the model in LDS, the
+ * ring of the last M lists A in registers, back-pointers (m, p, r) as uint16 in a per-call device buffer). */
+typedef struct ocr_lattice_params {
+  int32_t max_span;      /* 1..OCR_LATTICE_MAX_SPAN, default 2 */
+  int32_t top_k;         /* 1..8, default 1 */
+  double  span_cost[4];  /* finite, >= 0, default 0 */
+  int32_t reserved[2];   /* must be 0 */
+} ocr_lattice_params_t;
+typedef struct ocr_lattice_paths {
+  int32_t n_words, top_k, n_pieces;
+  const int32_t* labels;       /* [top_k*n_pieces] */
+  const int32_t* seg_len;      /* [top_k*n_pieces] */
+  const int32_t* n_chars;      /* [n_words*top_k]  */
+  const double*  costs;        /* [n_words*top_k] ascending per word, +inf where the word was not decoded */
+  const double*  raw_costs;    /* [n_words] */
+  const int32_t* word_flags;   /* [n_words] 1 no pieces, 2 more than 32 pieces */
+} ocr_lattice_paths_t;
+void ocr_lattice_default_params(ocr_lattice_params_t* p);
+/* *out: ocr_lattice_paths_free. */
+int  ocr_lattice_decode(ocr_rec_t* rec, const ocr_char_lm_t* lm, const float* costs, int n_spans, int mem_kind,
+                        const int32_t* span_offsets, const int32_t* piece_offsets, int n_words,
+                        const ocr_lattice_params_t* params, ocr_lattice_paths_t** out);
+void ocr_lattice_paths_free(ocr_lattice_paths_t* p);
 
 /* ---------------------------------------------------------------------------
  * Multi-GPU exchange.  Frames and crops are independent (eval-mode batch norm), so a batch shards over the GPUs of

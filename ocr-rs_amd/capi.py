@@ -42,6 +42,8 @@ EXPORTS = [
     "ocr_rec_glyph_costs", "ocr_lexicon_create", "ocr_lexicon_size", "ocr_lexicon_destroy", "ocr_lexicon_default_params", "ocr_lexicon_match",
     "ocr_lexicon_matches_free",
     "ocr_char_lm_create", "ocr_char_lm_destroy", "ocr_lm_default_params", "ocr_lm_decode", "ocr_lm_paths_free",
+    "ocr_split_default_params", "ocr_split_glyphs", "ocr_piece_map_free", "ocr_glyph_spans", "ocr_span_table_free",
+    "ocr_lattice_default_params", "ocr_lattice_decode", "ocr_lattice_paths_free",
     "ocr_ctc_beam_decode",
     "ocr_comm_unique_id", "ocr_comm_rccl_version", "ocr_comm_create", "ocr_comm_destroy",
     "ocr_comm_all_gather_polygons", "ocr_comm_all_gather_labels",
@@ -178,12 +180,45 @@ class LmPathsBlock(C.Structure):
                 ("costs", C.POINTER(C.c_double)), ("raw_costs", C.POINTER(C.c_double)), ("word_flags", C.POINTER(C.c_int32))]
 
 
+class SplitParams(C.Structure):
+    """ocr_split_params_t."""
+    _fields_ = [("aspect_pct", C.c_int32), ("max_pieces", C.c_int32), ("min_piece_w", C.c_int32), ("max_word_pieces", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class PieceMapBlock(C.Structure):
+    """ocr_piece_map_t."""
+    _fields_ = [("n_pieces", C.c_int32), ("glyph", C.POINTER(C.c_int32)), ("rank", C.POINTER(C.c_int32))]
+
+
+class SpanTableBlock(C.Structure):
+    """ocr_span_table_t."""
+    _fields_ = [("n_words", C.c_int32), ("n_spans", C.c_int32), ("n_pieces", C.c_int32), ("max_span", C.c_int32),
+                ("span_word", C.POINTER(C.c_int32)), ("span_end", C.POINTER(C.c_int32)), ("span_len", C.POINTER(C.c_int32)),
+                ("piece_offsets", C.POINTER(C.c_int32))]
+
+
+class LatticeParams(C.Structure):
+    """ocr_lattice_params_t."""
+    _fields_ = [("max_span", C.c_int32), ("top_k", C.c_int32), ("span_cost", C.c_double * 4), ("reserved", C.c_int32 * 2)]
+
+
+class LatticePathsBlock(C.Structure):
+    """ocr_lattice_paths_t."""
+    _fields_ = [("n_words", C.c_int32), ("top_k", C.c_int32), ("n_pieces", C.c_int32), ("labels", C.POINTER(C.c_int32)),
+                ("seg_len", C.POINTER(C.c_int32)), ("n_chars", C.POINTER(C.c_int32)), ("costs", C.POINTER(C.c_double)),
+                ("raw_costs", C.POINTER(C.c_double)), ("word_flags", C.POINTER(C.c_int32))]
+
+
 LEX_MAX_LEN = 32
 LEX_MAX_ENTRIES = 1 << 22
 LEX_CHUNK = 256   # entries per pass of a match workgroup (csrc/lexicon_host.hpp kLexChunk): lexicon sizes around it change the grid
 
 LM_MAX_LEN = 32
 LM_WORDS = 4      # words per workgroup of the decode kernel (csrc/char_lm_host.hpp kLmWords): word counts around it change the grid
+LATTICE_MAX_SPAN = 4
+LATTICE_MAX_PIECES = 32
+LATTICE_WORDS = 4  # words per workgroup of the lattice decode kernel (csrc/lattice_host.hpp kLatWords)
 LM_BEGIN = 62     # the model's row of begin-of-word
 LM_END = 62       # ... and its column of end-of-word
 
@@ -351,6 +386,21 @@ def lib() -> C.CDLL:
                                     C.POINTER(C.POINTER(LmPathsBlock))]
         L.ocr_lm_paths_free.argtypes = [C.POINTER(LmPathsBlock)]
         L.ocr_lm_paths_free.restype = None
+        L.ocr_split_default_params.argtypes = [C.POINTER(SplitParams)]
+        L.ocr_split_default_params.restype = None
+        L.ocr_split_glyphs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Glyphs), C.POINTER(SplitParams),
+                                       C.POINTER(C.POINTER(Glyphs)), C.POINTER(C.POINTER(PieceMapBlock))]
+        L.ocr_piece_map_free.argtypes = [C.POINTER(PieceMapBlock)]
+        L.ocr_piece_map_free.restype = None
+        L.ocr_glyph_spans.argtypes = [C.POINTER(Glyphs), C.c_int, C.POINTER(C.POINTER(Glyphs)), C.POINTER(C.POINTER(SpanTableBlock))]
+        L.ocr_span_table_free.argtypes = [C.POINTER(SpanTableBlock)]
+        L.ocr_span_table_free.restype = None
+        L.ocr_lattice_default_params.argtypes = [C.POINTER(LatticeParams)]
+        L.ocr_lattice_default_params.restype = None
+        L.ocr_lattice_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.POINTER(LatticeParams), C.POINTER(C.POINTER(LatticePathsBlock))]
+        L.ocr_lattice_paths_free.argtypes = [C.POINTER(LatticePathsBlock)]
+        L.ocr_lattice_paths_free.restype = None
         L.ocr_rec_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_rec_destroy.argtypes = [C.c_void_p]
         L.ocr_rec_destroy.restype = None
@@ -1197,6 +1247,130 @@ class LmPaths:
                        arr(s.raw_costs, nw, np.float64), arr(s.word_flags, nw, np.int32))
 
 
+def split_params(**fields) -> SplitParams:
+    """ocr_split_default_params with the given fields overridden (aspect_pct, max_pieces, min_piece_w, max_word_pieces, reserved)."""
+    p = SplitParams()
+    lib().ocr_split_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k in ("aspect_pct", "max_pieces", "min_piece_w", "max_word_pieces"):
+            setattr(p, k, int(v))
+        else:
+            raise TypeError(f"unknown split parameter {k!r}")
+    return p
+
+
+def _as_split_params(params) -> Optional[SplitParams]:
+    if params is None or isinstance(params, SplitParams):
+        return params
+    return split_params(**params)
+
+
+def lattice_params(**fields) -> LatticeParams:
+    """ocr_lattice_default_params with the given fields overridden (max_span, top_k, span_cost: up to 4 values, reserved)."""
+    p = LatticeParams()
+    lib().ocr_lattice_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k in ("reserved", "span_cost"):
+            for i, x in enumerate(v):
+                getattr(p, k)[i] = int(x) if k == "reserved" else float(x)
+        elif k in ("max_span", "top_k"):
+            setattr(p, k, int(v))
+        else:
+            raise TypeError(f"unknown lattice parameter {k!r}")
+    return p
+
+
+def _as_lattice_params(params) -> Optional[LatticeParams]:
+    if params is None or isinstance(params, LatticeParams):
+        return params
+    return lattice_params(**params)
+
+
+class SpanTable:
+    """The arrays of an ocr_span_table_t, copied into numpy: span_word, span_end (e), span_len (m) per span, piece_offsets
+    [n_words+1]; span_offsets [n_words+1] is the span block's word_offsets, kept beside them for the decode call."""
+
+    def __init__(self, span_word, span_end, span_len, piece_offsets, span_offsets, max_span: int):
+        self.span_word = np.ascontiguousarray(span_word, dtype=np.int32)
+        self.span_end = np.ascontiguousarray(span_end, dtype=np.int32)
+        self.span_len = np.ascontiguousarray(span_len, dtype=np.int32)
+        self.piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.int32)
+        self.span_offsets = np.ascontiguousarray(span_offsets, dtype=np.int32)
+        self.max_span = int(max_span)
+
+    @property
+    def n_spans(self) -> int:
+        return len(self.span_word)
+
+
+def glyph_spans(pieces: "GlyphSet", max_span: int):
+    """ocr_glyph_spans (host only): -> (the span block as a GlyphSet, whose word_offsets are the span ranges, and the SpanTable)."""
+    blk = pieces.block()
+    out, tab = C.POINTER(Glyphs)(), C.POINTER(SpanTableBlock)()
+    check(lib().ocr_glyph_spans(C.byref(blk), int(max_span), C.byref(out), C.byref(tab)))
+    try:
+        spans = GlyphSet.from_block(out)
+        t = tab.contents
+
+        def arr(ptr, n):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, np.int32)
+        return spans, SpanTable(arr(t.span_word, t.n_spans), arr(t.span_end, t.n_spans), arr(t.span_len, t.n_spans),
+                                arr(t.piece_offsets, t.n_words + 1), spans.word_offsets, t.max_span)
+    finally:
+        lib().ocr_glyphs_free(out)
+        lib().ocr_span_table_free(tab)
+
+
+class LatticePaths:
+    """The arrays of an ocr_lattice_paths_t, copied into numpy: labels and seg_len top_k x n_pieces int32 (class and length at the first
+    piece of every segment, -1 / 0 elsewhere), n_chars n_words x top_k, costs n_words x top_k f64 (+inf where the word was not decoded),
+    raw_costs [n_words] f64 (the all-singletons reading), word_flags [n_words] (1 no pieces, 2 more than 32 pieces)."""
+
+    def __init__(self, labels, seg_len, n_chars, costs, raw_costs, word_flags):
+        self.labels = np.ascontiguousarray(labels, dtype=np.int32)
+        self.seg_len = np.ascontiguousarray(seg_len, dtype=np.int32)
+        self.n_chars = np.ascontiguousarray(n_chars, dtype=np.int32)
+        self.costs = np.ascontiguousarray(costs, dtype=np.float64)
+        self.raw_costs = np.ascontiguousarray(raw_costs, dtype=np.float64)
+        self.word_flags = np.ascontiguousarray(word_flags, dtype=np.int32)
+
+    @property
+    def n_words(self) -> int:
+        return self.costs.shape[0]
+
+    @property
+    def top_k(self) -> int:
+        return self.costs.shape[1]
+
+    def text(self, piece_offsets, w: int, k: int = 0) -> str:
+        """hypothesis k of word w as a string: the classes at the segment starts ("" for a word that was not decoded)"""
+        lab = self.labels[k, int(piece_offsets[w]):int(piece_offsets[w + 1])]
+        return "".join(_ALPHABET[int(c)] for c in lab if c >= 0)
+
+    def texts(self, piece_offsets, k: int = 0) -> list:
+        """hypothesis k of every word as a string ("" for a word that was not decoded)"""
+        return [self.text(piece_offsets, w, k) for w in range(len(piece_offsets) - 1)]
+
+    def segments(self, piece_offsets, w: int, k: int = 0) -> list:
+        """hypothesis k of word w as [(first piece, length, class)] with piece indices into the block"""
+        p0, p1 = int(piece_offsets[w]), int(piece_offsets[w + 1])
+        return [(p, int(self.seg_len[k, p]), int(self.labels[k, p])) for p in range(p0, p1) if self.seg_len[k, p] > 0]
+
+    @staticmethod
+    def from_block(mp) -> "LatticePaths":
+        s = mp.contents
+        nw, k, n = s.n_words, s.top_k, s.n_pieces
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return LatticePaths(arr(s.labels, k * n, np.int32).reshape(k, n), arr(s.seg_len, k * n, np.int32).reshape(k, n),
+                            arr(s.n_chars, nw * k, np.int32).reshape(nw, k), arr(s.costs, nw * k, np.float64).reshape(nw, k),
+                            arr(s.raw_costs, nw, np.float64), arr(s.word_flags, nw, np.int32))
+
+
 class CharLm:
     """Owner of an ocr_char_lm_t: a 64 x 64 bigram cost table (char_lm_table), uploaded once to the recogniser's GPU and resident there
     until close() (or the end of a `with` block)."""
@@ -1433,6 +1607,33 @@ class Detector:
     def segment_glyphs_device(self, frames_ptr: int, n: int, h: int, w: int, polys, adjust_values, params=None, cc=None) -> GlyphSet:
         """The same on device-resident frames (a device pointer to N x 1 x H x W f32)."""
         return self._segment(C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, polys, adjust_values, params, cc)
+
+    def _split(self, frames_ptr, n: int, h: int, w: int, mem_kind: int, glyphs: GlyphSet, params):
+        blk = glyphs.block()
+        prm = _as_split_params(params)
+        out, pm = C.POINTER(Glyphs)(), C.POINTER(PieceMapBlock)()
+        check(lib().ocr_split_glyphs(self._h, frames_ptr, n, h, w, mem_kind, C.byref(blk), C.byref(prm) if prm is not None else None,
+                                     C.byref(out), C.byref(pm)))
+        try:
+            m = pm.contents
+
+            def arr(ptr):
+                return np.ctypeslib.as_array(ptr, shape=(m.n_pieces,)).copy() if m.n_pieces else np.zeros(0, np.int32)
+            return GlyphSet.from_block(out), np.stack([arr(m.glyph), arr(m.rank)], axis=1)
+        finally:
+            lib().ocr_glyphs_free(out)
+            lib().ocr_piece_map_free(pm)
+
+    def split_glyphs(self, frames: np.ndarray, glyphs: GlyphSet, params=None):
+        """ocr_split_glyphs on host frames N x 1 x H x W f32: wide glyphs of `glyphs` cut at ink minima.  params: SplitParams, a dict of
+        its fields, or None (defaults).  -> (the pieces as a GlyphSet, the piece map n_pieces x 2: source glyph, rank in it)."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        n, _, h, w = frames.shape
+        return self._split(_ptr(frames), n, h, w, MEM_HOST, glyphs, params)
+
+    def split_glyphs_device(self, frames_ptr: int, n: int, h: int, w: int, glyphs: GlyphSet, params=None):
+        """The same on device-resident frames (a device pointer to N x 1 x H x W f32)."""
+        return self._split(C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, glyphs, params)
 
     def _segment_labelled(self, frames_ptr, n: int, h: int, w: int, mem_kind: int, polys, adjust_values, params, cc):
         st, keep = python_to_polygons(polys, [[0.0] * len(p) for p in polys]) if not isinstance(polys, Polygons) else (polys, None)
@@ -2137,6 +2338,30 @@ class Recognizer:
 
     def lm_decode_device(self, lm: "CharLm", costs_ptr: int, n_glyphs: int, word_offsets, params=None) -> LmPaths:
         return self._lm_decode(lm, C.c_void_p(costs_ptr or None), n_glyphs, MEM_DEVICE, word_offsets, params)
+
+    def _lattice_decode(self, lm, costs_ptr, n_spans: int, mem_kind: int, span_offsets, piece_offsets, params) -> LatticePaths:
+        so = np.ascontiguousarray(span_offsets, dtype=np.int32).reshape(-1)
+        po = np.ascontiguousarray(piece_offsets, dtype=np.int32).reshape(-1)
+        if len(so) != len(po):
+            raise ValueError(f"{len(so)} span offsets, {len(po)} piece offsets")
+        prm = _as_lattice_params(params)
+        out = C.POINTER(LatticePathsBlock)()
+        check(lib().ocr_lattice_decode(self._h, lm.handle if isinstance(lm, CharLm) else lm, costs_ptr, n_spans, mem_kind,
+                                       _ptr(so) if so.size else None, _ptr(po) if po.size else None, len(so) - 1,
+                                       C.byref(prm) if prm is not None else None, C.byref(out)))
+        try:
+            return LatticePaths.from_block(out)
+        finally:
+            lib().ocr_lattice_paths_free(out)
+
+    def lattice_decode(self, lm: "CharLm", costs: np.ndarray, span_offsets, piece_offsets, params=None) -> LatticePaths:
+        """ocr_lattice_decode: costs n_spans x 62 f32 in host memory (glyph_costs of the span crops), span_offsets and piece_offsets
+        [n_words+1] (SpanTable); params: LatticeParams, a dict of its fields, or None (defaults).  Blocking, on the handle's stream."""
+        x = np.ascontiguousarray(costs, dtype=np.float32).reshape(-1, 62)
+        return self._lattice_decode(lm, _ptr(x) if x.size else None, x.shape[0], MEM_HOST, span_offsets, piece_offsets, params)
+
+    def lattice_decode_device(self, lm: "CharLm", costs_ptr: int, n_spans: int, span_offsets, piece_offsets, params=None) -> LatticePaths:
+        return self._lattice_decode(lm, C.c_void_p(costs_ptr or None), n_spans, MEM_DEVICE, span_offsets, piece_offsets, params)
 
 
 def python_to_polygons(polys, scores):

@@ -426,21 +426,7 @@ int ocr_extract_crops(ocr_det_t* det, const float* frames, int n, int h, int w, 
 }
 
 // ---- glyph segmentation (glyphs.hip; rule in include/ocr_amd.h, oracle tests/glyph_oracle.py)
-struct GlyphsOwned {   // the library-owned storage behind an ocr_glyphs_t* (released by ocr_glyphs_free)
-  ocr_glyphs_t view;
-  std::vector<int32_t> img_offsets, word_offsets, word_info, boxes;
-  std::vector<float> word_levels;
-  void finish() {
-    view.n_images = (int32_t)img_offsets.size() - 1;
-    view.n_words = (int32_t)word_offsets.size() - 1;
-    view.n_glyphs = (int32_t)(boxes.size() / 4);
-    view.img_offsets = img_offsets.data();
-    view.word_offsets = word_offsets.data();
-    view.word_info = word_info.data();
-    view.word_levels = word_levels.data();
-    view.boxes = boxes.data();
-  }
-};
+using ocr::GlyphsOwned;   // api_internal.hpp: glyph_split.hip and lattice.hip return glyph blocks too
 
 static ocr_segment_params_t segment_params(const ocr_segment_params_t* params, const char* who) {
   ocr_segment_params_t p;

@@ -24,6 +24,18 @@ struct ocr_rec {
   }
 };
 
+struct ocr_char_lm {   // the character model of char_lm.hip, also read by lattice.hip
+  int device = 0;
+  float* dev = nullptr;   // the 64 x 64 model
+  ~ocr_char_lm() {
+    if (dev) {
+      (void)hipSetDevice(device);
+      (void)hipDeviceSynchronize();   // whatever was queued with the model has finished before its memory goes
+      (void)hipFree(dev);
+    }
+  }
+};
+
 namespace ocr {
 
 extern thread_local std::string g_last_error;  // what ocr_last_error() returns (api.hip)
@@ -99,6 +111,23 @@ struct PolygonsOwned {
     view.poly_offsets = poly_offsets.data();
     view.xy = xy.data();
     view.scores = scores.data();
+  }
+};
+
+// the library-owned storage behind an ocr_glyphs_t* (released by ocr_glyphs_free)
+struct GlyphsOwned {
+  ocr_glyphs_t view;
+  std::vector<int32_t> img_offsets, word_offsets, word_info, boxes;
+  std::vector<float> word_levels;
+  void finish() {
+    view.n_images = (int32_t)img_offsets.size() - 1;
+    view.n_words = (int32_t)word_offsets.size() - 1;
+    view.n_glyphs = (int32_t)(boxes.size() / 4);
+    view.img_offsets = img_offsets.data();
+    view.word_offsets = word_offsets.data();
+    view.word_info = word_info.data();
+    view.word_levels = word_levels.data();
+    view.boxes = boxes.data();
   }
 };
 

@@ -196,18 +196,7 @@ __global__ __launch_bounds__(kLmWords * 64) void lm_decode_kernel(const float* _
 }  // namespace ocr
 
 // ---- the C surface (include/ocr_amd.h)
-struct ocr_char_lm {
-  int device = 0;
-  float* dev = nullptr;   // the 64 x 64 model
-  ~ocr_char_lm() {
-    if (dev) {
-      (void)hipSetDevice(device);
-      (void)hipDeviceSynchronize();   // whatever was queued with the model has finished before its memory goes
-      (void)hipFree(dev);
-    }
-  }
-};
-
+// (struct ocr_char_lm: api_internal.hpp - lattice.hip decodes under the same model)
 namespace {
 struct PathsOwned {   // the library-owned storage behind an ocr_lm_paths_t* (released by ocr_lm_paths_free)
   ocr_lm_paths_t view{};

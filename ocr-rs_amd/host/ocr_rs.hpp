@@ -10,6 +10,8 @@
 //   read_words: detected words -> glyphs -> text, the pipeline's segmentation step (README.md:20-26), which the reference never built
 //   Lexicon / glyph_costs / lexicon_match / read_words(.., lexicon): words read as a whole against a word list (ocr_lexicon_match)
 //   CharLm / lm_decode: words decoded under a character-bigram model from the same glyph costs, k best readings (ocr_lm_decode)
+//   split_glyphs / glyph_spans / lattice_decode: wide glyphs cut into pieces, runs of pieces recognised, segmentation and classes
+//     chosen together under the model (ocr_split_glyphs, ocr_glyph_spans, ocr_lattice_decode)
 //   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words,
 //     or through curved strips (ocr_plan_curved_strips / ocr_extract_curved_strips), for words that bend
 //   group_lines / read_lines: the words of every page grouped into text lines in reading order (ocr_group_lines), the "output text" step
@@ -406,6 +408,94 @@ inline LmPaths lm_decode(const char_recognition::Net& rec_net, const CharLm& lm,
   out.raw_costs.assign(m->raw_costs, m->raw_costs + nw);
   out.word_flags.assign(m->word_flags, m->word_flags + nw);
   ocr_lm_paths_free(m);
+  return out;
+}
+
+// ---- segmentation lattice (ocr_split_glyphs, ocr_glyph_spans, ocr_lattice_decode; the rules are stated in ocr_amd.h)
+// A glyph block owned by the library (ocr_glyphs_free): what split_glyphs and glyph_spans return and every crop call takes.
+struct GlyphBlock {
+  ocr_glyphs_t* g = nullptr;
+  GlyphBlock() = default;
+  explicit GlyphBlock(ocr_glyphs_t* p) : g(p) {}
+  GlyphBlock(GlyphBlock&& o) noexcept : g(o.g) { o.g = nullptr; }
+  GlyphBlock& operator=(GlyphBlock&& o) noexcept {
+    std::swap(g, o.g);
+    return *this;
+  }
+  GlyphBlock(const GlyphBlock&) = delete;
+  GlyphBlock& operator=(const GlyphBlock&) = delete;
+  ~GlyphBlock() { ocr_glyphs_free(g); }
+  const ocr_glyphs_t* get() const { return g; }
+};
+// wide glyphs of `glyphs` cut at ink minima; piece_map (optional) receives per piece (source glyph, rank in it)
+inline GlyphBlock split_glyphs(const text_detection::FuncT& det_net, const Tensor& frames, const ocr_glyphs_t* glyphs,
+                               const ocr_split_params_t* params = nullptr, std::vector<std::array<int32_t, 2>>* piece_map = nullptr) {
+  if (frames.c != 1) throw Error(OCR_ERR_INVALID, "expected N x 1 x H x W");
+  ocr_glyphs_t* pieces = nullptr;
+  ocr_piece_map_t* pm = nullptr;
+  check(ocr_split_glyphs(det_net.handle(), frames.data.data(), frames.n, frames.h, frames.w, OCR_MEM_HOST, glyphs, params, &pieces, &pm));
+  if (piece_map) {
+    piece_map->clear();
+    for (int32_t i = 0; i < pm->n_pieces; ++i) piece_map->push_back({pm->glyph[i], pm->rank[i]});
+  }
+  ocr_piece_map_free(pm);
+  return GlyphBlock(pieces);
+}
+// every run of 1..max_span consecutive pieces of a word, ordered by (end, length): spans.get()->word_offsets are the span offsets of
+// lattice_decode, piece_offsets the piece block's word_offsets
+struct GlyphSpans {
+  GlyphBlock spans;
+  std::vector<int32_t> span_word, span_end, span_len, span_offsets, piece_offsets;
+};
+inline GlyphSpans glyph_spans(const ocr_glyphs_t* pieces, int max_span) {
+  ocr_glyphs_t* s = nullptr;
+  ocr_span_table_t* t = nullptr;
+  check(ocr_glyph_spans(pieces, max_span, &s, &t));
+  GlyphSpans out;
+  out.spans = GlyphBlock(s);
+  out.span_word.assign(t->span_word, t->span_word + t->n_spans);
+  out.span_end.assign(t->span_end, t->span_end + t->n_spans);
+  out.span_len.assign(t->span_len, t->span_len + t->n_spans);
+  out.piece_offsets.assign(t->piece_offsets, t->piece_offsets + t->n_words + 1);
+  out.span_offsets.assign(s->word_offsets, s->word_offsets + s->n_words + 1);
+  ocr_span_table_free(t);
+  return out;
+}
+// labels and seg_len are top_k x n_pieces: class and length at the first piece of every segment, -1 / 0 elsewhere; n_chars and costs
+// n_words x top_k; the other two are per word.  Hypotheses are distinct (segmentation, classes) pairs: a string may come twice.
+struct LatticePaths {
+  int top_k = 1, n_pieces = 0;
+  std::vector<int32_t> labels, seg_len, n_chars, word_flags;
+  std::vector<double> costs, raw_costs;
+  // hypothesis k of the word with pieces [p0, p1): "" when it was not decoded
+  std::string text(int32_t p0, int32_t p1, int k = 0) const {
+    std::string t;
+    for (int32_t j = p0; j < p1; ++j) {
+      const int32_t c = labels[(size_t)k * n_pieces + j];
+      if (c >= 0) t.push_back(utils::VALUES()[c]);
+    }
+    return t;
+  }
+};
+inline LatticePaths lattice_decode(const char_recognition::Net& rec_net, const CharLm& lm, const std::vector<float>& costs,
+                                   const std::vector<int32_t>& span_offsets, const std::vector<int32_t>& piece_offsets,
+                                   const ocr_lattice_params_t* params = nullptr) {
+  if (span_offsets.empty() || span_offsets.size() != piece_offsets.size() || costs.size() != 62 * (size_t)span_offsets.back())
+    throw Error(OCR_ERR_INVALID, "costs do not match the span offsets, or the two offset arrays differ in length");
+  ocr_lattice_paths_t* m = nullptr;
+  check(ocr_lattice_decode(rec_net.handle(), lm.handle(), costs.empty() ? nullptr : costs.data(), (int)(costs.size() / 62), OCR_MEM_HOST,
+                           span_offsets.data(), piece_offsets.data(), (int)span_offsets.size() - 1, params, &m));
+  LatticePaths out;
+  const size_t nw = (size_t)m->n_words, k = (size_t)m->top_k, np = (size_t)m->n_pieces;
+  out.top_k = m->top_k;
+  out.n_pieces = m->n_pieces;
+  out.labels.assign(m->labels, m->labels + k * np);
+  out.seg_len.assign(m->seg_len, m->seg_len + k * np);
+  out.n_chars.assign(m->n_chars, m->n_chars + nw * k);
+  out.costs.assign(m->costs, m->costs + nw * k);
+  out.raw_costs.assign(m->raw_costs, m->raw_costs + nw);
+  out.word_flags.assign(m->word_flags, m->word_flags + nw);
+  ocr_lattice_paths_free(m);
   return out;
 }
 

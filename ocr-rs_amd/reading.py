@@ -32,6 +32,12 @@ recognition -> output text), composed over the C ABI.
     ... and lm=capi.CharLm (with lm_params): every word is decoded under a character-bigram model from the same costs, which reads
     words that no list contains:
         ocr_lm_decode             every word -> its k cheapest readings under glyph + transition cost  (csrc/char_lm.hip)
+    read_words(..., lattice={}) does not trust the segmentation: wide glyphs are cut, every run of up to max_span pieces is
+    recognised, and glyph cost plus model cost choose segmentation and classes together:
+        ocr_split_glyphs          wide glyphs -> pieces, cut at ink minima                 (csrc/glyph_split.hip)
+        ocr_glyph_spans           pieces -> every run of 1..max_span pieces, a glyph block (csrc/lattice_host.cpp, host)
+        ocr_extract_glyph_crops, ocr_rec_classify, ocr_rec_glyph_costs on the spans
+        ocr_lattice_decode        every word -> its k cheapest (segmentation, classes) pairs (csrc/lattice.hip)
 
 The segmentation, strip and line rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
 tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py, tests/strip_oracle.py, tests/curved_strip_oracle.py and
@@ -155,8 +161,56 @@ def _word(text: str, probs, where, k: int, n_glyphs: int, matches, lexicon, max_
     return (out, probs, where, *extra)
 
 
+def _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params, cc, lm, lattice, split):
+    """segment -> split -> spans -> crops -> classify + costs -> decode, everything between the calls on the device; per word
+    (text, probs, where, (cost, raw_cost, raw_text, seg_len)) with text, probs and where (the union boxes) along hypothesis 0's segments."""
+    import torch
+    if lm is not None and not isinstance(lm, capi.CharLm):
+        raise TypeError(f"lm: expected a capi.CharLm, got {type(lm).__name__}")
+    prm = capi._as_lattice_params(lattice)
+    glyphs = det.segment_glyphs_device(x.data_ptr(), n, h, w, polys, adjust_values, params, cc)
+    pieces, _ = det.split_glyphs_device(x.data_ptr(), n, h, w, glyphs, split)
+    spans, table = capi.glyph_spans(pieces, prm.max_span)
+    ns = spans.n_glyphs
+    labels, probs, costs_ptr = np.zeros(0, np.int32), np.zeros(0, np.float64), 0
+    if ns:
+        crops = torch.empty((ns, 784), dtype=torch.float32, device=dev)
+        det.extract_glyph_crops_device(x.data_ptr(), n, h, w, spans, crops.data_ptr(), params)
+        lab = torch.empty(ns, dtype=torch.int32, device=dev)
+        pr = torch.empty(ns, dtype=torch.float64, device=dev)
+        logits = torch.empty((ns, 62), dtype=torch.float32, device=dev)
+        costs = torch.empty((ns, 62), dtype=torch.float32, device=dev)
+        rec.classify_device(crops.data_ptr(), ns, logits.data_ptr(), lab.data_ptr(), pr.data_ptr())
+        rec.glyph_costs_device(logits.data_ptr(), ns, costs.data_ptr())   # blocking, behind the classify call
+        costs_ptr = costs.data_ptr()
+        labels, probs = lab.cpu().numpy(), pr.cpu().numpy()
+    so, po = table.span_offsets, table.piece_offsets
+    if lm is not None:
+        paths = rec.lattice_decode_device(lm, costs_ptr, ns, so, po, prm)
+    else:
+        with capi.CharLm(rec, np.zeros((64, 64), np.float32)) as zero:
+            paths = rec.lattice_decode_device(zero, costs_ptr, ns, so, po, prm)
+    M = prm.max_span
+    base = lambda e: e * (e + 1) // 2 if e <= M else M * (M + 1) // 2 + (e - M) * M   # the spans in front of end e + 1
+    out = []
+    for b in range(n):
+        words = []
+        for k in range(int(pieces.img_offsets[b]), int(pieces.img_offsets[b + 1])):
+            p0, G, s0 = int(po[k]), int(po[k + 1] - po[k]), int(so[k])
+            single = [s0 + base(e - 1) for e in range(1, G + 1)]
+            raw_text = "".join(VALUES[int(labels[r])] for r in single)
+            segs = [(p - p0, m) for p, m, _ in paths.segments(po, k)] if int(paths.word_flags[k]) == 0 else [(i, 1) for i in range(G)]
+            rows = [s0 + base(i + m - 1) + (m - 1) for i, m in segs]
+            text = paths.text(po, k) if int(paths.word_flags[k]) == 0 else raw_text
+            words.append((text, probs[rows].copy() if rows else np.zeros(0, np.float64), spans.boxes[rows].reshape(-1, 4).copy(),
+                          (float(paths.costs[k, 0]), float(paths.raw_costs[k]), raw_text, tuple(m for _, m in segs))))
+        out.append(words)
+    return out
+
+
 def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None, cc=None, mask=None, lexicon=None,
-               lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+               lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None, lattice=None,
+               split=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch.
 
     det_net: text_detection.FuncT or capi.Detector (supplies the GPU and stream of the segmentation); rec_net: char_recognition.Net
@@ -176,7 +230,14 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     dict of its fields or None), the text of a decoded word becomes hypothesis 0's string, and the tuple gains (lm_cost, raw_cost,
     raw_text) as its last element: the cost of hypothesis 0, the cost of the greedy reading under the model, the greedy text.  With
     both lexicon and lm a word the lexicon accepted keeps the entry's string, the others take the model's, and the lexicon's element
-    comes first.  With lm=None nothing changes."""
+    comes first.  With lm=None nothing changes.
+    lattice: None, or capi.LatticeParams, a dict of its fields or {} for the defaults: the segmentation is searched too.  The glyphs
+    are cut into pieces (ocr_split_glyphs with split: capi.SplitParams, a dict of its fields or None), every run of up to max_span
+    pieces is cropped and classified, and ocr_lattice_decode picks segments and classes together under lm (lm=None: a zero model
+    created for the call; lm_params is not used, top_k is the lattice's).  The text is hypothesis 0's, probs and where follow its
+    segments (where holds the union box of every segment), and the tuple gains (cost, raw_cost, raw_text, seg_len) as its last
+    element: raw_text is the reading of the pieces one by one, seg_len the pieces per character.  Masked crops with a lattice raise
+    OcrError (labels do not map to pieces), and so does lexicon= (a joint search is not built).  With lattice=None nothing changes."""
     import torch
 
     det = _handle(det_net, capi.Detector)
@@ -195,6 +256,12 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     n, _, h, w = x.shape
     # the library's calls run on their handles' streams: whatever torch queued to produce x is finished first
     torch.cuda.current_stream(dev).synchronize()
+    if lattice is not None:
+        if _masked(mask, cc):
+            raise capi.OcrError(1, "lattice: masked crops are not built for pieces (labels do not map to them)")
+        if lexicon is not None:
+            raise capi.OcrError(1, "lattice: a joint search with a lexicon is not built")
+        return _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params, cc, lm, lattice, split)
     glyphs, crops = _segment_and_crop(det, x.data_ptr(), n, h, w, polys, adjust_values, params, cc, mask, dev)   # blocking
     ng = glyphs.n_glyphs
     labels, probs, matches, paths = _classify(rec, crops, ng, dev, glyphs.word_offsets, lexicon, lexicon_params, lm, lm_params)
