@@ -1044,6 +1044,67 @@ int  ocr_lattice_decode(ocr_rec_t* rec, const ocr_char_lm_t* lm, const float* co
                         const ocr_lattice_params_t* params, ocr_lattice_paths_t** out);
 void ocr_lattice_paths_free(ocr_lattice_paths_t* p);
 
+/* 4. ocr_lexicon_lattice_match: the joint search.  The entries of a lexicon are matched over the PIECES of a word, a character
+ * reading a span of 1..M pieces, so that a wrong cut is re-cut instead of paid as an insertion or a deletion (BUILD-DEFINED).
+ * Inputs follow ocr_lattice_decode: costs n_spans x 62 f32 in mem_kind memory, span_offsets and piece_offsets [n_words+1] in host
+ * memory, spans in the (e, m) order of ocr_glyph_spans; the lexicon is ocr_lexicon_create's, on the recogniser's device.
+ * Rule.  f64 on the f32 values widened, every operation rounded on its own, adds and mins only.  Word w has G pieces,
+ * 1 <= G <= OCR_LATTICE_MAX_PIECES, M = max_span; an entry has classes c_0..c_(L-1).
+ *   s(row, c) = (double)cost[row][c]; with fold_case = 1 the min of that and the same for the other-case twin of c, exactly as in
+ *     ocr_lexicon_match.  row(e, m) is the span row of ocr_glyph_spans.
+ *   D[0][0] = 0;  D[i][0] = D[i-1][0] + del_cost;  D[0][j] = D[0][j-1] + ins_cost;
+ *   D[i][j] = min( min over m = 1..min(M, i) of ((D[i-m][j-1] + span_cost[m-1]) + s(row(i, m), c_(j-1))),
+ *                  min(D[i-1][j] + del_cost, D[i][j-1] + ins_cost) );                     cost(w, entry) = D[G][L].
+ * A rounded add is monotone, so the cost is the minimum, over all alignment paths, of the path's sum taken left to right.
+ * Candidates of w: the entries with max(1, ceil(G / M) - max_len_diff) <= L <= min(32, G + max_len_diff); n_candidates[w] is their
+ * number.  Output of w: the first top_k candidates by (cost ascending, entry index ascending); slots past the candidates hold -1
+ * and +inf.  word_flags[w]: 1 for G = 0, 2 for G > OCR_LATTICE_MAX_PIECES (no candidates, no other flag), else 4 when no entry has an
+ * admissible length.
+ * raw_costs[w]: the cheapest free segmentation with every span read as its cheapest class: F[0] = 0, F[e] = min over
+ * m = 1..min(M, e) of (F[e-m] + span_cost[m-1]) + min_c (double)cost[row(e, m)][c]; raw = F[G] (0.0 for G = 0; a word of more than
+ * 32 pieces is summed like any other).
+ * With max_span = 1 and span_cost 0 the whole result - entries, costs, raw costs, candidates, flags - is ocr_lexicon_match's bit for
+ * bit (x + 0.0 = x for x >= 0).
+ * Alignment of every returned (word, rank): the table is walked back from (G, L); at cell (i, j) with value v the first step whose
+ * recomputed value equals v bit for bit is taken, in the order: a segment of m = 1, 2, .., min(M, i) pieces (when j >= 1), a
+ * deletion (when i >= 1), an insertion (when j >= 1).  seg_len[k*n_pieces + piece] is m at the first piece of a segment, 0 at its
+ * other pieces, -1 at a deleted piece (0 in empty slots and in words without candidates); seg_char[k*n_pieces + piece] the entry
+ * position j at the first piece of a segment, -1 elsewhere; n_ins[w*top_k + k] the entry characters that got no segment.
+ * OCR_ERR_INVALID: a null pointer (params == NULL -> the defaults; costs may be NULL when n_spans = 0), a bad mem_kind, offsets that
+ * do not start at 0 or decrease, span offsets that are not exactly sum_e min(M, e) per word or do not end at n_spans, a parameter
+ * out of range or a nonzero reserved field, a lexicon of another device, a cost that is NaN, +-inf or negative (found on the device
+ * in the same pass; the message names the first such word).  The handle stays usable.  n_words = 0 launches nothing.  Runs on the
+ * recogniser's stream behind what is queued there, and blocks.  Oracle: tests/lexicon_lattice_oracle.py; kernels:
+ * csrc/lexicon_lattice.hip (the grid, best-k and merges of the lexicon kernels; the word's span rows in LDS, the DP column in
+ * registers with the last four old values beside it; one wave per returned pair recomputes the table and walks it back). */
+typedef struct ocr_lexlat_params {
+  double  ins_cost;      /* finite, >= 0; default 4.0: an entry character with no piece */
+  double  del_cost;      /* finite, >= 0; default 4.0: a piece with no entry character  */
+  double  span_cost[4];  /* finite, >= 0; default 0: added once per segment of m pieces */
+  int32_t max_span;      /* 1..OCR_LATTICE_MAX_SPAN, default 2 */
+  int32_t max_len_diff;  /* 0..8, default 2 */
+  int32_t fold_case;     /* 0 | 1, default 1 */
+  int32_t top_k;         /* 1..8, default 1 */
+  int32_t reserved[2];   /* must be 0 */
+} ocr_lexlat_params_t;
+typedef struct ocr_lexlat_matches {
+  int32_t n_words, top_k, n_pieces;
+  const int32_t* entries;       /* [n_words*top_k] caller's entry index, -1 past the candidates */
+  const double*  costs;         /* [n_words*top_k] +inf past the candidates                     */
+  const double*  raw_costs;     /* [n_words]                                                    */
+  const int32_t* n_candidates;  /* [n_words]                                                    */
+  const int32_t* word_flags;    /* [n_words] 1 no pieces, 2 more than 32 pieces, 4 no entry of an admissible length */
+  const int32_t* seg_len;       /* [top_k*n_pieces] */
+  const int32_t* seg_char;      /* [top_k*n_pieces] */
+  const int32_t* n_ins;         /* [n_words*top_k]  */
+} ocr_lexlat_matches_t;
+void ocr_lexlat_default_params(ocr_lexlat_params_t* p);
+/* *out: ocr_lexlat_matches_free. */
+int  ocr_lexicon_lattice_match(ocr_rec_t* rec, const ocr_lexicon_t* lex, const float* costs, int n_spans, int mem_kind,
+                               const int32_t* span_offsets, const int32_t* piece_offsets, int n_words,
+                               const ocr_lexlat_params_t* params, ocr_lexlat_matches_t** out);
+void ocr_lexlat_matches_free(ocr_lexlat_matches_t* m);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU exchange.  Frames and crops are independent (eval-mode batch norm), so a batch shards over the GPUs of
  * a node with no data-path collective: one process (or thread) per GPU, each with its own detector / recogniser

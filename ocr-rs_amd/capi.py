@@ -44,6 +44,7 @@ EXPORTS = [
     "ocr_char_lm_create", "ocr_char_lm_destroy", "ocr_lm_default_params", "ocr_lm_decode", "ocr_lm_paths_free",
     "ocr_split_default_params", "ocr_split_glyphs", "ocr_piece_map_free", "ocr_glyph_spans", "ocr_span_table_free",
     "ocr_lattice_default_params", "ocr_lattice_decode", "ocr_lattice_paths_free",
+    "ocr_lexlat_default_params", "ocr_lexicon_lattice_match", "ocr_lexlat_matches_free",
     "ocr_ctc_beam_decode",
     "ocr_comm_unique_id", "ocr_comm_rccl_version", "ocr_comm_create", "ocr_comm_destroy",
     "ocr_comm_all_gather_polygons", "ocr_comm_all_gather_labels",
@@ -208,6 +209,20 @@ class LatticePathsBlock(C.Structure):
     _fields_ = [("n_words", C.c_int32), ("top_k", C.c_int32), ("n_pieces", C.c_int32), ("labels", C.POINTER(C.c_int32)),
                 ("seg_len", C.POINTER(C.c_int32)), ("n_chars", C.POINTER(C.c_int32)), ("costs", C.POINTER(C.c_double)),
                 ("raw_costs", C.POINTER(C.c_double)), ("word_flags", C.POINTER(C.c_int32))]
+
+
+class LexLatParams(C.Structure):
+    """ocr_lexlat_params_t."""
+    _fields_ = [("ins_cost", C.c_double), ("del_cost", C.c_double), ("span_cost", C.c_double * 4), ("max_span", C.c_int32),
+                ("max_len_diff", C.c_int32), ("fold_case", C.c_int32), ("top_k", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class LexLatMatchesBlock(C.Structure):
+    """ocr_lexlat_matches_t."""
+    _fields_ = [("n_words", C.c_int32), ("top_k", C.c_int32), ("n_pieces", C.c_int32), ("entries", C.POINTER(C.c_int32)),
+                ("costs", C.POINTER(C.c_double)), ("raw_costs", C.POINTER(C.c_double)), ("n_candidates", C.POINTER(C.c_int32)),
+                ("word_flags", C.POINTER(C.c_int32)), ("seg_len", C.POINTER(C.c_int32)), ("seg_char", C.POINTER(C.c_int32)),
+                ("n_ins", C.POINTER(C.c_int32))]
 
 
 LEX_MAX_LEN = 32
@@ -401,6 +416,12 @@ def lib() -> C.CDLL:
                                          C.POINTER(LatticeParams), C.POINTER(C.POINTER(LatticePathsBlock))]
         L.ocr_lattice_paths_free.argtypes = [C.POINTER(LatticePathsBlock)]
         L.ocr_lattice_paths_free.restype = None
+        L.ocr_lexlat_default_params.argtypes = [C.POINTER(LexLatParams)]
+        L.ocr_lexlat_default_params.restype = None
+        L.ocr_lexicon_lattice_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.POINTER(LexLatParams), C.POINTER(C.POINTER(LexLatMatchesBlock))]
+        L.ocr_lexlat_matches_free.argtypes = [C.POINTER(LexLatMatchesBlock)]
+        L.ocr_lexlat_matches_free.restype = None
         L.ocr_rec_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_rec_destroy.argtypes = [C.c_void_p]
         L.ocr_rec_destroy.restype = None
@@ -1369,6 +1390,73 @@ class LatticePaths:
         return LatticePaths(arr(s.labels, k * n, np.int32).reshape(k, n), arr(s.seg_len, k * n, np.int32).reshape(k, n),
                             arr(s.n_chars, nw * k, np.int32).reshape(nw, k), arr(s.costs, nw * k, np.float64).reshape(nw, k),
                             arr(s.raw_costs, nw, np.float64), arr(s.word_flags, nw, np.int32))
+
+
+def lexlat_params(**fields) -> LexLatParams:
+    """ocr_lexlat_default_params with the given fields overridden (ins_cost, del_cost, span_cost: up to 4 values, max_span,
+    max_len_diff, fold_case, top_k, reserved)."""
+    p = LexLatParams()
+    lib().ocr_lexlat_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k in ("reserved", "span_cost"):
+            for i, x in enumerate(v):
+                getattr(p, k)[i] = int(x) if k == "reserved" else float(x)
+        elif k in ("ins_cost", "del_cost"):
+            setattr(p, k, float(v))
+        elif k in ("max_span", "max_len_diff", "fold_case", "top_k"):
+            setattr(p, k, int(v))
+        else:
+            raise TypeError(f"unknown lexicon-lattice parameter {k!r}")
+    return p
+
+
+def _as_lexlat_params(params) -> Optional[LexLatParams]:
+    if params is None or isinstance(params, LexLatParams):
+        return params
+    return lexlat_params(**params)
+
+
+class LexLatMatches:
+    """The arrays of an ocr_lexlat_matches_t, copied into numpy: entries and costs n_words x top_k (-1 and +inf past the candidates),
+    raw_costs [n_words] f64 (the cheapest free segmentation), n_candidates and word_flags [n_words] (1 no pieces, 2 more than 32
+    pieces, 4 no entry of an admissible length), seg_len and seg_char top_k x n_pieces int32 (m and the entry position at the first
+    piece of a segment; seg_len 0 inside a segment, -1 at a deleted piece), n_ins n_words x top_k (entry characters without a
+    segment)."""
+
+    def __init__(self, entries, costs, raw_costs, n_candidates, word_flags, seg_len, seg_char, n_ins):
+        self.entries = np.ascontiguousarray(entries, dtype=np.int32)
+        self.costs = np.ascontiguousarray(costs, dtype=np.float64)
+        self.raw_costs = np.ascontiguousarray(raw_costs, dtype=np.float64)
+        self.n_candidates = np.ascontiguousarray(n_candidates, dtype=np.int32)
+        self.word_flags = np.ascontiguousarray(word_flags, dtype=np.int32)
+        self.seg_len = np.ascontiguousarray(seg_len, dtype=np.int32)
+        self.seg_char = np.ascontiguousarray(seg_char, dtype=np.int32)
+        self.n_ins = np.ascontiguousarray(n_ins, dtype=np.int32)
+
+    @property
+    def n_words(self) -> int:
+        return self.entries.shape[0]
+
+    @property
+    def top_k(self) -> int:
+        return self.entries.shape[1]
+
+    def segments(self, piece_offsets, w: int, k: int = 0) -> list:
+        """alignment k of word w as [(first piece, length, entry position)] with piece indices into the block"""
+        p0, p1 = int(piece_offsets[w]), int(piece_offsets[w + 1])
+        return [(p, int(self.seg_len[k, p]), int(self.seg_char[k, p])) for p in range(p0, p1) if self.seg_len[k, p] > 0]
+
+    @staticmethod
+    def from_block(mp) -> "LexLatMatches":
+        s = mp.contents
+        nw, k, n = s.n_words, s.top_k, s.n_pieces
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return LexLatMatches(arr(s.entries, nw * k, np.int32).reshape(nw, k), arr(s.costs, nw * k, np.float64).reshape(nw, k),
+                             arr(s.raw_costs, nw, np.float64), arr(s.n_candidates, nw, np.int32), arr(s.word_flags, nw, np.int32),
+                             arr(s.seg_len, k * n, np.int32).reshape(k, n), arr(s.seg_char, k * n, np.int32).reshape(k, n),
+                             arr(s.n_ins, nw * k, np.int32).reshape(nw, k))
 
 
 class CharLm:
@@ -2362,6 +2450,32 @@ class Recognizer:
 
     def lattice_decode_device(self, lm: "CharLm", costs_ptr: int, n_spans: int, span_offsets, piece_offsets, params=None) -> LatticePaths:
         return self._lattice_decode(lm, C.c_void_p(costs_ptr or None), n_spans, MEM_DEVICE, span_offsets, piece_offsets, params)
+
+    def _lexicon_lattice_match(self, lex, costs_ptr, n_spans: int, mem_kind: int, span_offsets, piece_offsets, params) -> LexLatMatches:
+        so = np.ascontiguousarray(span_offsets, dtype=np.int32).reshape(-1)
+        po = np.ascontiguousarray(piece_offsets, dtype=np.int32).reshape(-1)
+        if len(so) != len(po):
+            raise ValueError(f"{len(so)} span offsets, {len(po)} piece offsets")
+        prm = _as_lexlat_params(params)
+        out = C.POINTER(LexLatMatchesBlock)()
+        check(lib().ocr_lexicon_lattice_match(self._h, lex.handle if isinstance(lex, Lexicon) else lex, costs_ptr, n_spans, mem_kind,
+                                              _ptr(so) if so.size else None, _ptr(po) if po.size else None, len(so) - 1,
+                                              C.byref(prm) if prm is not None else None, C.byref(out)))
+        try:
+            return LexLatMatches.from_block(out)
+        finally:
+            lib().ocr_lexlat_matches_free(out)
+
+    def lexicon_lattice_match(self, lex: "Lexicon", costs: np.ndarray, span_offsets, piece_offsets, params=None) -> LexLatMatches:
+        """ocr_lexicon_lattice_match: costs n_spans x 62 f32 in host memory (glyph_costs of the span crops), span_offsets and
+        piece_offsets [n_words+1] (SpanTable); params: LexLatParams, a dict of its fields, or None (defaults).  Blocking, on the
+        handle's stream."""
+        x = np.ascontiguousarray(costs, dtype=np.float32).reshape(-1, 62)
+        return self._lexicon_lattice_match(lex, _ptr(x) if x.size else None, x.shape[0], MEM_HOST, span_offsets, piece_offsets, params)
+
+    def lexicon_lattice_match_device(self, lex: "Lexicon", costs_ptr: int, n_spans: int, span_offsets, piece_offsets,
+                                     params=None) -> LexLatMatches:
+        return self._lexicon_lattice_match(lex, C.c_void_p(costs_ptr or None), n_spans, MEM_DEVICE, span_offsets, piece_offsets, params)
 
 
 def python_to_polygons(polys, scores):

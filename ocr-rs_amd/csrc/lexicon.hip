@@ -23,6 +23,7 @@
 #include <memory>
 
 #include "api_internal.hpp"
+#include "lexicon_handle.hpp"
 #include "lexicon_host.hpp"
 
 namespace ocr {
@@ -248,21 +249,7 @@ __global__ __launch_bounds__(64) void lex_merge_kernel(const LexWordJob* __restr
 }  // namespace
 }  // namespace ocr
 
-// ---- the C surface of the three calls (include/ocr_amd.h)
-struct ocr_lexicon {
-  int device = 0;
-  ocr::LexPacked host;   // start[] and n are read by every match; the arrays are released after the upload
-  void* dev = nullptr;   // codes | lens | index, carved
-  size_t o_codes = 0, o_lens = 0, o_index = 0;
-  ~ocr_lexicon() {
-    if (dev) {
-      (void)hipSetDevice(device);
-      (void)hipDeviceSynchronize();   // whatever was queued with the lexicon has finished before its memory goes
-      (void)hipFree(dev);
-    }
-  }
-};
-
+// ---- the C surface of the three calls (include/ocr_amd.h; struct ocr_lexicon: lexicon_handle.hpp)
 namespace {
 struct MatchesOwned {   // the library-owned storage behind an ocr_lexicon_matches_t* (released by ocr_lexicon_matches_free)
   ocr_lexicon_matches_t view{};

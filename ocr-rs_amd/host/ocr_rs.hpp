@@ -12,6 +12,7 @@
 //   CharLm / lm_decode: words decoded under a character-bigram model from the same glyph costs, k best readings (ocr_lm_decode)
 //   split_glyphs / glyph_spans / lattice_decode: wide glyphs cut into pieces, runs of pieces recognised, segmentation and classes
 //     chosen together under the model (ocr_split_glyphs, ocr_glyph_spans, ocr_lattice_decode)
+//   lexicon_lattice_match: the entries of a Lexicon matched over the pieces, a character reading a run of pieces (ocr_lexicon_lattice_match)
 //   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words,
 //     or through curved strips (ocr_plan_curved_strips / ocr_extract_curved_strips), for words that bend
 //   group_lines / read_lines: the words of every page grouped into text lines in reading order (ocr_group_lines), the "output text" step
@@ -496,6 +497,37 @@ inline LatticePaths lattice_decode(const char_recognition::Net& rec_net, const C
   out.raw_costs.assign(m->raw_costs, m->raw_costs + nw);
   out.word_flags.assign(m->word_flags, m->word_flags + nw);
   ocr_lattice_paths_free(m);
+  return out;
+}
+// The joint search (ocr_lexicon_lattice_match): entries matched over the pieces, a character reading a span of 1..max_span pieces.
+// entries, costs and n_ins are n_words x top_k; seg_len and seg_char top_k x n_pieces (m and the entry position at the first piece of
+// a segment; seg_len 0 inside a segment, -1 at a deleted piece); the others are per word.
+struct LexLatMatches {
+  int top_k = 1, n_pieces = 0;
+  std::vector<int32_t> entries, n_candidates, word_flags, seg_len, seg_char, n_ins;
+  std::vector<double> costs, raw_costs;
+};
+inline LexLatMatches lexicon_lattice_match(const char_recognition::Net& rec_net, const Lexicon& lex, const std::vector<float>& costs,
+                                           const std::vector<int32_t>& span_offsets, const std::vector<int32_t>& piece_offsets,
+                                           const ocr_lexlat_params_t* params = nullptr) {
+  if (span_offsets.empty() || span_offsets.size() != piece_offsets.size() || costs.size() != 62 * (size_t)span_offsets.back())
+    throw Error(OCR_ERR_INVALID, "costs do not match the span offsets, or the two offset arrays differ in length");
+  ocr_lexlat_matches_t* m = nullptr;
+  check(ocr_lexicon_lattice_match(rec_net.handle(), lex.handle(), costs.empty() ? nullptr : costs.data(), (int)(costs.size() / 62),
+                                  OCR_MEM_HOST, span_offsets.data(), piece_offsets.data(), (int)span_offsets.size() - 1, params, &m));
+  LexLatMatches out;
+  const size_t nw = (size_t)m->n_words, k = (size_t)m->top_k, np = (size_t)m->n_pieces;
+  out.top_k = m->top_k;
+  out.n_pieces = m->n_pieces;
+  out.entries.assign(m->entries, m->entries + nw * k);
+  out.costs.assign(m->costs, m->costs + nw * k);
+  out.raw_costs.assign(m->raw_costs, m->raw_costs + nw);
+  out.n_candidates.assign(m->n_candidates, m->n_candidates + nw);
+  out.word_flags.assign(m->word_flags, m->word_flags + nw);
+  out.seg_len.assign(m->seg_len, m->seg_len + k * np);
+  out.seg_char.assign(m->seg_char, m->seg_char + k * np);
+  out.n_ins.assign(m->n_ins, m->n_ins + nw * k);
+  ocr_lexlat_matches_free(m);
   return out;
 }
 

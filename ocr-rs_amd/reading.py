@@ -38,6 +38,8 @@ recognition -> output text), composed over the C ABI.
         ocr_glyph_spans           pieces -> every run of 1..max_span pieces, a glyph block (csrc/lattice_host.cpp, host)
         ocr_extract_glyph_crops, ocr_rec_classify, ocr_rec_glyph_costs on the spans
         ocr_lattice_decode        every word -> its k cheapest (segmentation, classes) pairs (csrc/lattice.hip)
+    ... and with lattice_lexicon=capi.Lexicon the word list is searched over the same pieces:
+        ocr_lexicon_lattice_match every word's pieces against every entry, a character reading a run of pieces (csrc/lexicon_lattice.hip)
 
 The segmentation, strip and line rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
 tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py, tests/strip_oracle.py, tests/curved_strip_oracle.py and
@@ -161,12 +163,17 @@ def _word(text: str, probs, where, k: int, n_glyphs: int, matches, lexicon, max_
     return (out, probs, where, *extra)
 
 
-def _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params, cc, lm, lattice, split):
+def _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params, cc, lm, lattice, split, lattice_lexicon=None,
+                        lattice_lexicon_params=None, max_penalty=1.5):
     """segment -> split -> spans -> crops -> classify + costs -> decode, everything between the calls on the device; per word
-    (text, probs, where, (cost, raw_cost, raw_text, seg_len)) with text, probs and where (the union boxes) along hypothesis 0's segments."""
+    (text, probs, where, (cost, raw_cost, raw_text, seg_len)) with text, probs and where (the union boxes) along hypothesis 0's segments.
+    With lattice_lexicon the joint match runs on the same span costs, and a word it accepts takes the entry's string, with probs and
+    where along the match's segments; every tuple then gains (entry or -1, cost, raw_cost, seg_len of the match over the word's pieces)."""
     import torch
     if lm is not None and not isinstance(lm, capi.CharLm):
         raise TypeError(f"lm: expected a capi.CharLm, got {type(lm).__name__}")
+    if lattice_lexicon is not None and not isinstance(lattice_lexicon, capi.Lexicon):
+        raise TypeError(f"lattice_lexicon: expected a capi.Lexicon, got {type(lattice_lexicon).__name__}")
     prm = capi._as_lattice_params(lattice)
     glyphs = det.segment_glyphs_device(x.data_ptr(), n, h, w, polys, adjust_values, params, cc)
     pieces, _ = det.split_glyphs_device(x.data_ptr(), n, h, w, glyphs, split)
@@ -190,6 +197,14 @@ def _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params,
     else:
         with capi.CharLm(rec, np.zeros((64, 64), np.float32)) as zero:
             paths = rec.lattice_decode_device(zero, costs_ptr, ns, so, po, prm)
+    matches = None
+    if lattice_lexicon is not None:
+        given = capi._as_lexlat_params(lattice_lexicon_params)
+        mp = capi.LexLatParams.from_buffer_copy(given) if given is not None else capi.lexlat_params()
+        mp.max_span = prm.max_span              # the lattice's spans and span costs: both searches read the same rows
+        for i in range(4):
+            mp.span_cost[i] = prm.span_cost[i]
+        matches = rec.lexicon_lattice_match_device(lattice_lexicon, costs_ptr, ns, so, po, mp)
     M = prm.max_span
     base = lambda e: e * (e + 1) // 2 if e <= M else M * (M + 1) // 2 + (e - M) * M   # the spans in front of end e + 1
     out = []
@@ -202,15 +217,21 @@ def _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params,
             segs = [(p - p0, m) for p, m, _ in paths.segments(po, k)] if int(paths.word_flags[k]) == 0 else [(i, 1) for i in range(G)]
             rows = [s0 + base(i + m - 1) + (m - 1) for i, m in segs]
             text = paths.text(po, k) if int(paths.word_flags[k]) == 0 else raw_text
-            words.append((text, probs[rows].copy() if rows else np.zeros(0, np.float64), spans.boxes[rows].reshape(-1, 4).copy(),
-                          (float(paths.costs[k, 0]), float(paths.raw_costs[k]), raw_text, tuple(m for _, m in segs))))
+            extra = [(float(paths.costs[k, 0]), float(paths.raw_costs[k]), raw_text, tuple(m for _, m in segs))]
+            if matches is not None:
+                e, c, r = int(matches.entries[k, 0]), float(matches.costs[k, 0]), float(matches.raw_costs[k])
+                if e >= 0 and c - r <= float(max_penalty) * G:
+                    text = lattice_lexicon.words[e]
+                    rows = [s0 + base(p - p0 + m - 1) + (m - 1) for p, m, _ in matches.segments(po, k)]
+                extra.append((e, c, r, tuple(int(v) for v in matches.seg_len[0, p0:p0 + G])))
+            words.append((text, probs[rows].copy() if rows else np.zeros(0, np.float64), spans.boxes[rows].reshape(-1, 4).copy(), *extra))
         out.append(words)
     return out
 
 
 def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None, cc=None, mask=None, lexicon=None,
                lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None, lattice=None,
-               split=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+               split=None, lattice_lexicon=None, lattice_lexicon_params=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch.
 
     det_net: text_detection.FuncT or capi.Detector (supplies the GPU and stream of the segmentation); rec_net: char_recognition.Net
@@ -237,7 +258,15 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     created for the call; lm_params is not used, top_k is the lattice's).  The text is hypothesis 0's, probs and where follow its
     segments (where holds the union box of every segment), and the tuple gains (cost, raw_cost, raw_text, seg_len) as its last
     element: raw_text is the reading of the pieces one by one, seg_len the pieces per character.  Masked crops with a lattice raise
-    OcrError (labels do not map to pieces), and so does lexicon= (a joint search is not built).  With lattice=None nothing changes."""
+    OcrError (labels do not map to pieces), and so does lexicon= (the match over a fixed segmentation; the joint search is
+    lattice_lexicon=).  With lattice=None nothing changes.
+    lattice_lexicon: None, or a capi.Lexicon on the recogniser's GPU, with lattice= only: after the decode the entries are matched
+    over the pieces on the same span costs (ocr_lexicon_lattice_match with lattice_lexicon_params: capi.LexLatParams, a dict of its
+    fields or None; max_span and span_cost are always the lattice's).  A word takes the best entry's string when an entry exists and
+    cost - raw_cost <= max_penalty * G for its G pieces (f64); its probs and where then follow the match's segments (an inserted
+    character has none, and neither has a deleted piece).  Every tuple gains (entry index or -1, cost, raw_cost, seg_len) as its last
+    element, seg_len being the match's per piece: m at the first piece of a segment, 0 inside it, -1 at a deleted piece.  With
+    lattice_lexicon=None nothing changes."""
     import torch
 
     det = _handle(det_net, capi.Detector)
@@ -260,8 +289,11 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
         if _masked(mask, cc):
             raise capi.OcrError(1, "lattice: masked crops are not built for pieces (labels do not map to them)")
         if lexicon is not None:
-            raise capi.OcrError(1, "lattice: a joint search with a lexicon is not built")
-        return _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params, cc, lm, lattice, split)
+            raise capi.OcrError(1, "lattice: lexicon= matches a fixed segmentation; the joint search is lattice_lexicon=")
+        return _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params, cc, lm, lattice, split, lattice_lexicon,
+                                   lattice_lexicon_params, max_penalty)
+    if lattice_lexicon is not None:
+        raise capi.OcrError(1, "lattice_lexicon: the joint search needs lattice= ({} for its defaults)")
     glyphs, crops = _segment_and_crop(det, x.data_ptr(), n, h, w, polys, adjust_values, params, cc, mask, dev)   # blocking
     ng = glyphs.n_glyphs
     labels, probs, matches, paths = _classify(rec, crops, ng, dev, glyphs.word_offsets, lexicon, lexicon_params, lm, lm_params)
