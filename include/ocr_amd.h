@@ -324,6 +324,16 @@ int ocr_det_detect_pipelined_host(ocr_det_t* det, const void* x_host, int x_elem
  * 255 (load_image_as_tensor's scaling, image_ops.rs:80-83): crops is n_polygons x 784 f32, ready
  * for ocr_rec_forward / ocr_rec_classify.  frames: N x 1 x H x W f32 (the detector's input).
  * frames and crops share mem_kind; polys and adj_xy are host memory.  Rule: oracle/crop_oracle.py.
+ * The box of a polygon, in f64: x0 = min(max(min_v x_v * adj_x, 0), W - 1), x1 = min(max(max_v x_v * adj_x + 1, x0 + 1), W),
+ * likewise y: always inside the frame and at least one pixel wide and tall, wherever the polygon lies (a polygon off the frame
+ * yields the nearest border pixel).  Non-finite adjust values: a NaN product x_v * adj_x takes no part in the minimum or the
+ * maximum; an axis on which every product is NaN yields the last pixel, [W - 1, W] or [H - 1, H]; +-inf clamps like any other
+ * value.  No adjust value makes the kernel read outside the frame.
+ * Limits: N >= 0, 1 <= H, W <= 2^24 (sample positions are f32), polys->n_images == N; the frame block may exceed 2^31 bytes
+ * (every offset is 64-bit; host frames are staged whole in device scratch, so device memory is the only bound).  N = 0 or a
+ * block without polygons does nothing and writes nothing.  OCR_ERR_INVALID for anything outside the limits, a null pointer
+ * (crops may be null only when there is no polygon) and a mem_kind other than OCR_MEM_HOST / OCR_MEM_DEVICE; nothing is
+ * written and the handle stays usable.
  * Stream order: the crop kernel runs behind everything queued on the detector's stream when the call is made - except,
  * while a pipelined batch is pending (ocr_det_detect_pipelined*), the forward of that pending batch: the crops of the batch
  * that has come back are cut beside it, behind whatever was queued before that forward was.  Device frames written by work
@@ -795,7 +805,12 @@ const char* ocr_rec_alphabet(void);
  * CTC greedy (best-path) decode of a sequence recogniser's output, the stage BASELINE.json's north_star names.  logits N x T x C f32
  * (or any monotone transform of them), blank in [0, C): per crop the first class attaining each column's maximum, consecutive repeats
  * collapsed, blanks dropped -> labels N x T int32 (row i: lengths[i] classes, then -1) and lengths N.  One wave per crop on the handle's
- * GPU and stream; blocking; mem_kind says where the three buffers live.  Exact integers: oracle/ctc_oracle.py. */
+ * GPU and stream; blocking; mem_kind says where the three buffers live.  Exact integers: oracle/ctc_oracle.py.
+ * Defined for logits without NaN.  +-inf are ordinary values (a column of -inf decodes to class 0, +inf at several classes to the
+ * lowest of them).  A crop that holds a NaN decodes to something unspecified - still lengths[i] in [0, T], that many classes of
+ * [0, C), then -1 - and every other crop of the batch is unaffected.  Exactly N x T labels and N lengths are written.
+ * T >= 1, C >= 1, N >= 0 (N = 0 does nothing).  OCR_ERR_INVALID for anything outside that, a blank outside [0, C), a null pointer
+ * and a mem_kind other than OCR_MEM_HOST / OCR_MEM_DEVICE; nothing is written and the handle stays usable. */
 int ocr_ctc_greedy_decode(ocr_rec_t* rec, const float* logits, int n, int t, int c, int blank, int mem_kind, int32_t* labels,
                           int32_t* lengths);
 /* EXTENSION - no counterpart in the reference (see above): CTC prefix beam search returning the beam_width (B) most probable label

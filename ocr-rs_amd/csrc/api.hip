@@ -376,7 +376,10 @@ int ocr_preprocess_batch(ocr_det_t* det, const ocr_image_t* images, int n, int s
   });
 }
 
-// the box of every polygon in frame coordinates (oracle/crop_oracle.py crop_boxes), shared by the crop and glyph entry points
+// the box of every polygon in frame coordinates (oracle/crop_oracle.py crop_boxes), shared by the crop and glyph entry points.
+// h, w >= 1 (the callers check).  Non-finite adjust values cannot move a box off the frame: std::min / std::max keep their first
+// argument against a NaN, so a NaN product never enters an extreme and an axis whose products are all NaN keeps the +-1e300
+// sentinels, which clamp to the last pixel [w - 1, w] / [h - 1, h]; +-inf clamps like any other value.
 static std::vector<ocr::CropBox> crop_boxes(const ocr_polygons_t* polys, const double* adj_xy, int n, int h, int w) {
   std::vector<ocr::CropBox> boxes;
   boxes.reserve(polys->n_polygons);
@@ -402,8 +405,11 @@ int ocr_extract_crops(ocr_det_t* det, const float* frames, int n, int h, int w, 
   return guard([&] {
     using namespace ocr;
     if (!det || !frames || !polys || !adj_xy || (!crops && polys->n_polygons > 0)) fail(OCR_ERR_INVALID, "extract_crops: null argument");
+    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "extract_crops: mem_kind %d", mem_kind);
+    // H, W <= 2^24: the kernel clamps a sample position to (float)(H - 1), which is H - 1 itself only up to there
+    if (n < 0 || h < 1 || w < 1 || h > (1 << 24) || w > (1 << 24))
+      fail(OCR_ERR_INVALID, "extract_crops: N=%d H=%d W=%d (limits: N >= 0, H and W 1..2^24)", n, h, w);
     if (polys->n_images != n) fail(OCR_ERR_INVALID, "extract_crops: polygon block holds %d images, frames %d", polys->n_images, n);
-    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "mem_kind %d", mem_kind);
     const int np = polys->n_polygons;
     if (np == 0) return;
     const std::vector<CropBox> boxes = crop_boxes(polys, adj_xy, n, h, w);
@@ -1316,6 +1322,7 @@ int ocr_ctc_greedy_decode(ocr_rec_t* rec, const float* logits, int n, int t, int
   return guard([&] {
     using namespace ocr;
     if (!rec || !logits || !labels || !lengths) fail(OCR_ERR_INVALID, "ctc_greedy_decode: null argument");
+    if (mem_kind != OCR_MEM_HOST && mem_kind != OCR_MEM_DEVICE) fail(OCR_ERR_INVALID, "ctc_greedy_decode: mem_kind %d", mem_kind);
     if (n < 0 || t <= 0 || c <= 0 || blank < 0 || blank >= c) fail(OCR_ERR_INVALID, "ctc_greedy_decode: N=%d T=%d C=%d blank=%d", n, t, c, blank);
     if (n == 0) return;
     OCR_HIP(hipSetDevice(rec->impl.device()));

@@ -16,18 +16,37 @@ import numpy as np
 F = np.float32
 
 
+def _extremes(vs):
+    """(min, max) of the products that are not NaN: a comparison with a NaN is false, so a NaN never replaces the running extreme,
+    whatever its place in the list (Python's min() / max() would depend on that place).  No such product at all leaves the +-1e300
+    sentinels, which the clamps of crop_boxes turn into the last pixel.  Finite products: the plain minimum and maximum."""
+    mn, mx = 1e300, -1e300
+    for v in vs:
+        if v < mn:
+            mn = v
+        if v > mx:
+            mx = v
+    return mn, mx
+
+
+def _clamp(v, lo, hi):
+    """min(max(v, lo), hi) with v never NaN here (lo, hi finite)"""
+    return hi if v > hi else (lo if v < lo else v)
+
+
 def crop_boxes(polys, adj, h, w):
-    """Per polygon: (frame index, x0, y0, x1, y1) as f32, polygons in batch order."""
+    """Per polygon: (frame index, x0, y0, x1, y1) as f32, polygons in batch order.  h, w >= 1.  Non-finite adjust values (pinned by
+    tests/test_gpu_crops.py): NaN products are skipped, an axis with nothing but NaN products gives the last pixel, +-inf clamps."""
     out = []
     for b, plist in enumerate(polys):
         ax, ay = float(adj[b][0]), float(adj[b][1])
         for poly in plist:
-            xs = [p[0] * ax for p in poly]
-            ys = [p[1] * ay for p in poly]
-            x0 = min(max(min(xs), 0.0), w - 1.0)
-            x1 = min(max(max(xs) + 1.0, x0 + 1.0), float(w))
-            y0 = min(max(min(ys), 0.0), h - 1.0)
-            y1 = min(max(max(ys) + 1.0, y0 + 1.0), float(h))
+            mnx, mxx = _extremes([p[0] * ax for p in poly])
+            mny, mxy = _extremes([p[1] * ay for p in poly])
+            x0 = _clamp(mnx, 0.0, w - 1.0)
+            x1 = _clamp(mxx + 1.0, x0 + 1.0, float(w))
+            y0 = _clamp(mny, 0.0, h - 1.0)
+            y1 = _clamp(mxy + 1.0, y0 + 1.0, float(h))
             out.append((b, F(x0), F(y0), F(x1), F(y1)))
     return out
 

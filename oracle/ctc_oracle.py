@@ -8,6 +8,11 @@ characters; a CTC head over it has 62 + 1 blank = 63 classes).  The rule is the 
     a[t]   = the first class attaining the maximum of column t            (ties: lowest class index)
     labels = a with consecutive repeats collapsed, then blanks removed    (i.e. keep a[t] iff a[t] != blank and (t == 0 or a[t] != a[t-1]))
 
+Defined for inputs WITHOUT NaN.  +-inf are ordinary values: a column of -inf decodes to class 0, +inf at several classes to the lowest
+of them, here (np.argmax) as in the kernel (a strict `>` scan).  On a NaN the two differ - np.argmax returns the first NaN, the kernel's
+scan passes over it - so a crop holding a NaN decodes to something unspecified (include/ocr_amd.h says the same): the kernel still
+writes a well-formed row for it, and the other crops of the batch equal this oracle.
+
 Parity unpinned by the reference (it holds no such test); pinned by the hand-written vectors of tests/test_ctc.py.
 """
 from __future__ import annotations
