@@ -13,7 +13,10 @@
  * single-threaded calls).  DIFFERENT handles are independent: the
  * library keeps no shared mutable state, so threads that each own their handles
  * (a serving process, or one thread per GPU) may call concurrently and get the
- * bits they would get alone (tests/test_gpu_threads.py).
+ * bits they would get alone (tests/test_gpu_threads.py: detection through
+ * classify, and the reading calls, both CTC decoders and ocr_preprocess_batch).
+ * What the library sets per device function rather than per handle (the beam
+ * kernel's dynamic-LDS attribute) is set to one value whatever the call.
  */
 #ifndef OCR_AMD_H
 #define OCR_AMD_H

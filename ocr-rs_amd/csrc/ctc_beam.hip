@@ -307,9 +307,13 @@ void launch_ctc_beam(const float* logits_dev, int n, int t, int c, int blank, in
   if (t < 1 || t > kMaxT || c < 1 || c > kMaxC || blank < 0 || blank >= c || beam_width < 1 || beam_width > kMaxB)
     fail(OCR_ERR_INVALID, "ctc_beam_decode: T=%d C=%d blank=%d B=%d", t, c, blank, beam_width);
   const size_t lds = lds_bytes(t, beam_width);
-  // (per launch: the attribute belongs to the device the calling thread has current; __syncthreads_or holds 256 B of static LDS,
-  // so the dynamic request is exactly what this shape needs, not the 160 KB ceiling)
-  OCR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_beam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  // (per launch: the attribute belongs to the device the calling thread has current.  It belongs to the function, not to a handle,
+  // so its value is the need of the limits (97 472 B; with the 256 B of static LDS that __syncthreads_or holds, well under 160 KB)
+  // whatever this launch's shape: handles that launch side by side then only ever write the same value, and none can lower it
+  // between another's set and launch.  The launch itself still requests exactly what its shape needs.)
+  static_assert(sizeof(Fixed) == 7360, "tests/test_ctc_beam.py restates lds_bytes() with this size");
+  const size_t lds_limit = lds_bytes(kMaxT, kMaxB);
+  OCR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_beam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
   hipLaunchKernelGGL(ctc_beam_kernel, dim3((unsigned)n), dim3(kThreads), lds, s, logits_dev, t, c, blank, beam_width, prefix_stride(t), labels_dev,
                      lengths_dev, scores_dev, bad_crop_dev);
   OCR_HIP(hipGetLastError());
