@@ -364,7 +364,8 @@ int ocr_extract_crops(ocr_det_t* det, const float* frames, int n, int h, int w, 
  * bilinear taps at floor(sx), floor(sy) in ocr_extract_crops's operation order; a tap reads r = (v - bg) / (ink - bg) as
  * g = r > 0 ? min(r, 1) : 0 (NaN -> 0) inside the glyph box and 0 outside it; ink_high = 0 writes 1 - o.  f32, separately rounded.
  * Out of scope: touching or kerned glyphs (they stay one glyph), rotated or curved words (the box is axis-aligned and pixels are not
- * masked by the polygon), lexicons, spaces inside a polygon.  Oracle: tests/glyph_oracle.py; kernels: csrc/glyphs.hip.
+ * masked by the polygon), lexicons.  Spaces inside a polygon are ocr_break_words', on the block this call returns.  Oracle:
+ * tests/glyph_oracle.py; kernels: csrc/glyphs.hip.
  * Both calls are blocking and run behind everything queued on the detector's stream; no overlap with a pending pipelined forward
  * (ocr_det_detect_pipelined*) is promised.  frames: N x 1 x H x W f32 in mem_kind memory; polys, adj_xy, params and the glyph block
  * are host memory; crops (n_glyphs x 784 f32) lives in the same mem_kind as frames.  OCR_ERR_INVALID for a null pointer, a bad mem_kind,
@@ -645,7 +646,8 @@ void ocr_curved_strips_free(ocr_curved_strips_t* s);
  *   word, ascending.  gaps[p] is g / hmax of the link that leads to the word at position p of `order`, 0.0 for a head: callers decide
  *   from it what is a space and what is a tab.
  * Out of scope: column detection (two columns closer than max_gap heights merge line by line, and the lines of wider-spaced columns
- *   interleave by height), right-to-left and vertical scripts, spaces inside a polygon, paragraph structure.
+ *   interleave by height), right-to-left and vertical scripts, paragraph structure.  Spaces inside a polygon are ocr_break_words':
+ *   the reading calls put them into a word's text before the lines join the texts.
  * Oracle: tests/line_oracle.py; kernels: csrc/lines.hip (link kernel over all pairs of an image, chain kernel per image).
  * The call is blocking and runs behind everything queued on the detector's stream, like the glyph calls (no overlap with a pending
  * pipelined forward is promised).  All pointers are host memory.  OCR_ERR_INVALID for a null pointer (params == NULL -> defaults),
@@ -710,7 +712,7 @@ void ocr_lines_free(ocr_lines_t* l);
  *    cap defines the result anyway.  The blocks of an image are ordered by (level, TL.y, TL.x, index), ascending.
  * Consequences (documented, not handled): a full-width heading within block_reach of the columns joins the column whose first line is
  *   nearest below it; a regular grid of words whose gaps reach min_gutter is a table and is read column by column.  Out of scope:
- *   tables, nested layouts (no recursive XY-cut), right-to-left and vertical scripts, spaces inside a polygon.
+ *   tables, nested layouts (no recursive XY-cut), right-to-left and vertical scripts (spaces inside a polygon: ocr_break_words).
  * Oracle: tests/column_oracle.py; kernels: csrc/columns.hip (stage A is the launch of ocr_group_lines).  Blocking, on the detector's
  * stream, host pointers, and the error cases of ocr_group_lines (OCR_ERR_INVALID before any launch, the handle stays usable); zero
  * words launch nothing and return valid offsets; at most OCR_LINE_MAX_WORDS words an image. */
@@ -1122,6 +1124,65 @@ int  ocr_lexicon_lattice_match(ocr_rec_t* rec, const ocr_lexicon_t* lex, const f
                                const int32_t* span_offsets, const int32_t* piece_offsets, int n_words,
                                const ocr_lexlat_params_t* params, ocr_lexlat_matches_t** out);
 void ocr_lexlat_matches_free(ocr_lexlat_matches_t* m);
+
+/* EXTENSION - word breaks inside a polygon (BUILD-DEFINED, like the rules above; the reference has no counterpart).  A detector of
+ * this family often returns one polygon for a phrase or a whole line.  ocr_break_words takes a glyph block whose words are polygons
+ * and returns a glyph block whose words are the words inside those polygons, cut at the inter-word gaps, plus the map back to the
+ * polygons.  Every decode call takes its word ranges as an offset array over glyphs and every crop, split and span call takes an
+ * ordinary glyph block, so the chain is segment -> break -> whatever followed the segmentation before.
+ * Rule.  All integer except one f64 score.  Source word k has the glyphs g0..g1-1, G = g1 - g0, with boxes (x0, y0, x1, y1) in block
+ * order; no ordering of the boxes is assumed.
+ *  1. G == 0: one sub-word without glyphs, rule 0, hw 0.  G > OCR_BREAK_MAX_GLYPHS: one sub-word holding every glyph, rule 0, hw 0,
+ *     flag 2.  Otherwise:
+ *  2. h_i = y1 - y0; hw is the element of index G / 2 (integer division) of the heights sorted ascending: the upper median.
+ *  3. for i = 1..G-1: R_i = max over j < i of x1_j (a prefix maximum: component boxes may overlap or nest), gap_i = max(0, x0_i - R_i).
+ *  4. fixed rule (rule 1): a break in front of glyph i iff gap_i * 100 >= space_pct * hw, in int64.
+ *  5. adaptive rule (rule 2), with mode == 1 and n = G - 1 >= min_gaps: the gaps sorted ascending are s_0..s_(n-1).  For every c in
+ *     1..n-1 with s_(c-1) < s_c: n0 = c, n1 = n - c, S0 and S1 the int64 sums of the two sides, d = (double)(S1*n0 - S0*n1) (the
+ *     products are exact in int64), score = d*d / ((double)n0 * (double)n1), every operation separately rounded, no FMA: the Otsu
+ *     form of step 3 of ocr_segment_glyphs.  The highest score wins, ties to the smaller c.  With L = s_(c-1) and T = s_c the split
+ *     is accepted iff T*100 >= min_space_pct*hw and T*100 >= sep_pct*L (int64); then a break in front of glyph i iff gap_i >= T.
+ *     No valid c (all gaps equal), a split that is not accepted, or too few gaps: the fixed rule decides (rule 1).  The adaptive
+ *     rule is what reads letter-spaced text, whose letter gaps alone exceed any fixed share of the height.
+ *  6. the sub-words are the maximal runs of glyphs between breaks, in order.  gap_pct of a sub-word is gap_i * 100 / hw at its first
+ *     glyph (int64, integer division, clamped to INT32_MAX), 0 for the first sub-word of a source word: a caller tells a space from
+ *     a tab by it.
+ * source_info[4k..]: hw, the rule that decided (0 / 1 / 2), the threshold in pixels (rule 2: T; rule 1: the smallest gap that
+ * breaks, ceil(space_pct*hw / 100); rule 0: 0), flags (2: more than OCR_BREAK_MAX_GLYPHS glyphs, not broken).
+ * *words is an ordinary glyph block (ocr_glyphs_free): n_images and n_glyphs are the input's, boxes is the same array, word_offsets
+ * holds the sub-word ranges, img_offsets counts sub-words, and every sub-word carries a copy of its source word's word_info and
+ * word_levels; ocr_extract_glyph_crops, ocr_split_glyphs, ocr_glyph_spans and every decode call take it unchanged.  The masked crop
+ * call does not: component labels are per source word, so masked crops are cut from the source block (its glyph order is the same).
+ * Blocking, on the detector's stream behind everything queued there, all pointers host memory; no overlap with a pending pipelined
+ * forward is promised (as ocr_group_lines).  OCR_ERR_INVALID before any launch for a null pointer (params == NULL -> the defaults),
+ * offsets that do not start at 0, decrease or do not span the glyphs (or the words), a box with x1 <= x0 or y1 <= y0, a coordinate
+ * outside 0..2^22, a parameter out of range or a nonzero reserved field; the handle stays usable.  A block without glyphs launches
+ * nothing and returns valid blocks.
+ * Out of scope: one threshold per polygon with no line-level context, so a single letter-spaced word whose gaps are all equal and
+ * wide breaks at every letter; phrases in the lexicon.
+ * Oracle: tests/word_break_oracle.py; kernel: csrc/word_breaks.hip (one wave per source word, glyph i in lane i % 64, slot i / 64;
+ * both sorts by rank counting over an LDS copy of the wave's keys). */
+#define OCR_BREAK_MAX_GLYPHS 256
+typedef struct ocr_break_params {
+  int32_t mode;           /* 0 fixed, 1 adaptive with the fixed rule behind it (default) */
+  int32_t space_pct;      /* 1..1000, default 35  */
+  int32_t min_space_pct;  /* 1..1000, default 25  */
+  int32_t sep_pct;        /* 100..1000, default 200 */
+  int32_t min_gaps;       /* 3..255, default 3    */
+  int32_t reserved[3];    /* must be 0 */
+} ocr_break_params_t;
+typedef struct ocr_word_breaks {
+  int32_t n_source, n_words;
+  const int32_t* source;       /* [n_words]     source word of every sub-word              */
+  const int32_t* sub_offsets;  /* [n_source+1]  sub-word range per source word (>= 1 each) */
+  const int32_t* gap_pct;      /* [n_words]                                                */
+  const int32_t* source_info;  /* [4*n_source]  hw, rule 0/1/2, threshold in pixels, flags */
+} ocr_word_breaks_t;
+void ocr_break_default_params(ocr_break_params_t* p);
+/* *words: ocr_glyphs_free; *breaks: ocr_word_breaks_free. */
+int  ocr_break_words(ocr_det_t* det, const ocr_glyphs_t* glyphs, const ocr_break_params_t* params,
+                     ocr_glyphs_t** words, ocr_word_breaks_t** breaks);
+void ocr_word_breaks_free(ocr_word_breaks_t* b);
 
 /* ---------------------------------------------------------------------------
  * Multi-GPU exchange.  Frames and crops are independent (eval-mode batch norm), so a batch shards over the GPUs of

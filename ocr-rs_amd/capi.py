@@ -45,6 +45,7 @@ EXPORTS = [
     "ocr_split_default_params", "ocr_split_glyphs", "ocr_piece_map_free", "ocr_glyph_spans", "ocr_span_table_free",
     "ocr_lattice_default_params", "ocr_lattice_decode", "ocr_lattice_paths_free",
     "ocr_lexlat_default_params", "ocr_lexicon_lattice_match", "ocr_lexlat_matches_free",
+    "ocr_break_default_params", "ocr_break_words", "ocr_word_breaks_free",
     "ocr_ctc_beam_decode",
     "ocr_comm_unique_id", "ocr_comm_rccl_version", "ocr_comm_create", "ocr_comm_destroy",
     "ocr_comm_all_gather_polygons", "ocr_comm_all_gather_labels",
@@ -224,6 +225,21 @@ class LexLatMatchesBlock(C.Structure):
                 ("word_flags", C.POINTER(C.c_int32)), ("seg_len", C.POINTER(C.c_int32)), ("seg_char", C.POINTER(C.c_int32)),
                 ("n_ins", C.POINTER(C.c_int32))]
 
+
+class BreakParams(C.Structure):
+    """ocr_break_params_t."""
+    _fields_ = [("mode", C.c_int32), ("space_pct", C.c_int32), ("min_space_pct", C.c_int32), ("sep_pct", C.c_int32),
+                ("min_gaps", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class WordBreaksBlock(C.Structure):
+    """ocr_word_breaks_t."""
+    _fields_ = [("n_source", C.c_int32), ("n_words", C.c_int32), ("source", C.POINTER(C.c_int32)), ("sub_offsets", C.POINTER(C.c_int32)),
+                ("gap_pct", C.POINTER(C.c_int32)), ("source_info", C.POINTER(C.c_int32))]
+
+
+BREAK_MAX_GLYPHS = 256
+BREAK_WORDS = 4   # source words per workgroup of the break kernel (csrc/word_breaks.hip kBreakWaves): word counts around it change the grid
 
 LEX_MAX_LEN = 32
 LEX_MAX_ENTRIES = 1 << 22
@@ -422,6 +438,12 @@ def lib() -> C.CDLL:
                                                 C.POINTER(LexLatParams), C.POINTER(C.POINTER(LexLatMatchesBlock))]
         L.ocr_lexlat_matches_free.argtypes = [C.POINTER(LexLatMatchesBlock)]
         L.ocr_lexlat_matches_free.restype = None
+        L.ocr_break_default_params.argtypes = [C.POINTER(BreakParams)]
+        L.ocr_break_default_params.restype = None
+        L.ocr_break_words.argtypes = [C.c_void_p, C.POINTER(Glyphs), C.POINTER(BreakParams), C.POINTER(C.POINTER(Glyphs)),
+                                      C.POINTER(C.POINTER(WordBreaksBlock))]
+        L.ocr_word_breaks_free.argtypes = [C.POINTER(WordBreaksBlock)]
+        L.ocr_word_breaks_free.restype = None
         L.ocr_rec_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_rec_destroy.argtypes = [C.c_void_p]
         L.ocr_rec_destroy.restype = None
@@ -1289,6 +1311,57 @@ def _as_split_params(params) -> Optional[SplitParams]:
     return split_params(**params)
 
 
+def break_params(**fields) -> BreakParams:
+    """ocr_break_default_params with the given fields overridden (mode, space_pct, min_space_pct, sep_pct, min_gaps, reserved)."""
+    p = BreakParams()
+    lib().ocr_break_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k == "reserved":
+            for i, x in enumerate(v):
+                p.reserved[i] = int(x)
+        elif k in ("mode", "space_pct", "min_space_pct", "sep_pct", "min_gaps"):
+            setattr(p, k, int(v))
+        else:
+            raise TypeError(f"unknown break parameter {k!r}")
+    return p
+
+
+def _as_break_params(params) -> Optional[BreakParams]:
+    if params is None or isinstance(params, BreakParams):
+        return params
+    return break_params(**params)
+
+
+class WordBreaks:
+    """The arrays of an ocr_word_breaks_t, copied into numpy: source [n_words] the source word of every sub-word, sub_offsets
+    [n_source+1] the sub-word range of every source word, gap_pct [n_words] the gap in front of a sub-word in percent of the source
+    word's median glyph height (0 for the first of a source word), source_info n_source x 4 (hw, rule 0 / 1 / 2, threshold in pixels,
+    flags: 2 = more than BREAK_MAX_GLYPHS glyphs, not broken)."""
+
+    def __init__(self, source, sub_offsets, gap_pct, source_info):
+        self.source = np.ascontiguousarray(source, dtype=np.int32)
+        self.sub_offsets = np.ascontiguousarray(sub_offsets, dtype=np.int32)
+        self.gap_pct = np.ascontiguousarray(gap_pct, dtype=np.int32)
+        self.source_info = np.ascontiguousarray(source_info, dtype=np.int32).reshape(-1, 4)
+
+    @property
+    def n_source(self) -> int:
+        return len(self.sub_offsets) - 1
+
+    @property
+    def n_words(self) -> int:
+        return len(self.source)
+
+    @staticmethod
+    def from_block(bp) -> "WordBreaks":
+        b = bp.contents
+
+        def arr(ptr, n):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, np.int32)
+        return WordBreaks(arr(b.source, b.n_words), arr(b.sub_offsets, b.n_source + 1), arr(b.gap_pct, b.n_words),
+                          arr(b.source_info, 4 * b.n_source))
+
+
 def lattice_params(**fields) -> LatticeParams:
     """ocr_lattice_default_params with the given fields overridden (max_span, top_k, span_cost: up to 4 values, reserved)."""
     p = LatticeParams()
@@ -1722,6 +1795,19 @@ class Detector:
     def split_glyphs_device(self, frames_ptr: int, n: int, h: int, w: int, glyphs: GlyphSet, params=None):
         """The same on device-resident frames (a device pointer to N x 1 x H x W f32)."""
         return self._split(C.c_void_p(frames_ptr), n, h, w, MEM_DEVICE, glyphs, params)
+
+    def break_words(self, glyphs: GlyphSet, params=None):
+        """ocr_break_words: the words of `glyphs` (polygons) re-cut at their inter-word gaps.  params: BreakParams, a dict of its fields
+        ({} = the defaults), or None (defaults).  -> (the sub-words as a GlyphSet over the same boxes, the WordBreaks map)."""
+        blk = glyphs.block()
+        prm = _as_break_params(params)
+        out, wb = C.POINTER(Glyphs)(), C.POINTER(WordBreaksBlock)()
+        check(lib().ocr_break_words(self._h, C.byref(blk), C.byref(prm) if prm is not None else None, C.byref(out), C.byref(wb)))
+        try:
+            return GlyphSet.from_block(out), WordBreaks.from_block(wb)
+        finally:
+            lib().ocr_glyphs_free(out)
+            lib().ocr_word_breaks_free(wb)
 
     def _segment_labelled(self, frames_ptr, n: int, h: int, w: int, mem_kind: int, polys, adjust_values, params, cc):
         st, keep = python_to_polygons(polys, [[0.0] * len(p) for p in polys]) if not isinstance(polys, Polygons) else (polys, None)

@@ -19,7 +19,7 @@
 // buffer.  glyph_crop_masked_kernel (ocr_extract_glyph_crops_masked) is the same sampling with a tap that first asks the word's label
 // plane (glyph_cc.hip) whose ink the pixel is: a kerned neighbour's ink inside the glyph's box reads as background.
 // Out of scope of the rule: touching or kerned glyphs (they stay one glyph), rotated or curved words (the word box is axis-aligned and
-// pixels are not masked by the polygon), lexicons, spaces inside a polygon.
+// pixels are not masked by the polygon), lexicons.  Spaces inside a polygon are word_breaks.hip's, on the block this rule returns.
 #include "common.hpp"
 #include "glyph_levels.hpp"
 

@@ -13,6 +13,7 @@
 //   split_glyphs / glyph_spans / lattice_decode: wide glyphs cut into pieces, runs of pieces recognised, segmentation and classes
 //     chosen together under the model (ocr_split_glyphs, ocr_glyph_spans, ocr_lattice_decode)
 //   lexicon_lattice_match: the entries of a Lexicon matched over the pieces, a character reading a run of pieces (ocr_lexicon_lattice_match)
+//   break_words / read_words(.., spaces): a polygon that holds several words cut at its inter-word gaps (ocr_break_words)
 //   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words,
 //     or through curved strips (ocr_plan_curved_strips / ocr_extract_curved_strips), for words that bend
 //   group_lines / read_lines: the words of every page grouped into text lines in reading order (ocr_group_lines), the "output text" step
@@ -158,11 +159,39 @@ class Net {
 
 // One detected word read glyph by glyph: its text (VALUES), the probability of every character, the glyph boxes (x0, y0, x1, y1
 // frame pixels, half-open).
+// With the `spaces` option the text carries one space in front of every inner word of the polygon, starts holds the sub-word ranges
+// inside the polygon's glyphs (S + 1 values) and gap_pct the gap in front of every sub-word (S values, 0 first); both stay empty without it.
 struct WordReading {
   std::string text;
   std::vector<double> probs;
   std::vector<std::array<int32_t, 4>> boxes;
+  std::vector<int32_t> starts, gap_pct;
 };
+// ocr_break_words for the readers: per word of `g` its sub-word range (sub_offsets), per sub-word its first glyph (starts, batch
+// glyph indices, n_glyphs appended) and the gap in front of it.
+struct WordSpaces {
+  std::vector<int32_t> sub_offsets, starts, gap_pct;
+  // word k of the block the breaks were made of -> (starts relative to the word's first glyph, gap_pct)
+  void of_word(int k, int32_t g0, std::vector<int32_t>& rel, std::vector<int32_t>& pct) const {
+    for (int s = sub_offsets[k]; s <= sub_offsets[k + 1]; ++s) rel.push_back(starts[s] - g0);
+    pct.assign(gap_pct.begin() + sub_offsets[k], gap_pct.begin() + sub_offsets[k + 1]);
+  }
+  bool starts_inside(int k, int32_t glyph) const {   // does an inner sub-word of word k start at this glyph?
+    return std::binary_search(starts.begin() + sub_offsets[k] + 1, starts.begin() + sub_offsets[k + 1], glyph);
+  }
+};
+inline WordSpaces word_spaces(const text_detection::FuncT& det_net, const ocr_glyphs_t* g, const ocr_break_params_t* spaces) {
+  ocr_glyphs_t* words = nullptr;
+  ocr_word_breaks_t* wb = nullptr;
+  check(ocr_break_words(det_net.handle(), g, spaces, &words, &wb));
+  WordSpaces out;
+  out.sub_offsets.assign(wb->sub_offsets, wb->sub_offsets + wb->n_source + 1);
+  out.starts.assign(words->word_offsets, words->word_offsets + words->n_words + 1);
+  out.gap_pct.assign(wb->gap_pct, wb->gap_pct + wb->n_words);
+  ocr_glyphs_free(words);
+  ocr_word_breaks_free(wb);
+  return out;
+}
 // The two glyph calls of both readers over host memory: the column rule (cc == nullptr), connected components (cc), or connected
 // components with every crop masked by its glyph's components (cc and mask: ocr_segment_glyphs_cc_labelled ->
 // ocr_extract_glyph_crops_masked; the label planes live on the GPU between the two calls).  mask without cc is OCR_ERR_INVALID.
@@ -197,7 +226,8 @@ inline std::vector<std::vector<WordReading>> read_words(const text_detection::Fu
                                                         const std::vector<double>& adjust_values,
                                                         const ocr_segment_params_t* params = nullptr,
                                                         const ocr_cc_params_t* cc = nullptr,
-                                                        const ocr_mask_params_t* mask = nullptr) {
+                                                        const ocr_mask_params_t* mask = nullptr,
+                                                        const ocr_break_params_t* spaces = nullptr) {
   if (frames.c != 1) throw Error(OCR_ERR_INVALID, "expected N x 1 x H x W");
   if ((int)ps.polygons.size() != frames.n || (int)adjust_values.size() != 2 * frames.n)
     throw Error(OCR_ERR_INVALID, "polygons / adjust_values do not match the frames");
@@ -230,11 +260,15 @@ inline std::vector<std::vector<WordReading>> read_words(const text_detection::Fu
   if (ng > 0) {
     check(ocr_rec_classify(rec_net.handle(), crops.data(), ng, labels.data(), probs.data(), OCR_MEM_HOST));
   }
+  WordSpaces sp;
+  if (spaces) sp = word_spaces(det_net, g, spaces);
   std::vector<std::vector<WordReading>> out(frames.n);
   for (int b = 0; b < frames.n; ++b) {
     for (int k = g->img_offsets[b]; k < g->img_offsets[b + 1]; ++k) {
       WordReading r;
+      if (spaces) sp.of_word(k, g->word_offsets[k], r.starts, r.gap_pct);
       for (int j = g->word_offsets[k]; j < g->word_offsets[k + 1]; ++j) {
+        if (spaces && sp.starts_inside(k, j)) r.text.push_back(' ');
         r.text.push_back(utils::VALUES()[labels[j]]);
         r.probs.push_back(probs[j]);
         r.boxes.push_back({g->boxes[4 * j], g->boxes[4 * j + 1], g->boxes[4 * j + 2], g->boxes[4 * j + 3]});
@@ -428,6 +462,28 @@ struct GlyphBlock {
   ~GlyphBlock() { ocr_glyphs_free(g); }
   const ocr_glyphs_t* get() const { return g; }
 };
+// ocr_break_words: the words of `glyphs` (polygons) re-cut at their inter-word gaps.  words is an ordinary glyph block over the same
+// boxes (every crop, split, span and decode call takes it); source names the polygon of every sub-word, sub_offsets the sub-word range
+// of every polygon, gap_pct the gap in front of every sub-word, source_info per polygon hw, rule, threshold, flags.
+struct WordBreaks {
+  GlyphBlock words;
+  std::vector<int32_t> source, sub_offsets, gap_pct;
+  std::vector<std::array<int32_t, 4>> source_info;
+};
+inline WordBreaks break_words(const text_detection::FuncT& det_net, const ocr_glyphs_t* glyphs, const ocr_break_params_t* params = nullptr) {
+  ocr_glyphs_t* w = nullptr;
+  ocr_word_breaks_t* b = nullptr;
+  check(ocr_break_words(det_net.handle(), glyphs, params, &w, &b));
+  WordBreaks out;
+  out.words = GlyphBlock(w);
+  out.source.assign(b->source, b->source + b->n_words);
+  out.sub_offsets.assign(b->sub_offsets, b->sub_offsets + b->n_source + 1);
+  out.gap_pct.assign(b->gap_pct, b->gap_pct + b->n_words);
+  for (int32_t k = 0; k < b->n_source; ++k)
+    out.source_info.push_back({b->source_info[4 * k], b->source_info[4 * k + 1], b->source_info[4 * k + 2], b->source_info[4 * k + 3]});
+  ocr_word_breaks_free(b);
+  return out;
+}
 // wide glyphs of `glyphs` cut at ink minima; piece_map (optional) receives per piece (source glyph, rank in it)
 inline GlyphBlock split_glyphs(const text_detection::FuncT& det_net, const Tensor& frames, const ocr_glyphs_t* glyphs,
                                const ocr_split_params_t* params = nullptr, std::vector<std::array<int32_t, 2>>* piece_map = nullptr) {
@@ -533,10 +589,12 @@ inline LexLatMatches lexicon_lattice_match(const char_recognition::Net& rec_net,
 
 // One detected word read through its upright strip: text, the probability of every character, and every glyph box mapped back to the
 // frame as a quad (x0, y0), (x1, y0), (x1, y1), (x0, y1) of strip pixels -> TL + cs * (U / Ws) + rs * (V / Hs), f64 frame coordinates.
+// starts and gap_pct as in WordReading: filled by the `spaces` option, measured on the strip.
 struct WordReadingRectified {
   std::string text;
   std::vector<double> probs;
   std::vector<std::array<double, 8>> quads;
+  std::vector<int32_t> starts, gap_pct;
 };
 // ocr_plan_word_strips -> ocr_extract_word_strips -> ocr_word_strip_polygons -> ocr_segment_glyphs -> ocr_extract_glyph_crops ->
 // ocr_rec_classify over host memory (the atlas is one frame of the glyph calls, adj = (1, 1)); per image, per polygon of `ps`.
@@ -547,7 +605,8 @@ inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
     const text_detection::FuncT& det_net, const char_recognition::Net& rec_net, const Tensor& frames,
     const text_detection::metrics::PolygonScores& ps, const std::vector<double>& adjust_values,
     const ocr_strip_params_t* strip_params = nullptr, const ocr_segment_params_t* params = nullptr,
-    const ocr_cc_params_t* cc = nullptr, const ocr_mask_params_t* mask = nullptr, const ocr_curve_params_t* curved = nullptr) {
+    const ocr_cc_params_t* cc = nullptr, const ocr_mask_params_t* mask = nullptr, const ocr_curve_params_t* curved = nullptr,
+    const ocr_break_params_t* spaces = nullptr) {
   if (frames.c != 1) throw Error(OCR_ERR_INVALID, "expected N x 1 x H x W");
   if ((int)ps.polygons.size() != frames.n || (int)adjust_values.size() != 2 * frames.n)
     throw Error(OCR_ERR_INVALID, "polygons / adjust_values do not match the frames");
@@ -613,6 +672,8 @@ inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
   if (ng > 0) {
     check(ocr_rec_classify(rec_net.handle(), crops.data(), ng, labels.data(), probs.data(), OCR_MEM_HOST));
   }
+  WordSpaces sp;
+  if (spaces) sp = word_spaces(det_net, g, spaces);
   for (int b = 0; b < frames.n; ++b) {
     for (int k = st_img[b]; k < st_img[b + 1]; ++k) {
       const double c0 = st_col[k], ws = st_col[k + 1] - st_col[k];
@@ -621,7 +682,9 @@ inline std::vector<std::vector<WordReadingRectified>> read_words_rectified(
       const double rvx = curved ? 0 : (q[6] - q[0]) / hs, rvy = curved ? 0 : (q[7] - q[1]) / hs;
       const float* kn = curved ? cst->knots + 4 * OCR_CURVE_KNOTS * (size_t)k : nullptr;
       WordReadingRectified r;
+      if (spaces) sp.of_word(k, g->word_offsets[k], r.starts, r.gap_pct);
       for (int j = g->word_offsets[k]; j < g->word_offsets[k + 1]; ++j) {
+        if (spaces && sp.starts_inside(k, j)) r.text.push_back(' ');
         r.text.push_back(utils::VALUES()[labels[j]]);
         r.probs.push_back(probs[j]);
         const int32_t* bx = g->boxes + 4 * (size_t)j;

@@ -40,10 +40,14 @@ recognition -> output text), composed over the C ABI.
         ocr_lattice_decode        every word -> its k cheapest (segmentation, classes) pairs (csrc/lattice.hip)
     ... and with lattice_lexicon=capi.Lexicon the word list is searched over the same pieces:
         ocr_lexicon_lattice_match every word's pieces against every entry, a character reading a run of pieces (csrc/lexicon_lattice.hip)
+    read_words(..., spaces={}) and read_words_rectified(..., spaces={}) cut a polygon that holds several words at its inter-word gaps,
+    between the crops and the classify call; the lexicon and the model then see every word on its own:
+        ocr_break_words           the words of a glyph block -> the words inside them      (csrc/word_breaks.hip)
 
 The segmentation, strip and line rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
 tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py, tests/strip_oracle.py, tests/curved_strip_oracle.py and
-tests/line_oracle.py; the lexicon rule likewise, restated in tests/lexicon_oracle.py, and the language model's in tests/char_lm_oracle.py.
+tests/line_oracle.py; the lexicon rule likewise, restated in tests/lexicon_oracle.py, the language model's in tests/char_lm_oracle.py
+and the word-break rule in tests/word_break_oracle.py.
 """
 from __future__ import annotations
 
@@ -163,6 +167,18 @@ def _word(text: str, probs, where, k: int, n_glyphs: int, matches, lexicon, max_
     return (out, probs, where, *extra)
 
 
+def _spaced_word(text: str, probs, where, k: int, g0: int, sub, breaks, matches, lexicon, max_penalty: float, paths=None):
+    """The tuple of polygon k read with spaces=: its sub-words (the words of `sub`, an ocr_break_words block; `breaks` maps them to the
+    polygons) each go through _word, the texts are joined by one space, the lexicon and model elements become lists with one entry per
+    sub-word, and (starts, gap_pct) is appended: starts int32 [S+1], the sub-word ranges inside the polygon's glyphs, gap_pct int32 [S]."""
+    s0, s1 = int(breaks.sub_offsets[k]), int(breaks.sub_offsets[k + 1])
+    off = sub.word_offsets[s0:s1 + 1] - np.int32(g0)     # (int32 - int32: a new int32 array)
+    o = off.tolist()
+    parts = [_word(text[o[i]:o[i + 1]], None, None, s0 + i, o[i + 1] - o[i], matches, lexicon, max_penalty, paths) for i in range(s1 - s0)]
+    extras = [list(e) for e in zip(*[p[3:] for p in parts])]
+    return (" ".join(p[0] for p in parts), probs, where, *extras, (off, breaks.gap_pct[s0:s1].copy()))
+
+
 def _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params, cc, lm, lattice, split, lattice_lexicon=None,
                         lattice_lexicon_params=None, max_penalty=1.5):
     """segment -> split -> spans -> crops -> classify + costs -> decode, everything between the calls on the device; per word
@@ -231,7 +247,7 @@ def _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params,
 
 def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None, cc=None, mask=None, lexicon=None,
                lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None, lattice=None,
-               split=None, lattice_lexicon=None, lattice_lexicon_params=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+               split=None, lattice_lexicon=None, lattice_lexicon_params=None, spaces=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch.
 
     det_net: text_detection.FuncT or capi.Detector (supplies the GPU and stream of the segmentation); rec_net: char_recognition.Net
@@ -266,7 +282,15 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     cost - raw_cost <= max_penalty * G for its G pieces (f64); its probs and where then follow the match's segments (an inserted
     character has none, and neither has a deleted piece).  Every tuple gains (entry index or -1, cost, raw_cost, seg_len) as its last
     element, seg_len being the match's per piece: m at the first piece of a segment, 0 inside it, -1 at a deleted piece.  With
-    lattice_lexicon=None nothing changes."""
+    lattice_lexicon=None nothing changes.
+    spaces: None, or capi.BreakParams, a dict of its fields or {} for the defaults: a polygon that holds several words is cut at its
+    inter-word gaps (ocr_break_words) between the crops and the classify call.  Segmentation and crops run on the polygons (masked
+    crops keep working: the labels are per polygon); lexicon= and lm= then match and decode every sub-word on its own.  The text of a
+    polygon is its sub-word texts joined by one space, probs and where stay per glyph, the lexicon's and the model's elements become
+    lists with one entry per sub-word, and the tuple gains (starts, gap_pct) as its last element: starts int32 [S+1], the sub-word
+    ranges inside the polygon's glyphs, and gap_pct int32 [S], the gap in front of every sub-word in percent of the polygon's median
+    glyph height (0 for the first).  lattice= with spaces= raises OcrError: the composition is not built.  With spaces=None nothing
+    changes."""
     import torch
 
     det = _handle(det_net, capi.Detector)
@@ -286,6 +310,8 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     # the library's calls run on their handles' streams: whatever torch queued to produce x is finished first
     torch.cuda.current_stream(dev).synchronize()
     if lattice is not None:
+        if spaces is not None:
+            raise capi.OcrError(1, "lattice: the composition with spaces= is not built (break the words, then call the lattice calls on the block)")
         if _masked(mask, cc):
             raise capi.OcrError(1, "lattice: masked crops are not built for pieces (labels do not map to them)")
         if lexicon is not None:
@@ -296,14 +322,19 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
         raise capi.OcrError(1, "lattice_lexicon: the joint search needs lattice= ({} for its defaults)")
     glyphs, crops = _segment_and_crop(det, x.data_ptr(), n, h, w, polys, adjust_values, params, cc, mask, dev)   # blocking
     ng = glyphs.n_glyphs
-    labels, probs, matches, paths = _classify(rec, crops, ng, dev, glyphs.word_offsets, lexicon, lexicon_params, lm, lm_params)
+    sub, breaks = det.break_words(glyphs, spaces) if spaces is not None else (glyphs, None)
+    labels, probs, matches, paths = _classify(rec, crops, ng, dev, sub.word_offsets, lexicon, lexicon_params, lm, lm_params)
     out = []
     for b in range(n):
         words = []
         for k in range(int(glyphs.img_offsets[b]), int(glyphs.img_offsets[b + 1])):
             g0, g1 = int(glyphs.word_offsets[k]), int(glyphs.word_offsets[k + 1])
-            words.append(_word("".join(VALUES[int(c)] for c in labels[g0:g1]), probs[g0:g1].copy(), glyphs.boxes[g0:g1].copy(), k, g1 - g0,
-                               matches, lexicon, max_penalty, paths))
+            text = "".join(VALUES[int(c)] for c in labels[g0:g1])
+            if breaks is None:
+                words.append(_word(text, probs[g0:g1].copy(), glyphs.boxes[g0:g1].copy(), k, g1 - g0, matches, lexicon, max_penalty, paths))
+            else:
+                words.append(_spaced_word(text, probs[g0:g1].copy(), glyphs.boxes[g0:g1].copy(), k, g0, sub, breaks, matches, lexicon,
+                                          max_penalty, paths))
         out.append(words)
     return out
 
@@ -373,7 +404,7 @@ def _curved(curved, strip_params):
 
 
 def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None, cc=None, mask=None,
-                         curved=None, lexicon=None, lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+                         curved=None, lexicon=None, lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None, spaces=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch through its upright strip: rotated words are read along their own axis, and with
     curved=True (or {} or a dict of capi.CurveParams' fields: strip_height, max_width, valid_pct) words that bend are read along their
     own centreline (ocr_plan_curved_strips, ocr_extract_curved_strips; the glyph quads then come from curved_glyph_quads).  curved=None
@@ -382,7 +413,8 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     Arguments as read_words; strip_params: capi.StripParams, a dict of its fields (strip_height, max_width) or None for the defaults;
     params, cc and mask: the segmentation parameters, rule and crop masking as in read_words, applied to the atlas.  Returns per image, per polygon: (text, probability of every character
     (f64), glyph quads k x 4 x 2 f64: the corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of every glyph box mapped back to frame
-    coordinates, strip_glyph_quads).  A flat word reads as "".  lexicon, lexicon_params, max_penalty, lm and lm_params as in read_words."""
+    coordinates, strip_glyph_quads).  A flat word reads as "".  lexicon, lexicon_params, max_penalty, lm and lm_params as in read_words; spaces likewise, applied to the atlas' glyph block (a strip is upright, so the
+    gaps are measured along the word's own axis)."""
     import torch
 
     det = _handle(det_net, capi.Detector)
@@ -408,7 +440,8 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     with strips.polygon_block() as rects:
         glyphs, crops = _segment_and_crop(det, atlas.data_ptr(), 1, hs, tw, rects, [[1.0, 1.0]], params, cc, mask, dev)
     ng = glyphs.n_glyphs
-    labels, probs, matches, paths = _classify(rec, crops, ng, dev, glyphs.word_offsets, lexicon, lexicon_params, lm, lm_params)
+    sub, breaks = det.break_words(glyphs, spaces) if spaces is not None else (glyphs, None)
+    labels, probs, matches, paths = _classify(rec, crops, ng, dev, sub.word_offsets, lexicon, lexicon_params, lm, lm_params)
     quads = (strip_glyph_quads if cp is None else curved_glyph_quads)(
         strips, np.repeat(np.arange(glyphs.n_words), np.diff(glyphs.word_offsets)), glyphs.boxes)
     text = "".join(VALUES[int(c)] for c in labels)
@@ -417,7 +450,11 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
         words = []
         for k in range(int(strips.img_offsets[b]), int(strips.img_offsets[b + 1])):
             g0, g1 = int(glyphs.word_offsets[k]), int(glyphs.word_offsets[k + 1])
-            words.append(_word(text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy(), k, g1 - g0, matches, lexicon, max_penalty, paths))
+            if breaks is None:
+                words.append(_word(text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy(), k, g1 - g0, matches, lexicon, max_penalty, paths))
+            else:
+                words.append(_spaced_word(text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy(), k, g0, sub, breaks, matches, lexicon,
+                                          max_penalty, paths))
         out.append(words)
     return out
 
@@ -442,7 +479,7 @@ def read_lines(det_net, rec_net, frames, polygon_scores, adjust_values, line_par
     """Reads every detected word of a batch and groups the words of every image into text lines in reading order (ocr_group_lines).
 
     Arguments as read_words_rectified (rectified=True, the default) or read_words (rectified=False); strip_params, params, cc, mask and
-    curved go to that call unchanged, and so do lexicon, lexicon_params, max_penalty, lm and lm_params (the lines then join the matched or decoded texts).  line_params: capi.LineParams, a dict of its fields (line_tol, height_ratio, min_cos, max_gap) or
+    curved go to that call unchanged, and so do lexicon, lexicon_params, max_penalty, lm and lm_params (the lines then join the matched or decoded texts) and spaces (a polygon's text then carries its inner spaces, in place).  line_params: capi.LineParams, a dict of its fields (line_tol, height_ratio, min_cos, max_gap) or
     None for the defaults.  The quads always come from ocr_plan_word_strips (with strip_params where given): word order equals polygon
     order in every reading call, and the curved plan carries no quads.
     Returns per image a list of lines (text, word_indices, gaps): word_indices are the image's polygon indices in reading order (int32),
