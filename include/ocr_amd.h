@@ -1159,7 +1159,7 @@ void ocr_lexlat_matches_free(ocr_lexlat_matches_t* m);
  * outside 0..2^22, a parameter out of range or a nonzero reserved field; the handle stays usable.  A block without glyphs launches
  * nothing and returns valid blocks.
  * Out of scope: one threshold per polygon with no line-level context, so a single letter-spaced word whose gaps are all equal and
- * wide breaks at every letter; phrases in the lexicon.
+ * wide breaks at every letter (ocr_lexicon_phrase_match below puts such a word back together from the lexicon).
  * Oracle: tests/word_break_oracle.py; kernel: csrc/word_breaks.hip (one wave per source word, glyph i in lane i % 64, slot i / 64;
  * both sorts by rank counting over an LDS copy of the wave's keys). */
 #define OCR_BREAK_MAX_GLYPHS 256
@@ -1183,6 +1183,74 @@ void ocr_break_default_params(ocr_break_params_t* p);
 int  ocr_break_words(ocr_det_t* det, const ocr_glyphs_t* glyphs, const ocr_break_params_t* params,
                      ocr_glyphs_t** words, ocr_word_breaks_t** breaks);
 void ocr_word_breaks_free(ocr_word_breaks_t* b);
+
+/* EXTENSION - phrase search: the glyphs of a line segmented into lexicon words (BUILD-DEFINED, like the rules above; the reference
+ * has no counterpart).  ocr_break_words cuts a polygon from its gaps alone, before any character is looked at, and an entry of
+ * ocr_lexicon_match reads one sub-word.  ocr_lexicon_phrase_match is dictionary word segmentation: one DP over the glyphs of a line
+ * picks the word boundaries and the lexicon entries together, gap evidence enters as a soft cost per glyph, and an out-of-vocabulary
+ * word costs something without making the line unreadable.
+ * costs n_glyphs x 62 f32 in mem_kind memory (ocr_rec_glyph_costs), line_offsets [n_lines+1] in host memory: line l owns the glyph
+ * rows [line_offsets[l], line_offsets[l+1]).  bound_cost and join_cost [n_glyphs] f32 in host memory, or both NULL for zeros:
+ * bound_cost[r] is paid when a word starts at glyph row r inside a line, join_cost[r] when r continues the word of the row before it
+ * (capi.phrase_gap_costs derives both from the result of ocr_break_words).
+ * Rule.  All arithmetic is f64 on the f32 values widened, every operation rounded separately, adds and mins only.  Line l has the glyph
+ * rows r_0..r_(G-1), 1 <= G <= OCR_PHRASE_MAX_GLYPHS.
+ *   s(i, c) is ocr_lexicon_match's: (double)cost[r_i][c], with fold_case = 1 the min of that and the same for the other-case twin.
+ *   raw(i) = min over c of (double)cost[r_i][c].
+ *   W(i, e), entry e with classes c_0..c_(M-1) at start i, i + M <= G: start at 0.0 and add s(i+k, c_k) in k order.  No insertions or
+ *     deletions inside the phrase search.
+ *   L(i, M) = the minimum of W(i, e) over the entries of length M by (value, entry index) ascending; +inf / -1 without such an entry.
+ *   U(i, M), an out-of-vocabulary word: start at oov_word_cost; for k = 0..M-1 add raw(i+k), then add oov_glyph_cost.
+ *   J(i, M), the interior joins: start at 0.0 and add (double)join_cost[r_(i+k)] for k = 1..M-1 in order.
+ *   T(i, M, 0) = (L(i, M) + word_cost) + J(i, M);  T(i, M, 1) = U(i, M) + J(i, M);  1 <= M <= min(OCR_LEX_MAX_LEN, G - i).
+ *   B[0] = 0.0.  For j = 1..G the candidates (M, kind) have v = (B[j-M] + bnd(j-M)) + T(j-M, M, kind), bnd(0) = 0.0 and
+ *     bnd(i) = (double)bound_cost[r_i] for i > 0; B[j] is the minimum by (v, kind, M) ascending: on a tie the lexicon comes before
+ *     out-of-vocabulary, then the shorter word.  An infinite v never wins; U is finite, so there is always a finite candidate.
+ *   The words of the line are read back from G along the chosen (M, kind) and come out in glyph order, with the entry of L for kind 0.
+ * The key is a total order, so the result does not depend on how a kernel chunks the lexicon or the line.
+ * Output: line_word_offsets [n_lines+1] the word range of every line (at least one word each), word_offsets [n_words+1] the glyph rows
+ * of every word - an ordinary offset array, a tiling of all glyph rows, that ocr_lm_decode and ocr_lexicon_match take -, entries
+ * [n_words] (the caller's index, -1 for an out-of-vocabulary word), word_costs [n_words] the T of the chosen segment, line_costs
+ * [n_lines] B[G], raw_costs [n_lines] the greedy sum exactly as ocr_lexicon_match's raw_costs, line_flags [n_lines].
+ * Flagged lines keep the tiling: G = 0 gives one word without glyphs, entry -1, word cost 0.0, line cost 0.0, flag 1; G >
+ * OCR_PHRASE_MAX_GLYPHS gives one word holding every glyph, entry -1, both costs +inf, flag 2.
+ * OCR_ERR_INVALID for a null pointer (params == NULL -> the defaults; costs may be NULL when n_glyphs = 0), a bad mem_kind, offsets
+ * that do not start at 0, decrease or do not end at n_glyphs, a parameter out of range or a nonzero reserved field, a lexicon of
+ * another device, exactly one of bound_cost / join_cost NULL, a value in them that is NaN, +-inf or negative, and a glyph cost that is
+ * NaN, +-inf or negative (found on the device in the same pass; the message names the first such line).  The handle stays usable.
+ * n_lines = 0 launches nothing and returns an empty block.  The call runs on the recogniser's stream behind what is queued there, and
+ * blocks.  Lines are processed in groups of at most 2 048 windows of 32 starts, so the call's workspace beyond the copies of its own
+ * arguments and results (costs 248 B, gap costs and results 40 B a glyph) stays under 96 MiB whatever the batch and the lexicon: 48 MiB of
+ * per-chunk minima (at most 64 chunks) and 40 MiB of segment costs and entries.
+ * Out of scope: insertions or deletions inside a phrase word (ocr_lexicon_match's edit distance reads one word); k-best phrases (one
+ * best segmentation); a model transition across words; lattice pieces; lines of more than OCR_PHRASE_MAX_GLYPHS glyphs (flagged).
+ * Oracle: tests/phrase_oracle.py; kernels: csrc/lexicon_phrase.hip (the match: grid over window of 32 starts x lexicon chunk of one
+ * length, the window's cost rows in LDS, one entry per lane with 32 accumulators, butterflies by (cost, index); the segment costs: one
+ * thread per (start, length); the DP: one wave per line, lane = kind * 32 + (M - 1)). */
+#define OCR_PHRASE_MAX_GLYPHS 256     /* glyphs per line; OCR_BREAK_MAX_GLYPHS */
+typedef struct ocr_phrase_params {
+  double  word_cost;       /* >= 0 finite, default 1.0: paid once per lexicon word (keeps "int he box" behind "in the box") */
+  double  oov_word_cost;   /* >= 0 finite, default 6.0: paid once per out-of-vocabulary word   */
+  double  oov_glyph_cost;  /* >= 0 finite, default 1.0: paid per glyph of such a word           */
+  int32_t fold_case;       /* 0 | 1, default 1: s(i, c) exactly as in ocr_lexicon_match         */
+  int32_t reserved[3];     /* must be 0 */
+} ocr_phrase_params_t;
+typedef struct ocr_phrase_matches {
+  int32_t n_lines, n_words, n_glyphs;
+  const int32_t* line_word_offsets; /* [n_lines+1] word range of every line (>= 1 word each)             */
+  const int32_t* word_offsets;      /* [n_words+1] glyph rows of every word: an ordinary offset array     */
+  const int32_t* entries;           /* [n_words] caller's entry index, -1 for an out-of-vocabulary word   */
+  const double*  word_costs;        /* [n_words] T of the chosen segment                                  */
+  const double*  line_costs;        /* [n_lines] B[G]                                                     */
+  const double*  raw_costs;         /* [n_lines] the greedy sum, as ocr_lexicon_match's raw_costs         */
+  const int32_t* line_flags;        /* [n_lines] 1 no glyphs, 2 more than OCR_PHRASE_MAX_GLYPHS           */
+} ocr_phrase_matches_t;
+void ocr_phrase_default_params(ocr_phrase_params_t* p);
+/* *out: ocr_phrase_matches_free. */
+int  ocr_lexicon_phrase_match(ocr_rec_t* rec, const ocr_lexicon_t* lex, const float* costs, int n_glyphs, int mem_kind,
+                              const int32_t* line_offsets, int n_lines, const float* bound_cost, const float* join_cost,
+                              const ocr_phrase_params_t* params, ocr_phrase_matches_t** out);
+void ocr_phrase_matches_free(ocr_phrase_matches_t* m);
 
 /* ---------------------------------------------------------------------------
  * Multi-GPU exchange.  Frames and crops are independent (eval-mode batch norm), so a batch shards over the GPUs of

@@ -46,6 +46,7 @@ EXPORTS = [
     "ocr_lattice_default_params", "ocr_lattice_decode", "ocr_lattice_paths_free",
     "ocr_lexlat_default_params", "ocr_lexicon_lattice_match", "ocr_lexlat_matches_free",
     "ocr_break_default_params", "ocr_break_words", "ocr_word_breaks_free",
+    "ocr_phrase_default_params", "ocr_lexicon_phrase_match", "ocr_phrase_matches_free",
     "ocr_ctc_beam_decode",
     "ocr_comm_unique_id", "ocr_comm_rccl_version", "ocr_comm_create", "ocr_comm_destroy",
     "ocr_comm_all_gather_polygons", "ocr_comm_all_gather_labels",
@@ -238,6 +239,22 @@ class WordBreaksBlock(C.Structure):
                 ("gap_pct", C.POINTER(C.c_int32)), ("source_info", C.POINTER(C.c_int32))]
 
 
+class PhraseParams(C.Structure):
+    """ocr_phrase_params_t."""
+    _fields_ = [("word_cost", C.c_double), ("oov_word_cost", C.c_double), ("oov_glyph_cost", C.c_double), ("fold_case", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class PhraseMatchesBlock(C.Structure):
+    """ocr_phrase_matches_t."""
+    _fields_ = [("n_lines", C.c_int32), ("n_words", C.c_int32), ("n_glyphs", C.c_int32), ("line_word_offsets", C.POINTER(C.c_int32)),
+                ("word_offsets", C.POINTER(C.c_int32)), ("entries", C.POINTER(C.c_int32)), ("word_costs", C.POINTER(C.c_double)),
+                ("line_costs", C.POINTER(C.c_double)), ("raw_costs", C.POINTER(C.c_double)), ("line_flags", C.POINTER(C.c_int32))]
+
+
+PHRASE_MAX_GLYPHS = 256
+PHRASE_STARTS = 32           # starts per window of the phrase match kernel (csrc/lexicon_phrase.hip kPhraseStarts)
+PHRASE_GROUP_WINDOWS = 2048  # windows per group of lines (kPhraseGroupWindows): batches around it take another launch sequence
 BREAK_MAX_GLYPHS = 256
 BREAK_WORDS = 4   # source words per workgroup of the break kernel (csrc/word_breaks.hip kBreakWaves): word counts around it change the grid
 
@@ -444,6 +461,12 @@ def lib() -> C.CDLL:
                                       C.POINTER(C.POINTER(WordBreaksBlock))]
         L.ocr_word_breaks_free.argtypes = [C.POINTER(WordBreaksBlock)]
         L.ocr_word_breaks_free.restype = None
+        L.ocr_phrase_default_params.argtypes = [C.POINTER(PhraseParams)]
+        L.ocr_phrase_default_params.restype = None
+        L.ocr_lexicon_phrase_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.POINTER(PhraseParams), C.POINTER(C.POINTER(PhraseMatchesBlock))]
+        L.ocr_phrase_matches_free.argtypes = [C.POINTER(PhraseMatchesBlock)]
+        L.ocr_phrase_matches_free.restype = None
         L.ocr_rec_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
         L.ocr_rec_destroy.argtypes = [C.c_void_p]
         L.ocr_rec_destroy.restype = None
@@ -1128,6 +1151,83 @@ class LexiconMatches:
             return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
         return LexiconMatches(arr(s.entries, nw * k, np.int32).reshape(nw, k), arr(s.costs, nw * k, np.float64).reshape(nw, k),
                               arr(s.raw_costs, nw, np.float64), arr(s.n_candidates, nw, np.int32), arr(s.word_flags, nw, np.int32))
+
+
+def phrase_params(**fields) -> PhraseParams:
+    """ocr_phrase_default_params with the given fields overridden (word_cost, oov_word_cost, oov_glyph_cost, fold_case, reserved)."""
+    p = PhraseParams()
+    lib().ocr_phrase_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k == "reserved":
+            p.reserved[0], p.reserved[1], p.reserved[2] = (int(x) for x in v)
+        elif k in ("word_cost", "oov_word_cost", "oov_glyph_cost"):
+            setattr(p, k, float(v))
+        elif k == "fold_case":
+            p.fold_case = int(v)
+        else:
+            raise TypeError(f"unknown phrase parameter {k!r}")
+    return p
+
+
+def _as_phrase_params(params) -> Optional[PhraseParams]:
+    if params is None or isinstance(params, PhraseParams):
+        return params
+    return phrase_params(**params)
+
+
+class PhraseMatches:
+    """The arrays of an ocr_phrase_matches_t, copied into numpy: line_word_offsets [n_lines+1] the word range of every line,
+    word_offsets [n_words+1] the glyph rows of every word (an ordinary offset array: lm_decode and lexicon_match take it), entries
+    [n_words] int32 (the caller's entry index, -1 for an out-of-vocabulary word), word_costs [n_words] f64, line_costs and raw_costs
+    [n_lines] f64, line_flags [n_lines] (1 no glyphs, 2 more than PHRASE_MAX_GLYPHS glyphs)."""
+
+    def __init__(self, line_word_offsets, word_offsets, entries, word_costs, line_costs, raw_costs, line_flags):
+        self.line_word_offsets = np.ascontiguousarray(line_word_offsets, dtype=np.int32)
+        self.word_offsets = np.ascontiguousarray(word_offsets, dtype=np.int32)
+        self.entries = np.ascontiguousarray(entries, dtype=np.int32)
+        self.word_costs = np.ascontiguousarray(word_costs, dtype=np.float64)
+        self.line_costs = np.ascontiguousarray(line_costs, dtype=np.float64)
+        self.raw_costs = np.ascontiguousarray(raw_costs, dtype=np.float64)
+        self.line_flags = np.ascontiguousarray(line_flags, dtype=np.int32)
+
+    @property
+    def n_lines(self) -> int:
+        return len(self.line_flags)
+
+    @property
+    def n_words(self) -> int:
+        return len(self.entries)
+
+    def line(self, l: int) -> "PhraseMatches":
+        """The rows of line l as a block of one line: word_offsets relative to the line's first glyph."""
+        w0, w1 = int(self.line_word_offsets[l]), int(self.line_word_offsets[l + 1])
+        return PhraseMatches([0, w1 - w0], self.word_offsets[w0:w1 + 1] - self.word_offsets[w0], self.entries[w0:w1],
+                             self.word_costs[w0:w1], self.line_costs[l:l + 1], self.raw_costs[l:l + 1], self.line_flags[l:l + 1])
+
+    @staticmethod
+    def from_block(mp) -> "PhraseMatches":
+        s = mp.contents
+        nl, nw = s.n_lines, s.n_words
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return PhraseMatches(arr(s.line_word_offsets, nl + 1, np.int32), arr(s.word_offsets, nw + 1, np.int32), arr(s.entries, nw, np.int32),
+                             arr(s.word_costs, nw, np.float64), arr(s.line_costs, nl, np.float64), arr(s.raw_costs, nl, np.float64),
+                             arr(s.line_flags, nl, np.int32))
+
+
+def phrase_gap_costs(sub, breaks=None, break_penalty: float = 2.0, join_penalty: float = 2.0):
+    """The gap costs of ocr_lexicon_phrase_match from the result of Detector.break_words (sub: the sub-words' GlyphSet, breaks: its
+    WordBreaks): at a glyph that starts a sub-word the bound costs 0 and the join join_penalty - the gaps say a word starts there -,
+    at every other glyph the bound costs break_penalty and the join 0.  -> (bound_cost, join_cost), f32 [n_glyphs]."""
+    ng = sub.n_glyphs
+    bound = np.full(ng, break_penalty, np.float32)
+    join = np.zeros(ng, np.float32)
+    starts = np.asarray(sub.word_offsets[:-1], np.int64)
+    starts = starts[starts < ng]
+    bound[starts] = 0.0
+    join[starts] = join_penalty
+    return bound, join
 
 
 class Lexicon:
@@ -2492,6 +2592,37 @@ class Recognizer:
 
     def lexicon_match_device(self, lex: "Lexicon", costs_ptr: int, n_glyphs: int, word_offsets, params=None) -> LexiconMatches:
         return self._lexicon_match(lex, C.c_void_p(costs_ptr or None), n_glyphs, MEM_DEVICE, word_offsets, params)
+
+    def _phrase_match(self, lex, costs_ptr, n_glyphs: int, mem_kind: int, line_offsets, bound_cost, join_cost, params) -> PhraseMatches:
+        off = np.ascontiguousarray(line_offsets, dtype=np.int32).reshape(-1)
+        prm = _as_phrase_params(params)
+        bound = None if bound_cost is None else np.ascontiguousarray(bound_cost, dtype=np.float32).reshape(-1)
+        join = None if join_cost is None else np.ascontiguousarray(join_cost, dtype=np.float32).reshape(-1)
+        for name, a in (("bound_cost", bound), ("join_cost", join)):
+            if a is not None and a.size != n_glyphs:
+                raise OcrError(1, f"phrase_match: {name} has {a.size} values for {n_glyphs} glyphs")
+        pad = np.zeros(1, np.float32)   # an array without glyphs still passes a pointer: NULL means "no gap costs"
+        out = C.POINTER(PhraseMatchesBlock)()
+        check(lib().ocr_lexicon_phrase_match(self._h, lex.handle if isinstance(lex, Lexicon) else lex, costs_ptr, n_glyphs, mem_kind,
+                                             _ptr(off) if off.size else None, len(off) - 1,
+                                             None if bound is None else _ptr(bound if bound.size else pad),
+                                             None if join is None else _ptr(join if join.size else pad),
+                                             C.byref(prm) if prm is not None else None, C.byref(out)))
+        try:
+            return PhraseMatches.from_block(out)
+        finally:
+            lib().ocr_phrase_matches_free(out)
+
+    def phrase_match(self, lex: "Lexicon", costs: np.ndarray, line_offsets, bound_cost=None, join_cost=None, params=None) -> PhraseMatches:
+        """ocr_lexicon_phrase_match: costs n_glyphs x 62 f32 in host memory (glyph_costs), line_offsets [n_lines+1] the glyph range of
+        every line (a polygon's glyphs: GlyphSet.word_offsets); bound_cost and join_cost f32 [n_glyphs] (phrase_gap_costs) or both None
+        for zeros; params: PhraseParams, a dict of its fields, or None (defaults).  Blocking, on the handle's stream."""
+        x = np.ascontiguousarray(costs, dtype=np.float32).reshape(-1, 62)
+        return self._phrase_match(lex, _ptr(x) if x.size else None, x.shape[0], MEM_HOST, line_offsets, bound_cost, join_cost, params)
+
+    def phrase_match_device(self, lex: "Lexicon", costs_ptr: int, n_glyphs: int, line_offsets, bound_cost=None, join_cost=None,
+                            params=None) -> PhraseMatches:
+        return self._phrase_match(lex, C.c_void_p(costs_ptr or None), n_glyphs, MEM_DEVICE, line_offsets, bound_cost, join_cost, params)
 
     def _lm_decode(self, lm, costs_ptr, n_glyphs: int, mem_kind: int, word_offsets, params) -> LmPaths:
         off = np.ascontiguousarray(word_offsets, dtype=np.int32).reshape(-1)

@@ -14,6 +14,7 @@
 //     chosen together under the model (ocr_split_glyphs, ocr_glyph_spans, ocr_lattice_decode)
 //   lexicon_lattice_match: the entries of a Lexicon matched over the pieces, a character reading a run of pieces (ocr_lexicon_lattice_match)
 //   break_words / read_words(.., spaces): a polygon that holds several words cut at its inter-word gaps (ocr_break_words)
+//   PhraseParams / phrase_match: the glyphs of a polygon segmented into lexicon words by one search (ocr_lexicon_phrase_match)
 //   read_words_rectified: the same through upright word strips (ocr_plan_word_strips / ocr_extract_word_strips), for rotated words,
 //     or through curved strips (ocr_plan_curved_strips / ocr_extract_curved_strips), for words that bend
 //   group_lines / read_lines: the words of every page grouped into text lines in reading order (ocr_group_lines), the "output text" step
@@ -330,6 +331,48 @@ inline LexiconMatches lexicon_match(const char_recognition::Net& rec_net, const 
   out.n_candidates.assign(m->n_candidates, m->n_candidates + nw);
   out.word_flags.assign(m->word_flags, m->word_flags + nw);
   ocr_lexicon_matches_free(m);
+  return out;
+}
+// ocr_lexicon_phrase_match: the glyphs of every line (a polygon's glyphs) segmented into lexicon words and out-of-vocabulary words by
+// one search over the glyph costs.  PhraseParams starts from ocr_phrase_default_params; bound_cost and join_cost are per glyph (both
+// empty: zeros).  word_offsets is an ordinary offset array over the glyph rows: lm_decode and lexicon_match take it.
+struct PhraseParams : ocr_phrase_params_t {
+  PhraseParams() { ocr_phrase_default_params(this); }
+};
+struct PhraseMatches {
+  std::vector<int32_t> line_word_offsets, word_offsets, entries, line_flags;   // entries: -1 for an out-of-vocabulary word
+  std::vector<double> word_costs, line_costs, raw_costs;
+  // the text of line l: an entry's string for a lexicon word, raw[a, b) (the per-glyph reading of the whole block) for any other
+  std::string text(const Lexicon& lex, const std::string& raw, size_t l) const {
+    std::string out;
+    for (int32_t w = line_word_offsets[l]; w < line_word_offsets[l + 1]; ++w) {
+      if (w > line_word_offsets[l]) out += ' ';
+      out += entries[w] >= 0 ? lex.words()[entries[w]] : raw.substr((size_t)word_offsets[w], (size_t)(word_offsets[w + 1] - word_offsets[w]));
+    }
+    return out;
+  }
+};
+inline PhraseMatches phrase_match(const char_recognition::Net& rec_net, const Lexicon& lex, const std::vector<float>& costs,
+                                  const std::vector<int32_t>& line_offsets, const std::vector<float>& bound_cost = {},
+                                  const std::vector<float>& join_cost = {}, const ocr_phrase_params_t* params = nullptr) {
+  if (line_offsets.empty() || costs.size() != 62 * (size_t)line_offsets.back()) throw Error(OCR_ERR_INVALID, "costs do not match the line offsets");
+  const size_t ng = costs.size() / 62;
+  const bool gaps = !bound_cost.empty() || !join_cost.empty();
+  if (gaps && (bound_cost.size() != ng || join_cost.size() != ng)) throw Error(OCR_ERR_INVALID, "gap costs do not match the glyphs");
+  ocr_phrase_matches_t* m = nullptr;
+  check(ocr_lexicon_phrase_match(rec_net.handle(), lex.handle(), costs.empty() ? nullptr : costs.data(), (int)ng, OCR_MEM_HOST,
+                                 line_offsets.data(), (int)line_offsets.size() - 1, gaps ? bound_cost.data() : nullptr,
+                                 gaps ? join_cost.data() : nullptr, params, &m));
+  PhraseMatches out;
+  const size_t nl = (size_t)m->n_lines, nw = (size_t)m->n_words;
+  out.line_word_offsets.assign(m->line_word_offsets, m->line_word_offsets + nl + 1);
+  out.word_offsets.assign(m->word_offsets, m->word_offsets + nw + 1);
+  out.entries.assign(m->entries, m->entries + nw);
+  out.word_costs.assign(m->word_costs, m->word_costs + nw);
+  out.line_costs.assign(m->line_costs, m->line_costs + nl);
+  out.raw_costs.assign(m->raw_costs, m->raw_costs + nl);
+  out.line_flags.assign(m->line_flags, m->line_flags + nl);
+  ocr_phrase_matches_free(m);
   return out;
 }
 // A word read against a lexicon: text is the best entry's string when a candidate exists and cost - raw_cost <= max_penalty * G for

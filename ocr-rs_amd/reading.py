@@ -43,11 +43,14 @@ recognition -> output text), composed over the C ABI.
     read_words(..., spaces={}) and read_words_rectified(..., spaces={}) cut a polygon that holds several words at its inter-word gaps,
     between the crops and the classify call; the lexicon and the model then see every word on its own:
         ocr_break_words           the words of a glyph block -> the words inside them      (csrc/word_breaks.hip)
+    read_words(..., phrases={"lexicon": lex}) and read_words_rectified(..., phrases=...) segment the glyphs of every polygon into
+    lexicon words and out-of-vocabulary words after the classify call; with spaces= the gaps enter as soft costs, not as cuts:
+        ocr_lexicon_phrase_match  the glyph costs of every polygon -> its words and their entries (csrc/lexicon_phrase.hip)
 
 The segmentation, strip and line rules are build-defined (the reference never built the step): include/ocr_amd.h, restated in
 tests/glyph_oracle.py, tests/glyph_cc_oracle.py, tests/glyph_mask_oracle.py, tests/strip_oracle.py, tests/curved_strip_oracle.py and
 tests/line_oracle.py; the lexicon rule likewise, restated in tests/lexicon_oracle.py, the language model's in tests/char_lm_oracle.py
-and the word-break rule in tests/word_break_oracle.py.
+the word-break rule in tests/word_break_oracle.py and the phrase rule in tests/phrase_oracle.py.
 """
 from __future__ import annotations
 
@@ -179,6 +182,70 @@ def _spaced_word(text: str, probs, where, k: int, g0: int, sub, breaks, matches,
     return (" ".join(p[0] for p in parts), probs, where, *extras, (off, breaks.gap_pct[s0:s1].copy()))
 
 
+_PHRASE_KEYS = ("lexicon", "params", "break_penalty", "join_penalty")
+
+
+def _check_phrases(phrases, lexicon, lattice=None):
+    """phrases=: a dict with `lexicon` (a capi.Lexicon) and optionally `params`, `break_penalty`, `join_penalty`; not with lexicon= or
+    lattice=, whose matches read a fixed word."""
+    if lattice is not None:
+        raise capi.OcrError(1, "phrases: the composition with lattice= is not built (the phrase search reads glyphs, not pieces)")
+    if lexicon is not None:
+        raise capi.OcrError(1, "phrases: lexicon= matches every word on its own; give the word list as phrases['lexicon'] alone")
+    if not isinstance(phrases, dict) or any(k not in _PHRASE_KEYS for k in phrases):
+        raise TypeError(f"phrases: expected a dict with the keys {_PHRASE_KEYS}, got {phrases!r}")
+    if not isinstance(phrases.get("lexicon"), capi.Lexicon):
+        raise TypeError(f"phrases: 'lexicon' must be a capi.Lexicon, got {type(phrases.get('lexicon')).__name__}")
+
+
+def _classify_phrases(rec, crops, ng: int, dev, glyphs, sub, breaks, phrases, lm=None, lm_params=None):
+    """classify on device crops, glyph costs, the phrase match over the polygons of `glyphs` and - with a language model - the decode
+    of the words the match found -> (labels, probs, PhraseMatches, LmPaths or None).  `sub` and `breaks` are the result of
+    ocr_break_words or None: with them the gaps enter as costs (capi.phrase_gap_costs), without them the gap costs are zeros."""
+    import torch
+    if lm is not None and not isinstance(lm, capi.CharLm):
+        raise TypeError(f"lm: expected a capi.CharLm, got {type(lm).__name__}")
+    labels = np.zeros(0, np.int32)
+    probs = np.zeros(0, np.float64)
+    costs_ptr = 0
+    if ng:
+        lab = torch.empty(ng, dtype=torch.int32, device=dev)
+        pr = torch.empty(ng, dtype=torch.float64, device=dev)
+        logits = torch.empty((ng, 62), dtype=torch.float32, device=dev)
+        rec.classify_device(crops.data_ptr(), ng, logits.data_ptr(), lab.data_ptr(), pr.data_ptr())
+        costs = torch.empty((ng, 62), dtype=torch.float32, device=dev)
+        rec.glyph_costs_device(logits.data_ptr(), ng, costs.data_ptr())   # blocking, behind the classify call
+        costs_ptr = costs.data_ptr()
+        labels, probs = lab.cpu().numpy(), pr.cpu().numpy()
+    bound = join = None
+    if breaks is not None:
+        bound, join = capi.phrase_gap_costs(sub, breaks, float(phrases.get("break_penalty", 2.0)), float(phrases.get("join_penalty", 2.0)))
+    pm = rec.phrase_match_device(phrases["lexicon"], costs_ptr, ng, glyphs.word_offsets, bound, join, phrases.get("params"))
+    paths = None
+    if lm is not None:
+        paths = rec.lm_decode_device(lm, costs_ptr, ng, pm.word_offsets, lm_params)
+        paths.best = paths.texts(pm.word_offsets)   # hypothesis 0 of every word of the match
+    return labels, probs, pm, paths
+
+
+def _phrase_word(text: str, probs, where, k: int, pm, lexicon, paths=None):
+    """The tuple of polygon k read with phrases=: its words (the rows of line k of the match) joined by one space, a lexicon word as the
+    entry's string, an out-of-vocabulary word as its per-glyph argmax or - with a language model and at most 32 glyphs - hypothesis 0
+    of the decode; the polygon's rows of the match (PhraseMatches.line) are appended."""
+    w0, w1 = int(pm.line_word_offsets[k]), int(pm.line_word_offsets[k + 1])
+    o = (pm.word_offsets[w0:w1 + 1] - pm.word_offsets[w0]).tolist()
+    parts = []
+    for i in range(w1 - w0):
+        e = int(pm.entries[w0 + i])
+        if e >= 0:
+            parts.append(lexicon.words[e])
+        elif paths is not None and int(paths.word_flags[w0 + i]) == 0:
+            parts.append(paths.best[w0 + i])
+        else:
+            parts.append(text[o[i]:o[i + 1]])
+    return (" ".join(parts), probs, where, pm.line(k))
+
+
 def _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params, cc, lm, lattice, split, lattice_lexicon=None,
                         lattice_lexicon_params=None, max_penalty=1.5):
     """segment -> split -> spans -> crops -> classify + costs -> decode, everything between the calls on the device; per word
@@ -247,7 +314,7 @@ def _read_words_lattice(det, rec, x, n, h, w, dev, polys, adjust_values, params,
 
 def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=None, cc=None, mask=None, lexicon=None,
                lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None, lattice=None,
-               split=None, lattice_lexicon=None, lattice_lexicon_params=None, spaces=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+               split=None, lattice_lexicon=None, lattice_lexicon_params=None, spaces=None, phrases=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch.
 
     det_net: text_detection.FuncT or capi.Detector (supplies the GPU and stream of the segmentation); rec_net: char_recognition.Net
@@ -290,7 +357,16 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     lists with one entry per sub-word, and the tuple gains (starts, gap_pct) as its last element: starts int32 [S+1], the sub-word
     ranges inside the polygon's glyphs, and gap_pct int32 [S], the gap in front of every sub-word in percent of the polygon's median
     glyph height (0 for the first).  lattice= with spaces= raises OcrError: the composition is not built.  With spaces=None nothing
-    changes."""
+    changes.
+    phrases: None, or a dict with `lexicon` (a capi.Lexicon) and optionally `params` (capi.PhraseParams or a dict of its fields),
+    `break_penalty` and `join_penalty` (default 2.0 each): the glyphs of every polygon are segmented into lexicon words and
+    out-of-vocabulary words by one search over the glyph costs (ocr_lexicon_phrase_match), after the classify call.  With spaces= the
+    breaks of ocr_break_words enter as costs (capi.phrase_gap_costs: starting a word where the gaps found none costs break_penalty,
+    reading across a found break costs join_penalty) and cut nothing; without it the gap costs are zeros.  The polygon's text is its
+    words joined by one space: a lexicon word is the entry's string, an out-of-vocabulary word its per-glyph argmax or, with lm=, the
+    model's best reading of it (words of at most 32 glyphs).  probs and where stay per glyph, and the tuple's last element is the
+    polygon's rows of the match (capi.PhraseMatches.line: word_offsets relative to the polygon, entries, word_costs, line_costs,
+    raw_costs, line_flags).  phrases= with lexicon= or lattice= raises OcrError.  With phrases=None nothing changes."""
     import torch
 
     det = _handle(det_net, capi.Detector)
@@ -309,6 +385,8 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     n, _, h, w = x.shape
     # the library's calls run on their handles' streams: whatever torch queued to produce x is finished first
     torch.cuda.current_stream(dev).synchronize()
+    if phrases is not None:
+        _check_phrases(phrases, lexicon, lattice)
     if lattice is not None:
         if spaces is not None:
             raise capi.OcrError(1, "lattice: the composition with spaces= is not built (break the words, then call the lattice calls on the block)")
@@ -323,14 +401,19 @@ def read_words(det_net, rec_net, frames, polygon_scores, adjust_values, params=N
     glyphs, crops = _segment_and_crop(det, x.data_ptr(), n, h, w, polys, adjust_values, params, cc, mask, dev)   # blocking
     ng = glyphs.n_glyphs
     sub, breaks = det.break_words(glyphs, spaces) if spaces is not None else (glyphs, None)
-    labels, probs, matches, paths = _classify(rec, crops, ng, dev, sub.word_offsets, lexicon, lexicon_params, lm, lm_params)
+    if phrases is not None:
+        labels, probs, pm, paths = _classify_phrases(rec, crops, ng, dev, glyphs, sub, breaks, phrases, lm, lm_params)
+    else:
+        labels, probs, matches, paths = _classify(rec, crops, ng, dev, sub.word_offsets, lexicon, lexicon_params, lm, lm_params)
     out = []
     for b in range(n):
         words = []
         for k in range(int(glyphs.img_offsets[b]), int(glyphs.img_offsets[b + 1])):
             g0, g1 = int(glyphs.word_offsets[k]), int(glyphs.word_offsets[k + 1])
             text = "".join(VALUES[int(c)] for c in labels[g0:g1])
-            if breaks is None:
+            if phrases is not None:
+                words.append(_phrase_word(text, probs[g0:g1].copy(), glyphs.boxes[g0:g1].copy(), k, pm, phrases["lexicon"], paths))
+            elif breaks is None:
                 words.append(_word(text, probs[g0:g1].copy(), glyphs.boxes[g0:g1].copy(), k, g1 - g0, matches, lexicon, max_penalty, paths))
             else:
                 words.append(_spaced_word(text, probs[g0:g1].copy(), glyphs.boxes[g0:g1].copy(), k, g0, sub, breaks, matches, lexicon,
@@ -404,7 +487,8 @@ def _curved(curved, strip_params):
 
 
 def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values, strip_params=None, params=None, cc=None, mask=None,
-                         curved=None, lexicon=None, lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None, spaces=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
+                         curved=None, lexicon=None, lexicon_params=None, max_penalty=1.5, lm=None, lm_params=None, spaces=None,
+                         phrases=None) -> List[List[Tuple[str, np.ndarray, np.ndarray]]]:
     """Reads every detected word of a batch through its upright strip: rotated words are read along their own axis, and with
     curved=True (or {} or a dict of capi.CurveParams' fields: strip_height, max_width, valid_pct) words that bend are read along their
     own centreline (ocr_plan_curved_strips, ocr_extract_curved_strips; the glyph quads then come from curved_glyph_quads).  curved=None
@@ -414,7 +498,7 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     params, cc and mask: the segmentation parameters, rule and crop masking as in read_words, applied to the atlas.  Returns per image, per polygon: (text, probability of every character
     (f64), glyph quads k x 4 x 2 f64: the corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) of every glyph box mapped back to frame
     coordinates, strip_glyph_quads).  A flat word reads as "".  lexicon, lexicon_params, max_penalty, lm and lm_params as in read_words; spaces likewise, applied to the atlas' glyph block (a strip is upright, so the
-    gaps are measured along the word's own axis)."""
+    gaps are measured along the word's own axis), and phrases likewise (the tuple's last element is then the polygon's rows of the match)."""
     import torch
 
     det = _handle(det_net, capi.Detector)
@@ -425,6 +509,8 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
     dev = x.device
     n, _, h, w = x.shape
     cp = _curved(curved, strip_params)
+    if phrases is not None:
+        _check_phrases(phrases, lexicon)
     if cp is None:
         strips = det.plan_word_strips(polys, adjust_values, h, w, strip_params, scores)
     else:
@@ -441,7 +527,10 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
         glyphs, crops = _segment_and_crop(det, atlas.data_ptr(), 1, hs, tw, rects, [[1.0, 1.0]], params, cc, mask, dev)
     ng = glyphs.n_glyphs
     sub, breaks = det.break_words(glyphs, spaces) if spaces is not None else (glyphs, None)
-    labels, probs, matches, paths = _classify(rec, crops, ng, dev, sub.word_offsets, lexicon, lexicon_params, lm, lm_params)
+    if phrases is not None:
+        labels, probs, pm, paths = _classify_phrases(rec, crops, ng, dev, glyphs, sub, breaks, phrases, lm, lm_params)
+    else:
+        labels, probs, matches, paths = _classify(rec, crops, ng, dev, sub.word_offsets, lexicon, lexicon_params, lm, lm_params)
     quads = (strip_glyph_quads if cp is None else curved_glyph_quads)(
         strips, np.repeat(np.arange(glyphs.n_words), np.diff(glyphs.word_offsets)), glyphs.boxes)
     text = "".join(VALUES[int(c)] for c in labels)
@@ -450,7 +539,9 @@ def read_words_rectified(det_net, rec_net, frames, polygon_scores, adjust_values
         words = []
         for k in range(int(strips.img_offsets[b]), int(strips.img_offsets[b + 1])):
             g0, g1 = int(glyphs.word_offsets[k]), int(glyphs.word_offsets[k + 1])
-            if breaks is None:
+            if phrases is not None:
+                words.append(_phrase_word(text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy(), k, pm, phrases["lexicon"], paths))
+            elif breaks is None:
                 words.append(_word(text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy(), k, g1 - g0, matches, lexicon, max_penalty, paths))
             else:
                 words.append(_spaced_word(text[g0:g1], probs[g0:g1].copy(), quads[g0:g1].copy(), k, g0, sub, breaks, matches, lexicon,
@@ -479,7 +570,7 @@ def read_lines(det_net, rec_net, frames, polygon_scores, adjust_values, line_par
     """Reads every detected word of a batch and groups the words of every image into text lines in reading order (ocr_group_lines).
 
     Arguments as read_words_rectified (rectified=True, the default) or read_words (rectified=False); strip_params, params, cc, mask and
-    curved go to that call unchanged, and so do lexicon, lexicon_params, max_penalty, lm and lm_params (the lines then join the matched or decoded texts) and spaces (a polygon's text then carries its inner spaces, in place).  line_params: capi.LineParams, a dict of its fields (line_tol, height_ratio, min_cos, max_gap) or
+    curved go to that call unchanged, and so do lexicon, lexicon_params, max_penalty, lm and lm_params (the lines then join the matched or decoded texts) and spaces (a polygon's text then carries its inner spaces, in place) and phrases (likewise).  line_params: capi.LineParams, a dict of its fields (line_tol, height_ratio, min_cos, max_gap) or
     None for the defaults.  The quads always come from ocr_plan_word_strips (with strip_params where given): word order equals polygon
     order in every reading call, and the curved plan carries no quads.
     Returns per image a list of lines (text, word_indices, gaps): word_indices are the image's polygon indices in reading order (int32),
