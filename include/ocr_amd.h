@@ -96,6 +96,12 @@ int ocr_det_create(const void* weights, size_t weights_bytes, int device, ocr_de
  *                               other's persistent grids.  Same workspace (a group is a pointer offset), same kernels, the same bits.  0 = off; k >= N = no
  *                               split; auto = two halves, in the f32 precision, when a half fills the resident slots of layer1's persistent grids once (5.12 frames of
  *                               640 x 640 on 256 CUs) and no pipelined batch is pending on the handle.  A negative or unparsable value is OCR_ERR_INVALID
+ *   top_side=auto|0|<mask> (auto) where overlap=3 is in effect, in the f32 precision with out4 / out5 as three-launch F(4x4) Winograd convs: launches behind
+ *                               layer3 that do not depend on their main-stream predecessors run on the second stream.  A mask of moves - 1: layer4's shortcut
+ *                               conv (beside layer4's first convs), 2: in4 as a plain conv beside layer4, the top-down add up2(in5) + in4 made where out4's
+ *                               input transform loads its patch (the one f32 add the conv's epilogue made, on the same operands), 4: out5's three launches
+ *                               beside out4's, on a Winograd scratch of their own.  Same kernels otherwise, the same bits.  0 = off; auto = all three, and
+ *                               none while a pipelined batch is pending on the handle.  A value outside 0..7 is OCR_ERR_INVALID
  *   bf16_block_fuse=0|1  (1)    bf16 precision: each BasicBlock of layer1 (conv3x3 + BN + ReLU, conv3x3 + BN, + x, ReLU: model.rs:40-55) as ONE launch, the
  *                               activation between its two convs held in LDS (basic_block_bf16_c64.hip): half the HBM traffic of the two launches, 1.25 x
  *                               their matrix work, 5-10 % less time; 0 = two conv3x3_bf16_c64 launches.  The same bits either way
@@ -192,6 +198,9 @@ int ocr_det_synchronize(ocr_det_t* det);
 /* Which schedule the most recent forward of this handle took (engine option front_split): *k = frames of the first frame group, 0 = it ran
  * unsplit (the last chunk's, for a batch that ran in several).  Results never depend on it. */
 int ocr_det_last_front_split(ocr_det_t* det, int32_t* k);
+/* ... and which moves of engine option top_side it took: a mask of 1 (layer4's shortcut conv), 2 (in4) and 4 (out5) on the side stream, 0 =
+ * none.  Results never depend on it. */
+int ocr_det_last_top_side(ocr_det_t* det, int32_t* moves);
 
 /* Per-kernel timing of one forward (hipEvents on the handle's stream around every
  * launch).  names[i] points to a static string; ms/flops/bytes are per launch:

@@ -26,7 +26,7 @@ EXPORTS = [
     "ocr_varstore_to_blob", "ocr_blob_free", "ocr_det_create_from_varstore", "ocr_rec_create_from_varstore",
     "ocr_det_create", "ocr_det_create_with_options", "ocr_det_destroy", "ocr_det_set_stream", "ocr_det_set_precision", "ocr_det_forward",
     "ocr_det_forward_u8", "ocr_host_alloc", "ocr_host_free", "ocr_det_detect_pipelined_host",
-    "ocr_det_forward_async", "ocr_det_synchronize", "ocr_det_last_front_split", "ocr_det_forward_profile",
+    "ocr_det_forward_async", "ocr_det_synchronize", "ocr_det_last_front_split", "ocr_det_last_top_side", "ocr_det_forward_profile",
     "ocr_preprocess_image", "ocr_preprocess_batch", "ocr_preprocess_batch_async", "ocr_postproc_default_params", "ocr_det_postprocess", "ocr_det_post_stats", "ocr_det_detect_pipelined", "ocr_polygons_free",
     "ocr_extract_crops", "ocr_segment_default_params", "ocr_segment_glyphs", "ocr_extract_glyph_crops", "ocr_glyphs_free",
     "ocr_cc_default_params", "ocr_segment_glyphs_cc",
@@ -1741,6 +1741,14 @@ class Detector:
         check(f(self._h, C.byref(k)))
         return int(k.value)
 
+    def last_top_side(self) -> int:
+        """The moves of option top_side that the most recent forward took (a mask of 1 | 2 | 4); 0 = today's order."""
+        m = C.c_int32(-1)
+        f = lib().ocr_det_last_top_side   # (bound here, like last_front_split)
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        check(f(self._h, C.byref(m)))
+        return int(m.value)
+
     def forward_host(self, x: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)
         n, c, h, w = x.shape
@@ -2283,6 +2291,21 @@ class Detector:
         check(test_lib().ocr_test_winograd_run(self._h, int(form), _ptr(x), n, h, w, cin, _ptr(wg), cout, p(sc), p(bi), p(rs), int(bool(relu)),
                                                int(bool(inplace)), int(num_cus), int(bool(poison)), _ptr(io), int(guard)))
         return io[:px].reshape(n, h, w, cout), io[px:]
+
+    def debug_winograd_topdown(self, x_nhwc, low_nhwc=None, guard=64, sentinel=-7.0):
+        """The F(4x4) input transform alone (test hook): with low (N x H/2 x W/2 x C) the engine's top_side form, which adds up2(low) on load;
+        without it the plain transform of x.  Both sources sit between NaN regions of their allocations.  Returns (V [36][T][C], the `guard`
+        elements behind it, which went to the device as `sentinel`)."""
+        x = np.ascontiguousarray(x_nhwc, dtype=np.float32)
+        low = None if low_nhwc is None else np.ascontiguousarray(low_nhwc, dtype=np.float32)
+        n, h, w, c = x.shape
+        assert low is None or low.shape == (n, h // 2, w // 2, c), low.shape
+        T = n * ((h + 3) // 4) * ((w + 3) // 4)
+        io = np.full(36 * T * c + guard, sentinel, np.float32)
+        f = test_lib().ocr_test_winograd_topdown
+        f.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_int]
+        check(f(self._h, _ptr(x), None if low is None else _ptr(low), n, h, w, c, _ptr(io), int(guard)))
+        return io[:36 * T * c].reshape(36, T, c), io[36 * T * c:]
 
     def debug_bf16_trunk_run(self, form, x_nhwc, wgt_ohwi, scale=None, bias=None, residual=None, relu=False, stride=1, up_residual=None, want_out=True,
                              wgt2=None, scale2=None, bias2=None, num_cus=0, guard=64, poison=False, sentinel=-7.0, claim=None):

@@ -175,6 +175,13 @@ int ocr_det_last_front_split(ocr_det_t* det, int32_t* k) {
   });
 }
 
+int ocr_det_last_top_side(ocr_det_t* det, int32_t* moves) {
+  return guard([&] {
+    if (!det || !moves) ocr::fail(OCR_ERR_INVALID, "det_last_top_side: null argument");
+    *moves = det->impl.last_top_side();
+  });
+}
+
 int ocr_det_synchronize(ocr_det_t* det) {
   return guard([&] {
     if (!det) ocr::fail(OCR_ERR_INVALID, "null handle");

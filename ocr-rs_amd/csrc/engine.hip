@@ -335,6 +335,13 @@ void Detector::parse_options(const char* options) {
         if (front_split_ < 0) fail(OCR_ERR_INVALID, "detector option front_split: %d (auto, 0 or the first group's frames)", front_split_);
       }
     }
+    else if (key == "top_side") {
+      if (val == "auto") top_side_ = -1;
+      else {
+        top_side_ = num();
+        if (top_side_ < 0 || top_side_ > 7) fail(OCR_ERR_INVALID, "detector option top_side: %d (auto, 0, or a mask of 1 | 2 | 4)", top_side_);
+      }
+    }
     else if (key == "w43_cus") {
       w43_cus_ = num();
       if (w43_cus_ < 0 || w43_cus_ > 4096) fail(OCR_ERR_INVALID, "detector option w43_cus: %d", w43_cus_);
@@ -400,6 +407,9 @@ Detector::Detector(const void* blob, size_t bytes, int device, const char* optio
       OCR_HIP(hipEventCreateWithFlags(&ev_side_, hipEventDisableTiming));
       OCR_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
       OCR_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
+      OCR_HIP(hipEventCreateWithFlags(&ev_d4_, hipEventDisableTiming));
+      OCR_HIP(hipEventCreateWithFlags(&ev_in4_, hipEventDisableTiming));
+      OCR_HIP(hipEventCreateWithFlags(&ev_i5_, hipEventDisableTiming));
     }
   }
   // 12.2 M parameters = 48.7 MB f32, the Winograd forms (F(4x4): 36 matrices per 3x3 conv of layer3/4, 113 MB; fused F(2x2): 16),
@@ -619,6 +629,9 @@ Detector::~Detector() {
     (void)hipEventDestroy(ev_side_);
     (void)hipEventDestroy(ev_fork_);
     (void)hipEventDestroy(ev_join_);
+    (void)hipEventDestroy(ev_d4_);
+    (void)hipEventDestroy(ev_in4_);
+    (void)hipEventDestroy(ev_i5_);
   }
   if (post_stream_) {
     (void)hipStreamSynchronize(post_stream_);
@@ -876,6 +889,14 @@ void Detector::ensure_workspace(int n, int h, int w) {
       wino_v_ = reinterpret_cast<float*>(alloc(need * 4));
       wino_m_ = reinterpret_cast<float*>(alloc(need * 4));
     }
+    // out5's own scratch (top_side): V over its 256 input channels, M over its 64 output channels
+    wino_v2_ = wino_m2_ = nullptr;
+    if (need && !bf16_ && fpn_composed_ && out_[3].wino && side_stream_) {
+      const size_t m = out_[3].wino_tile, a = m + 2;
+      const size_t T = N * (((h >> 5) + m - 1) / m) * (((w >> 5) + m - 1) / m);
+      wino_v2_ = reinterpret_cast<float*>(alloc(a * a * T * out_[3].cin * 4));
+      wino_m2_ = reinterpret_cast<float*>(alloc(a * a * T * out_[3].cout * 4));
+    }
   }
   tr1buf_ = fused_tail_ ? nullptr : reinterpret_cast<float*>(alloc(N * (h / 2) * (w / 2) * 64 * 4));
   ws_bf16_ = bf16_;
@@ -887,6 +908,8 @@ void Detector::ensure_workspace(int n, int h, int w) {
 namespace {
 // front_split=auto: the smaller frame group must fill the resident slots of layer1's persistent grids (two workgroups per CU) this many times
 constexpr long long kFrontSplitMinRounds = 1;
+// top_side=auto: the moves that measured a gain (1: layer4's shortcut, 2: in4, 4: out5)
+constexpr int kTopSideAuto = 7;
 
 // hipEvent pairs around every launch of ONE forward_chunk; entries are appended to the shared `prof` vector,
 // so a batch that runs in several chunks keeps every chunk's launches (base = first entry of this chunk).
@@ -1013,6 +1036,22 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
   };
   Group groups[2] = {{stream_, 0, n}, {side_stream_, front_k, n - front_k}};
   last_front_k_ = front_k;
+  // top_side: where overlap=3 is in effect and out4 / out5 take the three-launch F(4x4) form.  From layer3's end on the side stream holds
+  // only p3's upsampled term, and layer4's later launches and the FPN top leave CUs idle: layer4's shortcut conv and in4 read nothing but
+  // x_[2] and go in front of and behind that term; out5's chain needs only in5 and runs beside out4's.  auto: not while a pipelined call's previous
+  // batch is pending - its post-processing already runs beside this part of the forward (measured)
+  int top = 0;
+  {
+    const int h16 = h >> 4, w16 = w >> 4;
+    auto f43 = [&](const ConvW& cw, int hh, int ww) {
+      const size_t T = (size_t)n * ((hh + 3) / 4) * ((ww + 3) / 4);
+      return !cw.wino43_fused && cw.wino && cw.wino_tile == 4 && wino_v_ && 36 * T * std::max(cw.cin, cw.cout) * 4 < ((size_t)1 << 31);
+    };
+    if (overlap3 && !bf && top_side_ != 0 && wino_v2_ && f43(out_[2], h16, w16) && f43(out_[3], h16 / 2, w16 / 2) && f43(layer_[3][0][1], h16 / 2, w16 / 2) &&
+        in_[2].cout == out_[2].cin)
+      top = top_side_ > 0 ? top_side_ : pending_.valid ? 0 : kTopSideAuto;
+  }
+  last_top_side_ = top;
   int ngroups = 1;
   if (front_k) {
     groups[0].nf = front_k;
@@ -1128,37 +1167,56 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
     wa = (wm + 2) * (wm + 2);
     T = (size_t)n * ((hh + wm - 1) / wm) * ((ww + wm - 1) / wm);
   };
-  auto wino_in = [&](const ConvW& cw, const void* src, int hh, int ww) {
+  // (scratch and stream are the caller's: the shared pair on the main stream, or out5's own on the side stream - top_side)
+  struct WinoRun {
+    float *v, *m;
+    hipStream_t s;
+  };
+  const WinoRun wino_main{wino_v_, wino_m_, stream_};
+  // low != null: the top-down sum up2(low) + src is formed on load (F(4x4) only)
+  auto wino_in = [&](const WinoRun& wr, const ConvW& cw, const void* src, int hh, int ww, const void* low = nullptr) {
     size_t wm, wa, T;
     wino_dims(cw, hh, ww, wm, wa, T);
     rec.begin();
-    launch_winograd_input(static_cast<const float*>(src), wino_v_, n, hh, ww, cw.cin, (int)wm, stream_);
+    if (low) launch_winograd_input_up2(static_cast<const float*>(src), static_cast<const float*>(low), wr.v, n, hh, ww, cw.cin, wr.s);
+    else launch_winograd_input(static_cast<const float*>(src), wr.v, n, hh, ww, cw.cin, (int)wm, wr.s);
     rec.end(wm == 4 ? "winograd43_input_transform" : "winograd_input_transform", 0.0,
             (double)n * hh * ww * cw.cin * 4.0 + (double)wa * T * cw.cin * 4.0);
   };
-  auto wino_gemm = [&](const char* name, const ConvW& cw, int hh, int ww) {
+  auto wino_gemm = [&](const WinoRun& wr, const char* name, const ConvW& cw, int hh, int ww) {
     size_t wm, wa, T;
     wino_dims(cw, hh, ww, wm, wa, T);
     const bool x3 = split_bf16_ && cw.wino_x3;
     rec.begin();
-    const ConvDesc d = launch_winograd_gemm(wino_v_, x3 ? cw.wino_x3 : cw.wino, x3, (int)wa, T, cw.cin, cw.cout, wino_m_, name, stream_);
+    const ConvDesc d = launch_winograd_gemm(wr.v, x3 ? cw.wino_x3 : cw.wino, x3, (int)wa, T, cw.cin, cw.cout, wr.m, name, wr.s);
     rec.end(conv_igemm_kernel_name(d), 2.0 * wa * T * cw.cin * cw.cout,
             (double)wa * 4.0 * ((double)T * cw.cin + (double)T * cw.cout + (double)cw.cin * cw.cout));
   };
-  auto wino_out = [&](const ConvW& cw, int hh, int ww, void* out, const void* residual, bool relu) {
+  auto wino_out = [&](const WinoRun& wr, const ConvW& cw, int hh, int ww, void* out, const void* residual, bool relu) {
     size_t wm, wa, T;
     wino_dims(cw, hh, ww, wm, wa, T);
     rec.begin();
-    launch_winograd_output(wino_m_, cw.scale, cw.bias, static_cast<const float*>(residual), relu ? 1 : 0, static_cast<float*>(out),
-                           n, hh, ww, cw.cout, (int)wm, stream_);
+    launch_winograd_output(wr.m, cw.scale, cw.bias, static_cast<const float*>(residual), relu ? 1 : 0, static_cast<float*>(out),
+                           n, hh, ww, cw.cout, (int)wm, wr.s);
     rec.end(wm == 4 ? "winograd43_output_transform" : "winograd_output_transform", 0.0,
             (double)wa * T * cw.cout * 4.0 + (double)n * hh * ww * cw.cout * 4.0 * (residual ? 2.0 : 1.0));
   };
 
   // 3x3 s1 conv + BN (+ residual) + ReLU of the deep layers as Winograd F(2x2,3x3): input transform, sixteen
   // [tiles x Cin] x [Cin x Cout] GEMMs in one batched launch, output transform with the epilogue (f32 only)
+  // does conv3x3 run this conv as the three launches on the shared scratch?
+  auto three_launch = [&](const ConvW& cw, int hh, int ww) {
+    const size_t wm = cw.wino_tile, wa = (wm + 2) * (wm + 2);
+    const size_t T = (size_t)n * ((hh + wm - 1) / wm) * ((ww + wm - 1) / wm);
+    return !bf && !cw.wino43_fused && cw.wino && wino_v_ && wa * T * std::max(cw.cin, cw.cout) * 4 < ((size_t)1 << 31);
+  };
+  hipEvent_t residual_ready = nullptr;   // top_side: the next conv3x3's residual comes from the side stream - the main stream waits here, as late as the form allows
   auto conv3x3 = [&](const char* name, const ConvW& cw, const void* src, int hh, int ww, void* out, const void* residual,
                      bool relu = true) {
+    if (residual_ready && !three_launch(cw, hh, ww)) {
+      OCR_HIP(hipStreamWaitEvent(stream_, residual_ready, 0));
+      residual_ready = nullptr;
+    }
     if (!bf && cw.wino43_fused) {  // transforms fused into the GEMM kernel
       {
         rec.begin();
@@ -1192,9 +1250,13 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
       return;
     }
     if (frn != n) fail(OCR_ERR_INTERNAL, "conv %s: a frame group of the three-launch Winograd form (shared scratch)", name);
-    wino_in(cw, src, hh, ww);
-    wino_gemm(name, cw, hh, ww);
-    wino_out(cw, hh, ww, out, residual, relu);
+    wino_in(wino_main, cw, src, hh, ww);
+    wino_gemm(wino_main, name, cw, hh, ww);
+    if (residual_ready) {
+      OCR_HIP(hipStreamWaitEvent(stream_, residual_ready, 0));
+      residual_ready = nullptr;
+    }
+    wino_out(wino_main, cw, hh, ww, out, residual, relu);
   };
 
   // composed FPN level lv (0: p2, 1: p3) and its term of bin_conv1: p_k = A_k * x_k + B_k *' x_{k+1} - the
@@ -1262,7 +1324,8 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
         if (l == 0) per_group([&] { conv3x3("layer.conv1", layer_[l][0][0], cur, hin, win, t_[l], nullptr); });  // stride 1 in layer1
         else per_group([&] { conv("layer.conv1", layer_[l][0][0], cur, hin, win, stride, t_[l], true); });
         if (l > 0) {
-          per_group([&] { conv("layer.downsample", down_[l], cur, hin, win, stride, d_[l], false); });
+          if (l == 3 && (top & 1)) residual_ready = ev_d4_;   // queued on the side stream behind layer3; conv2's output transform waits for it
+          else per_group([&] { conv("layer.downsample", down_[l], cur, hin, win, stride, d_[l], false); });
           sc.residual = d_[l];
         }
       }
@@ -1279,6 +1342,10 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
       // its upsampled term, bin_conv1's p2 term (into layer1's free temporary) and p3's lateral term follow layer2, p3's upsampled term
       // layer3.  Sums are re-associated (lateral + upsampled instead of upsampled + lateral: the same bits; pyramid + bias + p2 term instead
       // of p2 term + bias + pyramid: one rounding apart)
+      // top_side adds split-bf16 launches that also depend on the trunk alone: layer4's shortcut conv follows layer3, in front of p3's
+      // upsampled term, in4 (plain) behind it; out5's three launches follow in5, on a Winograd scratch of their own.  The main stream waits
+      // for the shortcut before the output transform of layer4.0.conv2 and for in4 before out4's input transform; ev_side_ in front of
+      // bin_conv1 covers out5
       // Split front: the side stream first takes the second group through layer2, and the main stream waits for that before layer3; the
       // side work follows it, and as it reads whole-batch x_[0] / x_[1], it waits for the first group's layer1 / layer2 as before
       OCR_HIP(hipEventRecord(ev_x1_, stream_));
@@ -1319,10 +1386,21 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
       OCR_HIP(hipEventRecord(ev_x3_, stream_));
       OCR_HIP(hipStreamWaitEvent(side_stream_, ev_x3_, 0));
       cs = side_stream_;
+      // top_side: what else reads only x_[2] - layer4's shortcut conv first (d_[3], wanted four launches into layer4), and behind p3's term in4
+      // as a plain conv into sum_[2] (the top-down add happens in out4's input transform; in front of p3's term it measured 0.016 ms slower:
+      // three launches beside layer4's stride-2 conv at once).  Both buffers were last touched on the main stream before ev_x3_
+      if (top & 1) {
+        conv("layer.downsample", down_[3], x_[2], h >> 4, w >> 4, 2, d_[3], false);
+        OCR_HIP(hipEventRecord(ev_d4_, side_stream_));
+      }
       Extra up;
       up.store = STORE_PHASE;
       up.residual = p_[1];
       conv("fpn.upsampled", fpn_b_[1], x_[2], h >> 4, w >> 4, 1, p_[1], false, up);
+      if (top & 2) {
+        conv("in4", in_[2], x_[2], h >> 4, w >> 4, 1, sum_[2], false);
+        OCR_HIP(hipEventRecord(ev_in4_, side_stream_));
+      }
       cs = stream_;
     } else if (overlap && (l == 1 || l == 2)) {
       // x_{l+1}... is ready: p2 (after layer2) / p3 (after layer3) and their bin_conv1 terms only need the trunk
@@ -1350,14 +1428,33 @@ void Detector::forward_chunk(const void* x, int n, int h, int w, float* prob, ui
       conv3x3("out", out_[2], sum_[2], h >> 4, w >> 4, p_[2], nullptr, false);
       join();
     } else {
-      {
-        Extra td;
-        td.up_residual = i_[3];
-        td.out2 = sum_[2];
-        conv("in+topdown", in_[2], x_[2], h >> 4, w >> 4, 1, nullptr, false, td);
+      if (top & 4) {
+        // out5 needs only in5: its three launches on the side stream, on their own scratch, beside out4's.  The side stream's record of
+        // ev_side_ below comes after them, so bin_conv1 - and with it the next call's in5 and out5 - waits for p_[3] and for the reads of i_[3]
+        OCR_HIP(hipEventRecord(ev_i5_, stream_));
+        OCR_HIP(hipStreamWaitEvent(side_stream_, ev_i5_, 0));
+        const WinoRun wino_side{wino_v2_, wino_m2_, side_stream_};
+        wino_in(wino_side, out_[3], i_[3], h >> 5, w >> 5);
+        wino_gemm(wino_side, "out5", out_[3], h >> 5, w >> 5);
+        wino_out(wino_side, out_[3], h >> 5, w >> 5, p_[3], nullptr, false);
       }
-      conv3x3("out", out_[2], sum_[2], h >> 4, w >> 4, p_[2], nullptr, false);
-      if (out_[3].wino) conv3x3("out5", out_[3], i_[3], h >> 5, w >> 5, p_[3], nullptr, false);
+      if (top & 2) {
+        // sum_[2] holds in4 alone (side stream); up2(in5) + in4 is the one add it always was, made where out4's transform loads its patch
+        OCR_HIP(hipStreamWaitEvent(stream_, ev_in4_, 0));
+        wino_in(wino_main, out_[2], sum_[2], h >> 4, w >> 4, i_[3]);
+        wino_gemm(wino_main, "out", out_[2], h >> 4, w >> 4);
+        wino_out(wino_main, out_[2], h >> 4, w >> 4, p_[2], nullptr, false);
+      } else {
+        {
+          Extra td;
+          td.up_residual = i_[3];
+          td.out2 = sum_[2];
+          conv("in+topdown", in_[2], x_[2], h >> 4, w >> 4, 1, nullptr, false, td);
+        }
+        conv3x3("out", out_[2], sum_[2], h >> 4, w >> 4, p_[2], nullptr, false);
+      }
+      if (top & 4) {}   // (queued above)
+      else if (out_[3].wino) conv3x3("out5", out_[3], i_[3], h >> 5, w >> 5, p_[3], nullptr, false);
       else conv("out5", out_[3], i_[3], h >> 5, w >> 5, 1, p_[3], false);
     }
     if (overlap) {

@@ -76,6 +76,7 @@ class Detector {
   void set_precision(int precision);
   int precision() const { return bf16_ ? 1 : 0; }
   int last_front_split() const { return last_front_k_; }   // ocr_det_last_front_split
+  int last_top_side() const { return last_top_side_; }     // ocr_det_last_top_side
   // device pointers; enqueues on stream().  prof != null -> per-launch events.
   // x: N x 1 x H x W frames, f32 or (x_u8 != 0) u8 raw luma; wait_for: an event the first launch waits for (the
   // copy that brings x in), may be null
@@ -192,8 +193,15 @@ class Detector {
   // k > 0: the first group's frames (k >= n: no split)
   int front_split_ = -1;
   int last_front_k_ = 0;   // frames of the first group in the most recent forward_chunk (0: it ran unsplit)
+  // option top_side: launches behind layer3 that do not depend on their main-stream predecessors go to the side stream,
+  // where overlap=3 is in effect and out4 / out5 run as three-launch F(4x4) Winograd convs (f32 precision).  A mask of moves - 1: layer4's
+  // shortcut conv, 2: in4 as a plain conv (the top-down add moves into out4's input transform), 4: out5's three launches beside out4's on a
+  // scratch of their own; -1: auto = kTopSideAuto, not while a pipelined call's previous batch is pending; 0: off
+  int top_side_ = -1;
+  int last_top_side_ = 0;  // the moves of the most recent forward_chunk
   hipStream_t side_stream_ = nullptr;
   hipEvent_t ev_x1_ = nullptr, ev_x2_ = nullptr, ev_x3_ = nullptr, ev_side_ = nullptr, ev_fork_ = nullptr, ev_join_ = nullptr;
+  hipEvent_t ev_d4_ = nullptr, ev_in4_ = nullptr, ev_i5_ = nullptr;   // top_side: layer4's shortcut and in4 done (side stream), in5 done (main stream)
   DeviceArena arena_;
   float *stem_w_ = nullptr, *stem_scale_ = nullptr, *stem_bias_ = nullptr;
   std::vector<float> stem_w_host_;  // conv1 [64][49], kept for the bf16 fragments
@@ -229,6 +237,7 @@ class Detector {
   int winograd_min_cin_ = 256;
   int winograd43_min_cin_ = 256;      // unfused Winograd layers with at least this many channels use F(4x4,3x3)
   float *wino_v_ = nullptr, *wino_m_ = nullptr;  // [(m+2)^2][T][C] and [(m+2)^2][T][K] scratch of the layer in flight
+  float *wino_v2_ = nullptr, *wino_m2_ = nullptr;  // ... and out5's own, so that it can run beside out4 (top_side)
   void add_winograd_weights(ConvW& cw);
   void add_winograd_fused_weights(ConvW& cw);
   bool out4_fused_ = false;      // option out4_fused=1: out4 (256 -> 64 at H/16) on the fused F(4x4,3x3) kernel (0.102 ms) instead of the

@@ -1409,6 +1409,36 @@ int ocr_test_winograd_run(ocr_det_t* det, int form, const float* x, int n, int h
   });
 }
 
+// the F(4x4) input transform alone, as the engine launches it for out4.  low != null: launch_winograd_input_up2 over x [n][h][w][c] and low
+// [n][h / 2][w / 2][c] (top_side: the top-down sum formed on load); low == null: launch_winograd_input over x.  x and low sit inside one
+// allocation each with (w + 1) c floats or more in front and behind - quiet NaN: both descriptors start one row and one pixel before their
+// tensor, so the front region is what a failed mask would read.  v_io: [36 T c + guard_elems], T = n ceil(h / 4) ceil(w / 4), uploaded before
+// the launch and downloaded whole after it
+int ocr_test_winograd_topdown(ocr_det_t* det, const float* x, const float* low, int n, int h, int w, int c, float* v_io, int guard_elems) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !x || !v_io) fail(OCR_ERR_INVALID, "null argument");
+    if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || guard_elems < 0 || (low && ((h | w) & 1))) fail(OCR_ERR_INVALID, "winograd top-down hook: bad shape");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    HookBuffers b;
+    const size_t T = (size_t)n * ((h + 3) / 4) * ((w + 3) / 4), v_e = 36 * T * c + guard_elems;
+    auto between_nan = [&](const float* src, int hh, int ww) {
+      const size_t e = (size_t)n * hh * ww * c, lead = (((size_t)(ww + 1) * c + 1023) / 1024) * 1024;
+      std::vector<float> img(lead + e + lead, std::numeric_limits<float>::quiet_NaN());
+      std::copy(src, src + e, img.begin() + lead);
+      return b.f32(img.data(), img.size()) + lead;
+    };
+    const float* d_x = between_nan(x, h, w);
+    const float* d_low = low ? between_nan(low, h / 2, w / 2) : nullptr;
+    float* d_v = b.f32(v_io, v_e);
+    if (d_low) launch_winograd_input_up2(d_x, d_low, d_v, n, h, w, c, s);
+    else launch_winograd_input(d_x, d_v, n, h, w, c, 4, s);
+    OCR_HIP(hipStreamSynchronize(s));
+    OCR_HIP(hipMemcpy(v_io, d_v, v_e * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 }  // extern "C"
 
 // ---- the trunk convs of the bf16 precision: conv3x3_bf16_c64.hip, basic_block_bf16_c64.hip and conv_igemm with bf16 operands ----

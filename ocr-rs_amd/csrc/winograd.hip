@@ -193,6 +193,69 @@ __global__ __launch_bounds__(256) void winograd43_input_kernel(const float* __re
   }
 }
 
+// winograd43_input_kernel with the FPN's top-down add on load: d = up2(low)(y, x) + x(y, x) before bt6, low [N][H/2][W/2][C] (H and W even).
+// The engine runs out4 this way (top_side): in4 stores its plain conv, and the one f32 add that conv_igemm's epilogue
+// made of the same two values (up + v) happens here - the same bits in V.  A tile starts at a multiple of 4, so the low pixel of tap
+// (i, j) is (2 ty - 1 + (i + 1) / 2, 2 tx - 1 + (j + 1) / 2): a 4 x 4 patch of low values per tile, each requested once.  The low tensor has
+// its own descriptor (it, too, starts one row and one pixel before the tensor) and its own out-of-range voffset; with H and W even a low
+// pixel is inside exactly where the taps it covers are, so a tap outside the image is 0 + 0.
+__global__ __launch_bounds__(256) void winograd43_input_up2_kernel(const float* __restrict__ x, const float* __restrict__ low, float* __restrict__ v,
+                                                                   int H, int W, int C, int th, int tw, long long T, unsigned x_bytes,
+                                                                   unsigned low_bytes, unsigned v_bytes) {
+  const int c2n = C >> 1;
+  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= T * c2n) return;
+  const long long t = gid / c2n;
+  const int c = (int)(gid - t * c2n) * 2;
+  const int tx = (int)(t % tw);
+  const long long r = t / tw;
+  const int ty = (int)(r % th);
+  const int n = (int)(r / th);
+  const int Hl = H >> 1, Wl = W >> 1;
+  const unsigned lead = (unsigned)(W + 1) * C * 4, lead_l = (unsigned)(Wl + 1) * C * 4;
+  const auto x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x) - (size_t)(W + 1) * C, 0, x_bytes + lead, 0x00020000);
+  const auto l_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(low) - (size_t)(Wl + 1) * C, 0, low_bytes + lead_l, 0x00020000);
+  const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc(v, 0, v_bytes, 0x00020000);
+  const unsigned voff0 = (unsigned)((((n * H + 4 * ty) * W + 4 * tx) * C + c) * 4);
+  const unsigned voff0_l = (unsigned)((((n * Hl + 2 * ty) * Wl + 2 * tx) * C + c) * 4);
+  bool row_ok[6], col_ok[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    row_ok[i] = (unsigned)(4 * ty - 1 + i) < (unsigned)H;
+    col_ok[i] = (unsigned)(4 * tx - 1 + i) < (unsigned)W;
+  }
+  f32x2 lo[4][4];   // low row li covers the taps i = 2 li - 1, 2 li: inside with tap 2 li (li < 3) / tap 5
+#pragma unroll
+  for (int li = 0; li < 4; ++li)
+#pragma unroll
+    for (int lj = 0; lj < 4; ++lj) {
+      const bool ok = row_ok[li < 3 ? 2 * li : 5] && col_ok[lj < 3 ? 2 * lj : 5];
+      lo[li][lj] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(l_rsrc, ok ? voff0_l : WOOB, (li * Wl + lj) * C * 4, 0));
+    }
+  f32x2 rt[6][6];  // B^T d, column by column
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    f32x2 d[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+      d[i] = lo[(i + 1) >> 1][(j + 1) >> 1] +
+             __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(x_rsrc, (row_ok[i] && col_ok[j]) ? voff0 : WOOB, (i * W + j) * C * 4, 0));
+    f32x2 tcol[6];
+    bt6(d[0], d[1], d[2], d[3], d[4], d[5], tcol);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) rt[i][j] = tcol[i];
+  }
+  const unsigned step = (unsigned)(T * C) * 4u;              // bytes between components (36 x step < 2^31: checked by the launcher)
+  const unsigned voff_v = (unsigned)((t * C + c) * 4);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {  // (B^T d) B
+    f32x2 o[6];
+    bt6(rt[i][0], rt[i][1], rt[i][2], rt[i][3], rt[i][4], rt[i][5], o);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o[j]), v_rsrc, voff_v, (6 * i + j) * step, 0);
+  }
+}
+
 template <typename V>
 __device__ __forceinline__ void at6(const V m0, const V m1, const V m2, const V m3, const V m4, const V m5, V* y) {
   const V s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
@@ -267,6 +330,20 @@ __global__ __launch_bounds__(256) void winograd43_output_kernel(const float* __r
 }
 
 }  // namespace
+
+void launch_winograd_input_up2(const float* x, const float* low, float* v, int N, int H, int W, int C, hipStream_t s) {
+  if (!x || !low || !v || N <= 0 || H <= 0 || W <= 0 || ((H | W) & 1) || C <= 0 || C % 4)
+    fail(OCR_ERR_INVALID, "winograd input + top-down: bad shape N=%d H=%d W=%d C=%d (H and W even, C a multiple of 4)", N, H, W, C);
+  const int th = (H + 3) / 4, tw = (W + 3) / 4;
+  const long long T = (long long)N * th * tw;
+  const long long threads = T * (C / 2);
+  if (threads >= (1ll << 31) * 256) fail(OCR_ERR_INVALID, "winograd input + top-down: too large");
+  const unsigned long long xb = (unsigned long long)N * H * W * C * 4, lb = xb / 4, vb = 36ull * T * C * 4;
+  if (xb + (unsigned long long)(W + 1) * C * 4 >= (1ull << 31) || vb >= (1ull << 31)) fail(OCR_ERR_INVALID, "winograd input + top-down: tensors beyond 2 GB");
+  hipLaunchKernelGGL(winograd43_input_up2_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, x, low, v, H, W, C, th, tw, T, (unsigned)xb,
+                     (unsigned)lb, (unsigned)vb);
+  OCR_HIP(hipGetLastError());
+}
 
 void launch_winograd_input(const float* x, float* v, int N, int H, int W, int C, int m, hipStream_t s) {
   if (N <= 0 || H <= 0 || W <= 0 || C % 4 || (m != 2 && m != 4)) fail(OCR_ERR_INVALID, "winograd input: bad shape N=%d H=%d W=%d C=%d m=%d", N, H, W, C, m);
