@@ -17,6 +17,7 @@
 //                        K = 8 and 32 glyphs would leave one workgroup per CU, the buffer costs one coalesced 128-byte store per rank
 //                        and step.  The end: top_k rounds of a wave argmin over (value, c, r) - lane c offers the head of its list,
 //                        the winner pops it -, then lane k walks hypothesis k back along the links and stores its labels.
+//                        The butterflies, the list insertion and the f64 readlane are word_search.hpp's, shared with lattice.hip.
 // LDS: 16 KB per workgroup.  Registers and scratch: DESIGN.md 3.21 and docs/vmcnt_audit.md.
 #include <cfloat>
 #include <cmath>
@@ -25,15 +26,10 @@
 
 #include "api_internal.hpp"
 #include "char_lm_host.hpp"
+#include "word_search.hpp"
 
 namespace ocr {
 namespace {
-
-__device__ inline double readlane_f64(double x, int l) {   // l is uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-  return __hiloint2double(hi, lo);
-}
 
 template <int K>
 __global__ __launch_bounds__(kLmWords * 64) void lm_decode_kernel(const float* __restrict__ costs, const int32_t* __restrict__ word_off,
@@ -62,15 +58,7 @@ __global__ __launch_bounds__(kLmWords * 64) void lm_decode_kernel(const float* _
         bad |= !(v >= 0.0f && v <= FLT_MAX);   // NaN, +-inf or negative
       }
       int c = lane;
-#pragma unroll
-      for (int k = 32; k > 0; k >>= 1) {   // the first minimum: by (cost, class)
-        const float ov = __shfl_xor(v, k, 64);
-        const int oc = __shfl_xor(c, k, 64);
-        if (ov < v || (ov == v && oc < c)) {
-          v = ov;
-          c = oc;
-        }
-      }
+      wave_argmin(v, c);   // the first minimum: by (cost, class)
       acc = acc + (double)T[prev][c];
       acc = acc + (double)v;
       prev = c;
@@ -126,20 +114,9 @@ __global__ __launch_bounds__(kLmWords * 64) void lm_decode_kernel(const float* _
         if (r >= top_k) break;                  // uniform
         const double s = readlane_f64(pv[r], p);
         if (s == INFINITY) break;               // uniform: the end of p's list
-        double nv = s + tr;
+        const double nv = s + tr;
         if (!__any(cls && nv < bv[K - 1])) break;   // uniform: enters no list, and neither does a later rank
-        int nc = p | (r << 6);
-        bool ins = false;
-#pragma unroll
-        for (int t = 0; t < K; ++t) {           // behind its equals; what it displaces moves down
-          ins = ins || nv < bv[t];
-          const double ov = bv[t];
-          const int oc = bc[t];
-          bv[t] = ins ? nv : ov;
-          bc[t] = ins ? nc : oc;
-          nv = ins ? ov : nv;
-          nc = ins ? oc : nc;
-        }
+        list_insert(bv, bc, nv, p | (r << 6));
       }
     }
 #pragma unroll
@@ -156,15 +133,7 @@ __global__ __launch_bounds__(kLmWords * 64) void lm_decode_kernel(const float* _
   for (int k = 0; k < top_k; ++k) {
     double v = bv[0];
     int c = lane;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {   // by (value, class); the rank is the winner's own
-      const double ov = __shfl_xor(v, m, 64);
-      const int oc = __shfl_xor(c, m, 64);
-      if (ov < v || (ov == v && oc < c)) {
-        v = ov;
-        c = oc;
-      }
-    }
+    wave_argmin(v, c);   // by (value, class); the rank is the winner's own
     const int r = __shfl(popped, c, 64);
     if (lane == 0) out_cost[(size_t)w * top_k + k] = v;
     if (lane == k) {

@@ -14,7 +14,7 @@
 //                        A list entry carries the link (p, r) of its A entry; L_e's link adds m: (m - 1) << 9 | r << 6 | p as uint16,
 //                        to a per-call device buffer [piece e - 1][rank][64].  The end is lm_decode_kernel's: top_k rounds of a wave
 //                        argmin over (value, c, r), then lane k walks hypothesis k back and stores class and length at the first
-//                        piece of every segment.
+//                        piece of every segment.  The butterflies, the list insertion and the f64 readlane are word_search.hpp's.
 // LDS: 16 KB per workgroup.  Registers and scratch: DESIGN.md 3.22 and docs/vmcnt_audit.md.
 // Also here: ocr_glyph_spans, the C entry of the host-only span table (lattice_host.cpp).
 #include <cfloat>
@@ -24,35 +24,14 @@
 
 #include "api_internal.hpp"
 #include "lattice_host.hpp"
+#include "word_search.hpp"
 
 namespace ocr {
 namespace {
 
-__device__ inline double lat_readlane_f64(double x, int l) {   // l is uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-  return __hiloint2double(hi, lo);
-}
-
 struct LatSpanCost {
   double v[kLatMaxSpan];
 };
-
-// behind its equals; what it displaces moves down
-template <int K>
-__device__ inline void lat_insert(double (&bv)[K], int (&bc)[K], double nv, int nc) {
-  bool ins = false;
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    ins = ins || nv < bv[t];
-    const double ov = bv[t];
-    const int oc = bc[t];
-    bv[t] = ins ? nv : ov;
-    bc[t] = ins ? nc : oc;
-    nv = ins ? ov : nv;
-    nc = ins ? oc : nc;
-  }
-}
 
 template <int K>
 __global__ __launch_bounds__(kLatWords * 64) void lattice_decode_kernel(const float* __restrict__ costs, const int32_t* __restrict__ span_off,
@@ -89,15 +68,7 @@ __global__ __launch_bounds__(kLatWords * 64) void lattice_decode_kernel(const fl
         }
       }
       int c = lane;
-#pragma unroll
-      for (int k = 32; k > 0; k >>= 1) {   // the first minimum: by (cost, class)
-        const float ov = __shfl_xor(v, k, 64);
-        const int oc = __shfl_xor(c, k, 64);
-        if (ov < v || (ov == v && oc < c)) {
-          v = ov;
-          c = oc;
-        }
-      }
+      wave_argmin(v, c);   // the first minimum: by (cost, class)
       acc = acc + (double)T[prev][c];
       acc = acc + sc.v[0];
       acc = acc + (double)v;
@@ -149,7 +120,7 @@ __global__ __launch_bounds__(kLatWords * 64) void lattice_decode_kernel(const fl
           bv[0] = ins ? nv : bv[0];
           bc[0] = ins ? nc : bc[0];
         } else {
-          lat_insert<K>(bv, bc, nv, nc);
+          list_insert(bv, bc, nv, nc);
         }
       }
     }
@@ -175,7 +146,7 @@ __global__ __launch_bounds__(kLatWords * 64) void lattice_decode_kernel(const fl
     if constexpr (K == 1) {
       // one value per class: no list to leave early, so the loop is branch-free, in groups of 8 whose LDS reads are in flight together
       auto relax = [&](int p) {
-        const double nv = lat_readlane_f64(bv[0], p) + (double)T[p][lane];
+        const double nv = readlane_f64(bv[0], p) + (double)T[p][lane];
         const bool ins = nv < rv[0][0];   // the first minimum: p ascends
         rv[0][0] = ins ? nv : rv[0][0];
         rc[0][0] = ins ? p : rc[0][0];
@@ -193,11 +164,11 @@ __global__ __launch_bounds__(kLatWords * 64) void lattice_decode_kernel(const fl
 #pragma unroll
       for (int r = 0; r < K; ++r) {
         if (r >= top_k) break;                  // uniform
-        const double s = lat_readlane_f64(bv[r], p);
+        const double s = readlane_f64(bv[r], p);
         if (s == INFINITY) break;               // uniform: the end of p's list
         const double nv = s + tr;
         if (!__any(cls && nv < rv[0][K - 1])) break;   // uniform: enters no list, and neither does a later rank
-        lat_insert<K>(rv[0], rc[0], nv, p | (r << 6));
+        list_insert(rv[0], rc[0], nv, p | (r << 6));
       }
     }
   }
@@ -209,15 +180,7 @@ __global__ __launch_bounds__(kLatWords * 64) void lattice_decode_kernel(const fl
   for (int k = 0; k < top_k; ++k) {
     double v = bv[0];
     int c = lane;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {   // by (value, class); the rank is the winner's own
-      const double ov = __shfl_xor(v, m, 64);
-      const int oc = __shfl_xor(c, m, 64);
-      if (ov < v || (ov == v && oc < c)) {
-        v = ov;
-        c = oc;
-      }
-    }
+    wave_argmin(v, c);   // by (value, class); the rank is the winner's own
     const int r = __shfl(popped, c, 64);
     if (lane == 0) out_cost[(size_t)w * top_k + k] = v;
     if (lane == k) {

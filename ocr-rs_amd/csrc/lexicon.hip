@@ -14,8 +14,9 @@
 //                       characters per 32-bit load of the position-major code array, 256 bytes per wave).  Every lane keeps its best K
 //                       (1 or 8) by the key (cost, caller's index); top_k rounds of a workgroup argmin pop the winners into the
 //                       chunk's slots.
-//   lex_merge_kernel    one wave per word: top_k rounds over the slots of all its chunks, each taking the smallest key above the
-//                       previous winner.  The key is a total order, so neither the chunking nor the layout shows in the result.
+//   lex_merge_kernel    one wave per word over the slots of all its chunks (merge_slots of word_search.hpp).
+// The key, the best K, the butterfly, the slot read-back, the staging and the checked row minimum are word_search.hpp's, which states
+// the tie rules; lexicon_lattice.hip and lexicon_phrase.hip use the same functions.
 // LDS: 8 KB table + 384 B of merge slots per workgroup.  Registers and scratch: DESIGN.md 3.19 and docs/vmcnt_audit.md.
 #include <cfloat>
 #include <cmath>
@@ -25,13 +26,13 @@
 #include "api_internal.hpp"
 #include "lexicon_handle.hpp"
 #include "lexicon_host.hpp"
+#include "word_search.hpp"
 
 namespace ocr {
 namespace {
 
 constexpr int kLexRows = 4;            // glyph rows of the DP column per uniform branch
 static_assert(kLexMaxLen % kLexRows == 0, "row groups");
-constexpr int kNoIndex = 0x7FFFFFFF;   // the index of an empty best-k slot: with cost +inf it is behind every entry
 
 __global__ __launch_bounds__(256) void glyph_cost_kernel(const float* __restrict__ logits, int n, float* __restrict__ costs,
                                                          int32_t* __restrict__ bad_row) {
@@ -41,9 +42,7 @@ __global__ __launch_bounds__(256) void glyph_cost_kernel(const float* __restrict
   const bool live = row < n && lane < kLexClasses;
   const float x = live ? logits[(size_t)row * kLexClasses + lane] : -INFINITY;
   if (live && !(fabsf(x) <= FLT_MAX)) atomicMin(bad_row, row);   // NaN or +-inf
-  float m = x;
-#pragma unroll
-  for (int k = 32; k > 0; k >>= 1) m = fmaxf(m, __shfl_xor(m, k, 64));
+  const float m = wave_max(x);
   ex[wave][lane] = live ? exp((double)x - (double)m) : 0.0;
   __syncthreads();
   double sum = 0.0;
@@ -61,20 +60,11 @@ __global__ __launch_bounds__(256) void lex_raw_kernel(const float* __restrict__ 
   double acc = 0.0;
   bool bad = false;
   for (int g = word_off[w]; g < g1; ++g) {
-    float v = INFINITY;
-    if (lane < kLexClasses) {
-      v = costs[(size_t)g * kLexClasses + lane];
-      bad |= !(v >= 0.0f && v <= FLT_MAX);   // NaN, +-inf or negative
-    }
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) v = fminf(v, __shfl_xor(v, k, 64));
-    acc = acc + (double)v;
+    acc = acc + (double)row_min_checked(costs, (size_t)g, lane, bad);
   }
   if (lane == 0) raw[w] = acc;
   if (bad) atomicMin(bad_word, w);
 }
-
-__device__ inline bool key_less(double ca, int ia, double cb, int ib) { return ca < cb || (ca == cb && ia < ib); }
 
 template <int K>
 __global__ __launch_bounds__(kLexChunk) void lex_match_kernel(const float* __restrict__ costs, const LexWordJob* __restrict__ jobs,
@@ -90,25 +80,12 @@ __global__ __launch_bounds__(kLexChunk) void lex_match_kernel(const float* __res
   const int base = job.r0 + (int)blockIdx.y * span * kLexChunk;   // (below n_entries <= 2^22 for every chunk that stays)
   if (base >= job.r1) return;   // the whole workgroup leaves, before any barrier: the merge counts the chunks of a word itself
 
-  for (int t = tid; t < G * 64; t += kLexChunk) {
-    const int i = t >> 6, c = t & 63;
-    float v = 0.0f;
-    if (c < kLexClasses) {
-      const float* row = costs + (size_t)(job.g0 + i) * kLexClasses;
-      v = row[c];
-      if (fold && c < 52) v = fminf(v, row[c < 26 ? c + 26 : c - 26]);
-    }
-    tab[i][c] = v;
-  }
+  stage_cost_rows(tab, costs, job.g0, G, fold, tid, kLexChunk);
   __syncthreads();
 
   double best_c[K];
   int best_i[K];
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    best_c[t] = INFINITY;
-    best_i[t] = kNoIndex;
-  }
+  best_clear(best_c, best_i);
 
   for (int pass = 0; pass < span; ++pass) {
     const int p0 = base + pass * kLexChunk;
@@ -148,18 +125,7 @@ __global__ __launch_bounds__(kLexChunk) void lex_match_kernel(const float* __res
 #pragma unroll
       for (int i = 1; i <= kLexMaxLen; ++i)
         if (i == G) nc = D[i];
-      int ni = index[e];
-#pragma unroll
-      for (int t = 0; t < K; ++t) {   // insertion into the sorted best-k
-        if (key_less(nc, ni, best_c[t], best_i[t])) {
-          const double c = best_c[t];
-          const int x = best_i[t];
-          best_c[t] = nc;
-          best_i[t] = ni;
-          nc = c;
-          ni = x;
-        }
-      }
+      best_insert(best_c, best_i, nc, index[e]);
     }
   }
 
@@ -168,82 +134,26 @@ __global__ __launch_bounds__(kLexChunk) void lex_match_kernel(const float* __res
   for (int r = 0; r < top_k; ++r) {
     double c = best_c[0];
     int x = best_i[0];
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) {
-      const double oc = __shfl_xor(c, k, 64);
-      const int ox = __shfl_xor(x, k, 64);
-      if (key_less(oc, ox, c, x)) {
-        c = oc;
-        x = ox;
-      }
-    }
+    wave_argmin(c, x);
     if (lane == 0) {
       red_c[r][wave] = c;
       red_i[r][wave] = x;
     }
     __syncthreads();   // (a round has slots of its own: one barrier per round)
-    c = red_c[r][0];
-    x = red_i[r][0];
-#pragma unroll
-    for (int v = 1; v < kLexChunk / 64; ++v)
-      if (key_less(red_c[r][v], red_i[r][v], c, x)) {
-        c = red_c[r][v];
-        x = red_i[r][v];
-      }
+    slots_argmin(red_c[r], red_i[r], 1, c, x);
     if (tid == 0) {
       part_cost[slot + r] = c;
       part_idx[slot + r] = x == kNoIndex ? -1 : x;
     }
-    if (x != kNoIndex && best_i[0] == x) {   // the winner's lane pops it: an index is in one lane only
-#pragma unroll
-      for (int t = 0; t + 1 < K; ++t) {
-        best_c[t] = best_c[t + 1];
-        best_i[t] = best_i[t + 1];
-      }
-      best_c[K - 1] = INFINITY;
-      best_i[K - 1] = kNoIndex;
-    }
+    if (x != kNoIndex && best_i[0] == x) best_pop(best_c, best_i);   // the winner's lane pops it: an index is in one lane only
   }
 }
 
 __global__ __launch_bounds__(64) void lex_merge_kernel(const LexWordJob* __restrict__ jobs, int n_chunks, int span, int top_k,
                                                        const double* __restrict__ part_cost, const int32_t* __restrict__ part_idx,
                                                        int32_t* __restrict__ entries, double* __restrict__ out_cost) {
-  const int w = blockIdx.x, lane = threadIdx.x;
-  const LexWordJob job = jobs[w];
-  const int per = span * kLexChunk;
-  const int live = (job.r1 - job.r0 + per - 1) / per;   // the chunks of this word that wrote their slots (at most n_chunks)
-  const int total = live * top_k;
-  const size_t slot = (size_t)w * n_chunks * top_k;
-  double prev_c = -1.0;   // below every key: costs are >= 0
-  int prev_i = -1;
-  for (int r = 0; r < top_k; ++r) {
-    double c = INFINITY;
-    int x = kNoIndex;
-    for (int t = lane; t < total; t += 64) {
-      const double pc = part_cost[slot + t];
-      const int px = part_idx[slot + t];
-      if (px >= 0 && key_less(prev_c, prev_i, pc, px) && key_less(pc, px, c, x)) {
-        c = pc;
-        x = px;
-      }
-    }
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) {
-      const double oc = __shfl_xor(c, k, 64);
-      const int ox = __shfl_xor(x, k, 64);
-      if (key_less(oc, ox, c, x)) {
-        c = oc;
-        x = ox;
-      }
-    }
-    if (lane == 0) {
-      entries[(size_t)w * top_k + r] = x == kNoIndex ? -1 : x;
-      out_cost[(size_t)w * top_k + r] = c;
-    }
-    prev_c = c;
-    prev_i = x;
-  }
+  const LexWordJob job = jobs[blockIdx.x];
+  merge_slots(job.r0, job.r1, n_chunks, span, top_k, part_cost, part_idx, entries, out_cost);
 }
 
 }  // namespace

@@ -11,8 +11,9 @@
 //                             The DP column D[0..G] lives in 33 f64 registers and is updated in place: the old values
 //                             D[i-1..i-4][j-1] are carried in four scalars.  Rows are unrolled in groups of 4 behind one scalar
 //                             test of G, so the up to 16 LDS reads of a group are in flight together.  Per-lane best K (1 or 8) by
-//                             (cost, caller's index), then top_k rounds of a workgroup argmin into the chunk's slots.
-//   lexlat_merge_kernel       lex_merge_kernel's scheme, a copy of its own: one wave per word over the slots of its chunks.
+//                             (cost, caller's index), then top_k rounds of a workgroup argmin into the chunk's slots: the functions
+//                             lex_match_kernel calls (word_search.hpp, which states the tie rules).
+//   lexlat_merge_kernel       one wave per word over the slots of its chunks (merge_slots of word_search.hpp, as lex_merge_kernel).
 //   lexlat_trace_kernel       one wave per returned (word, rank): finds the entry's sorted position (lane L searches the bucket of
 //                             length L for the caller's index, which ascends inside a bucket), stages the word's span rows, builds the
 //                             full table in LDS along anti-diagonals with row i in lane i, and lane 0 walks it back by the rule's
@@ -28,13 +29,13 @@
 #include "api_internal.hpp"
 #include "lexicon_handle.hpp"
 #include "lexicon_lattice_host.hpp"
+#include "word_search.hpp"
 
 namespace ocr {
 namespace {
 
 constexpr int kRowsPerBranch = 4;     // piece rows of the DP column per uniform branch
 static_assert(kLexMaxLen % kRowsPerBranch == 0, "row groups");
-constexpr int kNoIndex = 0x7FFFFFFF;  // the index of an empty best-k slot: with cost +inf it is behind every entry
 
 struct LexLatSpanCost {
   double v[kLatMaxSpan];
@@ -42,23 +43,6 @@ struct LexLatSpanCost {
 
 // the spans of a word's first e pieces: sum over e' = 1..e of min(M, e') (lat_span_count, for the device)
 __host__ __device__ constexpr int lexlat_rows(int e, int M) { return e <= M ? e * (e + 1) / 2 : M * (M + 1) / 2 + (e - M) * M; }
-
-__device__ inline bool key_less(double ca, int ia, double cb, int ib) { return ca < cb || (ca == cb && ia < ib); }
-
-// the span rows [s0, s0 + rows) of a word -> tab, rows of 64 floats, folded when fold is set
-__device__ inline void lexlat_stage(float (*tab)[64], const float* __restrict__ costs, int s0, int rows, int fold, int tid, int threads) {
-  rows = rows < kLexLatMaxRows ? rows : kLexLatMaxRows;
-  for (int t = tid; t < rows * 64; t += threads) {
-    const int i = t >> 6, c = t & 63;
-    float v = 0.0f;
-    if (c < kLexClasses) {
-      const float* row = costs + (size_t)(s0 + i) * kLexClasses;
-      v = row[c];
-      if (fold && c < 52) v = fminf(v, row[c < 26 ? c + 26 : c - 26]);
-    }
-    tab[i][c] = v;
-  }
-}
 
 __global__ __launch_bounds__(256) void lexlat_raw_kernel(const float* __restrict__ costs, const int32_t* __restrict__ span_off,
                                                          const int32_t* __restrict__ piece_off, int n_words, int M, LexLatSpanCost sc,
@@ -76,13 +60,7 @@ __global__ __launch_bounds__(256) void lexlat_raw_kernel(const float* __restrict
 #pragma unroll
     for (int m = 1; m <= kLatMaxSpan; ++m) {
       if (m <= ms) {   // uniform
-        float v = INFINITY;
-        if (lane < kLexClasses) {
-          v = costs[(row + (m - 1)) * kLexClasses + lane];
-          bad |= !(v >= 0.0f && v <= FLT_MAX);   // NaN, +-inf or negative
-        }
-#pragma unroll
-        for (int k = 32; k > 0; k >>= 1) v = fminf(v, __shfl_xor(v, k, 64));
+        const float v = row_min_checked(costs, row + (m - 1), lane, bad);
         const double f = m == 1 ? f1 : m == 2 ? f2 : m == 3 ? f3 : f4;
         best = fmin(best, (f + sc.v[m - 1]) + (double)v);
       }
@@ -113,16 +91,12 @@ __global__ __launch_bounds__(kLexChunk) void lexlat_match_kernel(const float* __
   const int base = job.r0 + (int)blockIdx.y * span * kLexChunk;   // (below n_entries <= 2^22 for every chunk that stays)
   if (base >= job.r1) return;   // the whole workgroup leaves, before any barrier: the merge counts the chunks of a word itself
                                 // (a word with a flag has r0 == r1, so 1 <= G <= 32 from here on)
-  lexlat_stage(tab, costs, job.s0, lexlat_rows(G, MS), fold, tid, kLexChunk);
+  stage_cost_rows(tab, costs, job.s0, min(lexlat_rows(G, MS), kLexLatMaxRows), fold, tid, kLexChunk);   // (the word's span rows)
   __syncthreads();
 
   double best_c[K];
   int best_i[K];
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    best_c[t] = INFINITY;
-    best_i[t] = kNoIndex;
-  }
+  best_clear(best_c, best_i);
 
   for (int pass = 0; pass < span; ++pass) {
     const int p0 = base + pass * kLexChunk;
@@ -169,18 +143,7 @@ __global__ __launch_bounds__(kLexChunk) void lexlat_match_kernel(const float* __
 #pragma unroll
       for (int i = 1; i <= kLexMaxLen; ++i)
         if (i == G) nc = D[i];
-      int ni = index[e];
-#pragma unroll
-      for (int t = 0; t < K; ++t) {   // insertion into the sorted best-k
-        if (key_less(nc, ni, best_c[t], best_i[t])) {
-          const double c = best_c[t];
-          const int x = best_i[t];
-          best_c[t] = nc;
-          best_i[t] = ni;
-          nc = c;
-          ni = x;
-        }
-      }
+      best_insert(best_c, best_i, nc, index[e]);
     }
   }
 
@@ -189,82 +152,26 @@ __global__ __launch_bounds__(kLexChunk) void lexlat_match_kernel(const float* __
   for (int r = 0; r < top_k; ++r) {
     double c = best_c[0];
     int x = best_i[0];
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) {
-      const double oc = __shfl_xor(c, k, 64);
-      const int ox = __shfl_xor(x, k, 64);
-      if (key_less(oc, ox, c, x)) {
-        c = oc;
-        x = ox;
-      }
-    }
+    wave_argmin(c, x);
     if (lane == 0) {
       red_c[r][wave] = c;
       red_i[r][wave] = x;
     }
     __syncthreads();   // (a round has slots of its own: one barrier per round)
-    c = red_c[r][0];
-    x = red_i[r][0];
-#pragma unroll
-    for (int v = 1; v < kLexChunk / 64; ++v)
-      if (key_less(red_c[r][v], red_i[r][v], c, x)) {
-        c = red_c[r][v];
-        x = red_i[r][v];
-      }
+    slots_argmin(red_c[r], red_i[r], 1, c, x);
     if (tid == 0) {
       part_cost[slot + r] = c;
       part_idx[slot + r] = x == kNoIndex ? -1 : x;
     }
-    if (x != kNoIndex && best_i[0] == x) {   // the winner's lane pops it: an index is in one lane only
-#pragma unroll
-      for (int t = 0; t + 1 < K; ++t) {
-        best_c[t] = best_c[t + 1];
-        best_i[t] = best_i[t + 1];
-      }
-      best_c[K - 1] = INFINITY;
-      best_i[K - 1] = kNoIndex;
-    }
+    if (x != kNoIndex && best_i[0] == x) best_pop(best_c, best_i);   // the winner's lane pops it: an index is in one lane only
   }
 }
 
 __global__ __launch_bounds__(64) void lexlat_merge_kernel(const LexLatJob* __restrict__ jobs, int n_chunks, int span, int top_k,
                                                           const double* __restrict__ part_cost, const int32_t* __restrict__ part_idx,
                                                           int32_t* __restrict__ entries, double* __restrict__ out_cost) {
-  const int w = blockIdx.x, lane = threadIdx.x;
-  const LexLatJob job = jobs[w];
-  const int per = span * kLexChunk;
-  const int live = (job.r1 - job.r0 + per - 1) / per;   // the chunks of this word that wrote their slots (at most n_chunks)
-  const int total = live * top_k;
-  const size_t slot = (size_t)w * n_chunks * top_k;
-  double prev_c = -1.0;   // below every key: costs are >= 0
-  int prev_i = -1;
-  for (int r = 0; r < top_k; ++r) {
-    double c = INFINITY;
-    int x = kNoIndex;
-    for (int t = lane; t < total; t += 64) {
-      const double pc = part_cost[slot + t];
-      const int px = part_idx[slot + t];
-      if (px >= 0 && key_less(prev_c, prev_i, pc, px) && key_less(pc, px, c, x)) {
-        c = pc;
-        x = px;
-      }
-    }
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) {
-      const double oc = __shfl_xor(c, k, 64);
-      const int ox = __shfl_xor(x, k, 64);
-      if (key_less(oc, ox, c, x)) {
-        c = oc;
-        x = ox;
-      }
-    }
-    if (lane == 0) {
-      entries[(size_t)w * top_k + r] = x == kNoIndex ? -1 : x;
-      out_cost[(size_t)w * top_k + r] = c;
-    }
-    prev_c = c;
-    prev_i = x;
-  }
+  const LexLatJob job = jobs[blockIdx.x];
+  merge_slots(job.r0, job.r1, n_chunks, span, top_k, part_cost, part_idx, entries, out_cost);
 }
 
 __global__ __launch_bounds__(64) void lexlat_trace_kernel(const float* __restrict__ costs, const LexLatJob* __restrict__ jobs,
@@ -302,7 +209,7 @@ __global__ __launch_bounds__(64) void lexlat_trace_kernel(const float* __restric
   int L = lens[p];
   L = L < kLexMaxLen ? L : kLexMaxLen;
   if (lane < L) cls[lane] = (int)((codes[(size_t)(lane >> 2) * n_entries + p] >> (8 * (lane & 3))) & 0x3F);
-  lexlat_stage(tab, costs, job.s0, lexlat_rows(G, M), fold, lane, 64);
+  stage_cost_rows(tab, costs, job.s0, min(lexlat_rows(G, M), kLexLatMaxRows), fold, lane, 64);
   __syncthreads();
 
   // the full table, anti-diagonal t = i + j per step, row i in lane i

@@ -9,7 +9,8 @@
 //                        reads tab[s + k][c_k] for its character k and every start s: 32 f64 accumulators, the starts unrolled in
 //                        groups of 4 behind one scalar test, their LDS reads in flight together.  A workgroup makes `span` passes of
 //                        256 entries; every lane keeps its best (cost, caller's index) per start.  The 32 minima of a wave come from
-//                        32 butterflies by (cost, index), the waves meet in LDS, and the chunk's 32 slots are written.
+//                        32 butterflies by (cost, index), the waves meet in LDS, and the chunk's 32 slots are written (key_less,
+//                        wave_argmin and slots_argmin of word_search.hpp, which states the tie rules).
 //   phrase_seg_kernel    one thread per (start, M): L(i, M) as the minimum over the chunks of length M by (cost, index) - a total
 //                        order, so the chunking does not show -, U and J summed in the association of the rule, T for both kinds.
 //   phrase_dp_kernel     one wave per line, lane = kind * 32 + (M - 1): B and the boundary costs in LDS, the segment costs of eight
@@ -25,6 +26,7 @@
 #include "api_internal.hpp"
 #include "lexicon_handle.hpp"
 #include "lexicon_host.hpp"
+#include "word_search.hpp"
 
 namespace ocr {
 namespace {
@@ -35,7 +37,6 @@ constexpr int kPhraseRows = 4;                 // starts per uniform branch
 constexpr int kPhraseGroupWindows = 2048;      // windows per group of lines: bounds the workspace
 constexpr int kPhraseMaxChunks = 64;           // chunks the lexicon is cut into: at most one more per length than kPhraseMaxChunks / 2
 constexpr int kPhraseAhead = 8;                // DP steps whose segment costs are loaded together
-constexpr int kNoIndex = 0x7FFFFFFF;           // the index of an empty slot: with cost +inf it is behind every entry
 static_assert(kPhraseStarts == kLexMaxLen && kPhraseStarts % kPhraseRows == 0, "a window has one start per length, in whole groups");
 static_assert(kPhraseMaxGlyphs % kPhraseStarts == 0, "whole windows");
 
@@ -49,8 +50,6 @@ struct PhraseLine {     // the DP kernel's job: glyph rows [g0, g0 + G), the lin
   int32_t g0, G, win0, line;
 };
 
-__device__ inline bool key_less(double ca, int ia, double cb, int ib) { return ca < cb || (ca == cb && ia < ib); }
-
 __global__ __launch_bounds__(256) void phrase_raw_kernel(const float* __restrict__ costs, const int32_t* __restrict__ line_off, int n_lines,
                                                          double* __restrict__ raw, double* __restrict__ raw_line, int32_t* __restrict__ bad_line) {
   const int lane = threadIdx.x & 63;
@@ -60,13 +59,7 @@ __global__ __launch_bounds__(256) void phrase_raw_kernel(const float* __restrict
   double acc = 0.0;
   bool bad = false;
   for (int g = line_off[l]; g < g1; ++g) {
-    float v = INFINITY;
-    if (lane < kLexClasses) {
-      v = costs[(size_t)g * kLexClasses + lane];
-      bad |= !(v >= 0.0f && v <= FLT_MAX);   // NaN, +-inf or negative
-    }
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) v = fminf(v, __shfl_xor(v, k, 64));
+    const float v = row_min_checked(costs, (size_t)g, lane, bad);
     acc = acc + (double)v;
     if (lane == 0) raw[g] = (double)v;
   }
@@ -89,16 +82,7 @@ __global__ __launch_bounds__(kLexChunk) void phrase_match_kernel(const float* __
   if (n_start <= 0) return;   // the whole workgroup leaves, before any barrier: phrase_seg_kernel reads no slot of such a pair
 
   const int n_rows = min(2 * kPhraseStarts - 1, left);
-  for (int t = tid; t < n_rows * 64; t += kLexChunk) {
-    const int i = t >> 6, c = t & 63;
-    float v = 0.0f;
-    if (c < kLexClasses) {
-      const float* row = costs + (size_t)(win.g0 + win.i0 + i) * kLexClasses;
-      v = row[c];
-      if (fold && c < 52) v = fminf(v, row[c < 26 ? c + 26 : c - 26]);
-    }
-    tab[i][c] = v;
-  }
+  stage_cost_rows(tab, costs, win.g0 + win.i0, n_rows, fold, tid, kLexChunk);
   __syncthreads();
 
   double best_c[kPhraseStarts];
@@ -144,18 +128,10 @@ __global__ __launch_bounds__(kLexChunk) void phrase_match_kernel(const float* __
 
   const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
-  for (int s = 0; s < kPhraseStarts; ++s) {   // the wave's minimum of every start: a butterfly by (cost, index), as in lex_match_kernel
+  for (int s = 0; s < kPhraseStarts; ++s) {   // the wave's minimum of every start: a butterfly by (cost, index)
     double c = best_c[s];
     int x = best_i[s];
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) {
-      const double oc = __shfl_xor(c, k, 64);
-      const int ox = __shfl_xor(x, k, 64);
-      if (key_less(oc, ox, c, x)) {
-        c = oc;
-        x = ox;
-      }
-    }
+    wave_argmin(c, x);
     if (lane == 0) {
       red_c[wave][s] = c;
       red_i[wave][s] = x;
@@ -163,14 +139,9 @@ __global__ __launch_bounds__(kLexChunk) void phrase_match_kernel(const float* __
   }
   __syncthreads();
   if (tid < n_start) {
-    double c = red_c[0][tid];
-    int x = red_i[0][tid];
-#pragma unroll
-    for (int v = 1; v < kLexChunk / 64; ++v)
-      if (key_less(red_c[v][tid], red_i[v][tid], c, x)) {
-        c = red_c[v][tid];
-        x = red_i[v][tid];
-      }
+    double c;
+    int x;
+    slots_argmin(&red_c[0][tid], &red_i[0][tid], kPhraseStarts, c, x);
     const size_t slot = ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * kPhraseStarts + tid;
     part_cost[slot] = c;
     part_idx[slot] = x;
@@ -247,15 +218,7 @@ __global__ __launch_bounds__(64) void phrase_dp_kernel(const PhraseLine* __restr
         double v = INFINITY;
         if (i >= 0) v = (B[i] + bnd[i]) + t[a];
         int x = lane;
-#pragma unroll
-        for (int k = 32; k > 0; k >>= 1) {
-          const double ov = __shfl_xor(v, k, 64);
-          const int ox = __shfl_xor(x, k, 64);
-          if (key_less(ov, ox, v, x)) {
-            v = ov;
-            x = ox;
-          }
-        }
+        wave_argmin(v, x);
         if (lane == 0) {
           B[j] = v;
           choice[j] = (uint8_t)x;

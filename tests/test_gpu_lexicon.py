@@ -117,6 +117,17 @@ def test_ties_go_to_the_smaller_index(rec):
     assert want["ties"] > 0
 
 
+@pytest.mark.parametrize("top_k", [1, 8])
+def test_equal_costs_in_every_wave_of_three_chunks_go_to_the_smaller_index(rec, top_k):
+    """One word of 3 glyphs whose cost rows are constant against 600 distinct entries of 3 characters (behind four of other lengths):
+    every one of them costs the same, in all four waves of three chunks, so the wave's butterfly, the read-back of the waves' slots
+    and the merge over the chunks all see equal costs and the index alone decides."""
+    words = ["a", "bc", "defg", "hijkl"] + ["".join(LX.ALPHABET[37 * n // d % 62] for d in (3844, 62, 1)) for n in range(600)]
+    assert len(set(words)) == 604
+    got, want = _check(rec, np.full((3, 62), 1.5, np.float32), [0, 3], words, dict(top_k=top_k))
+    assert want["n_candidates"].tolist() == [604] and got.entries.tolist() == [list(range(4, 4 + top_k))] and np.all(got.costs == 4.5)
+
+
 def test_layout_independence(rec):
     """The same lexicon permuted: the same costs, and the same entries through the permutation (no cost ties, so the index decides
     nothing)."""

@@ -173,6 +173,20 @@ def test_rank_ties_and_trace_ties_go_by_the_written_order(rec):
     assert want["trace_ties"] == 1 and got.seg_len.tolist() == [[-1, 1]] and got.seg_char.tolist() == [[-1, 0]] and got.costs.tolist() == [[4.0]]
 
 
+@pytest.mark.parametrize("top_k", [1, 8])
+def test_equal_costs_in_every_wave_of_three_chunks_go_to_the_smaller_index(rec, top_k):
+    """One word of 3 pieces whose span rows are constant against 600 distinct entries of 3 characters (behind four of other lengths):
+    every one of them costs the same, in all four waves of three chunks, so the wave's butterfly, the read-back of the waves' slots
+    and the merge over the chunks all see equal costs and the index alone decides."""
+    words = ["a", "defg", "hijkl", "mnop"] + ["".join(LX.ALPHABET[37 * n // d % 62] for d in (3844, 62, 1)) for n in range(600)]
+    assert len(set(words)) == 604   # (none of 2 characters: it would read two of the pieces as one and be cheaper)
+    po = O.offsets([3])
+    so = O.span_offsets(po, 2)
+    got, want = _check(rec, np.full((int(so[-1]), 62), 1.5, np.float32), so, po, words, max_span=2, top_k=top_k)
+    assert want["n_candidates"].tolist() == [604] and got.entries.tolist() == [list(range(4, 4 + top_k))] and np.all(got.costs == 4.5)
+    assert np.all(got.seg_len == 1) and got.seg_char.tolist() == [[0, 1, 2]] * top_k
+
+
 def test_hand_cases(rec):
     res = {}
     for name, (cost, so, po, words, prm) in O.hand_cases().items():

@@ -154,6 +154,18 @@ def test_lexicon_sizes_at_pass_and_chunk_edges(rec, n):
             _check(rec, lex, mixed, _case(25, mixed, [9, 65], gaps=True), device=True)
 
 
+def test_equal_costs_in_every_wave_of_three_chunks_go_to_the_smaller_index(rec):
+    """One line of 3 glyphs whose cost rows are constant against 600 distinct entries of 3 characters (behind four of other lengths):
+    every one of them costs the same, in all four waves of the three chunks of length 3, so the wave's butterflies, the read-back of
+    the waves' slots and the minimum over the chunks all see equal costs and the index alone decides."""
+    from ocr_rs_amd import capi
+    words = ["a", "bc", "defg", "hijkl"] + ["".join(LX.ALPHABET[37 * n // d % 62] for d in (3844, 62, 1)) for n in range(600)]
+    assert len(set(words)) == 604
+    with capi.Lexicon(rec, words) as lex:
+        got = _check(rec, lex, words, (np.full((3, 62), 0.5, np.float32), np.array([0, 3], np.int32), None, None))
+    assert got.entries.tolist() == [4] and got.word_offsets.tolist() == [0, 3] and got.line_costs.tolist() == [2.5]
+
+
 @pytest.mark.parametrize("name,lens", [("all lengths", list(range(1, 33))), ("missing lengths", [2, 5, 9, 32]), ("one length", [4]),
                                         ("long only", [31, 32])])
 def test_lexicon_length_sets(rec, name, lens):
