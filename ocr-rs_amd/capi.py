@@ -544,6 +544,8 @@ def test_lib() -> C.CDLL:
                                             [C.c_void_p, C.c_int])
         L.ocr_test_bf16_trunk_run.argtypes = ([C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] +
                                               [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 2 + [C.c_int])
+        L.ocr_test_igemm_run.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4 +
+                                         [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int])
         _test_lib = L
     return _test_lib
 
@@ -2337,6 +2339,47 @@ class Detector:
                                                  int(guard)))
         outs = [None if a is None else a[:px].reshape(-1, ho, wo, cout) for a in (io, io2)]
         return outs[0], outs[1], np.concatenate([a[px:] for a in (io, io2) if a is not None])
+
+    def debug_igemm_run(self, form, x, wgt, out_bf16=False, stride=1, src_mode=0, store_mode=0, scale=None, bias=None, residual=None, up_residual=None,
+                        want_out=True, want_out2=False, relu=False, tile=0, poison=False, guard=64, sentinel=-7.0, claim=None):
+        """One launch_conv_igemm with a SRC_PLAIN (0) / SRC_CAT4 (2) source and a STORE_NHWC (0) / STORE_SHUFFLE2 (1) store on caller data (test
+        hook).  form 0 exact f32, 1 split bf16, 2 bf16 operands; out_bf16: bf16 results and residuals.  x: [N][H][W][Cin], [B][N][H][W][Cin] for the
+        batched GEMM of B problems, or for CAT4 the four levels (p5, p4, p3, p2) of 64 channels; wgt: [Cout][ks ks][Cin] ([B][Cout][1][Cin]).
+        want_out2: the second output, value + nearest_up2(up_residual [N][Ho / 2][Wo / 2][Cout]).  tile: 0 automatic, 1 128 x 128, 2 128 x 64,
+        3 64 x 64, for this launch only.  poison: the regions around the source (and between the levels) inside its allocation hold NaN instead of
+        zeros.  Returns (out or None, out2 or None, guard): f32 arrays [N][Ho][Wo][Cout] ([B][N].. batched; [N][2 Ho][2 Wo][64] shuffled) and the
+        `guard` rows behind every output, one after the other, which went to the device as `sentinel`.  claim: an (N, H, W) handed to the hook
+        instead of x's own, for shapes the launcher refuses by their size alone - nothing is allocated."""
+        f = lambda a, shape=None: None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).reshape(shape or np.shape(a)))
+        wg = f(wgt)
+        batch = wg.shape[0] if wg.ndim == 4 else 1
+        cout, taps, cin = wg.shape[-3:]
+        ks = {1: 1, 9: 3}[taps]
+        if src_mode == 2:
+            levels = [f(a) for a in x]
+            n, h, w, _ = levels[3].shape
+            assert [a.shape for a in levels] == [(n, h >> (3 - l), w >> (3 - l), 64) for l in range(4)], [a.shape for a in levels]
+            xs = np.concatenate([a.reshape(-1) for a in levels])
+        else:
+            xs = f(x)
+            assert xs.ndim == (5 if wg.ndim == 4 else 4) and xs.shape[-1] == cin and (wg.ndim == 3 or xs.shape[0] == batch), (xs.shape, wg.shape)
+            n, h, w = xs.shape[-4:-1]
+        pad = (ks - 1) // 2
+        ho, wo = (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
+        shape = (n, 2 * ho, 2 * wo, 64) if store_mode == 1 else ((batch,) if wg.ndim == 4 else ()) + (n, ho, wo, cout)
+        rows, row = int(np.prod(shape[:-1])), shape[-1]
+        if claim is not None:
+            n, h, w = claim
+            rows = 0
+        io = np.full((rows + guard, row), sentinel, np.float32) if want_out else None
+        io2 = np.full((rows + guard, row), sentinel, np.float32) if want_out2 else None
+        p = lambda a: None if a is None else _ptr(a)
+        ops = [f(scale), f(bias), f(residual), f(up_residual)]
+        check(test_lib().ocr_test_igemm_run(self._h, int(form), int(bool(out_bf16)), _ptr(xs), n, h, w, cin, _ptr(wg), cout, ks, int(stride), int(src_mode),
+                                            int(store_mode), batch, p(ops[0]), p(ops[1]), p(ops[2]), p(ops[3]), int(bool(relu)), int(tile), int(bool(poison)),
+                                            p(io), p(io2), int(guard)))
+        outs = [None if a is None else a[:rows].reshape(shape) for a in (io, io2)]
+        return outs[0], outs[1], np.concatenate([a[rows:] for a in (io, io2) if a is not None])
 
     def debug_box_scores(self, pred_hw: np.ndarray, polys):
         """Test hook: raw (sum, count) of the GPU box-score kernel for given polygons."""

@@ -100,7 +100,7 @@ std::vector<uint16_t> split3_weights(const float* w, size_t count);
 // ordered [row / 16][K-step][plane]: `wrow` = weights per row (taps x Cin), rows a multiple of 16
 std::vector<uint16_t> split3_weights_tiled(const float* w, size_t count, int wrow);
 const char* conv_igemm_kernel_name(const ConvDesc& d);
-void set_conv_tile_override(int t);  // tuning aid: 0 = automatic
+int set_conv_tile_override(int t);   // tuning aid: 0 = automatic; returns the value it replaces
 void set_conv_debug(int d);          // ablation bits, effective in -DIGEMM_DEBUG builds only
 
 // stem: conv7x7 s2 p3 (Cin=1) + BN + ReLU + maxpool3x3 s2 p1 -> NHWC 64 channels at H/4

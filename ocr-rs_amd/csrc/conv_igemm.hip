@@ -1355,6 +1355,21 @@ static void check(const ConvDesc& d) {
   const long long in_bytes = d.src_mode == SRC_CAT4 ? (long long)d.src_bytes : (long long)nb * d.N * d.Hin * d.Win * d.Cin * eb;
   if (in_bytes >= (1ll << 31) || (long long)d.src_bytes >= (1ll << 31) || (long long)d.src_bytes < in_bytes)
     fail(OCR_ERR_INVALID, "%s: input of %lld bytes (addressable %zu) must be < 2^31 bytes; split the batch", d.name, in_bytes, d.src_bytes);
+  // ... and what an epilogue can address.  f32 NHWC results without out2 (epilogue A, the batched GEMM included) are stored relative to each
+  // wave's corner, found by a 64-bit element index, and the general form of epilogue B indexes with size_t: no bound of their own.  bf16 NHWC
+  // results without out2 (epilogue B's buffer form) take 32-bit BYTE offsets row * Cout * 2 + column for every row of the last tile, and
+  // the rows beyond M must land beyond the descriptor's range M * Cout * 2, itself an unsigned, not wrap: the last tile must end below 2^32
+  // bytes; the pixel-shuffle store and the top-down sum keep an
+  // int ELEMENT index per row (row_aux: of the shuffled output, of up_residual's pixel)
+  if (!phase2) {
+    const long long M = (long long)d.N * d.Ho * d.Wo;
+    const bool beyond = d.store_mode == STORE_SHUFFLE2 ? M * d.Cout >= (1ll << 31)
+                        : d.out2                       ? (M / 4) * d.Cout >= (1ll << 31)
+                                                       : d.out_bf16 && (M + 127) / 128 * 128 * d.Cout * 2 >= (1ll << 32);
+    if (beyond)
+      fail(OCR_ERR_INVALID, "%s: output of %lld bytes is more than the epilogue's 32-bit offsets address; split the batch", d.name,
+           M * d.Cout * (d.out_bf16 ? 2 : 4));
+  }
   if ((long long)d.wgt_bytes != (long long)(phase2 ? d.up * d.up : nb) * d.Cout * d.ks * d.ks * d.Cin * ebw) fail(OCR_ERR_INVALID, "%s: weight bytes", d.name);
   if ((long long)d.wgt_bytes >= (1ll << 31)) fail(OCR_ERR_INVALID, "%s: weights too large", d.name);
   if (d.src_mode != SRC_PLAIN && d.src_mode != SRC_CAT4) fail(OCR_ERR_INVALID, "%s: source mode %d", d.name, d.src_mode);
@@ -1368,7 +1383,7 @@ static void check(const ConvDesc& d) {
         fail(OCR_ERR_INVALID, "%s: CAT4 source %d lies outside the shared allocation", d.name, i);
     }
   }
-  if (d.store_mode == STORE_SHUFFLE2 && (d.Cout != 256 || d.ks != 1 || d.residual || d.out2 || d.in_bf16 || d.out_bf16))
+  if (d.store_mode == STORE_SHUFFLE2 && (d.Cout != 256 || d.ks != 1 || d.stride != 1 || d.residual || d.out2 || d.in_bf16 || d.out_bf16))
     fail(OCR_ERR_INVALID, "%s: SHUFFLE2 store needs a plain f32 1x1 conv with Cout 4*64", d.name);
   if (d.out2 && (!d.up_residual || ((d.Ho | d.Wo) & 1))) fail(OCR_ERR_INVALID, "%s: out2 needs up_residual and an even grid", d.name);
   if (!d.src[0] || !d.wgt || (!d.out && !d.out2)) fail(OCR_ERR_INVALID, "%s: null operand", d.name);
@@ -1386,7 +1401,11 @@ static void check(const ConvDesc& d) {
 // 128x64 otherwise.
 enum Tile { T128x128, T128x64, T64x64 };
 static int g_tile_override = 0;  // tuning aid (ocr_test_set_conv_tile): 1 = 128x128, 2 = 128x64, 3 = 64x64
-void set_conv_tile_override(int t) { g_tile_override = t; }
+int set_conv_tile_override(int t) {
+  const int before = g_tile_override;
+  g_tile_override = t;
+  return before;
+}
 static Tile pick_tile(const ConvDesc& d) {
   if (d.x3) {  // the split-bf16 kernels exist as 128 x 128 and 128 x 64 only
     const long long M = (long long)d.N * d.Ho * d.Wo;

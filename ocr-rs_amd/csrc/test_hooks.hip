@@ -1537,3 +1537,116 @@ int ocr_test_bf16_trunk_run(ocr_det_t* det, int form, const float* x, int n, int
 }
 
 }  // extern "C"
+
+// ---- conv_igemm's plain, concat and shuffle forms: SRC_PLAIN / SRC_CAT4 sources with STORE_NHWC / STORE_SHUFFLE2 stores ----
+namespace {
+// the tile override for one launch: put back on every way out
+struct TileOverride {
+  int before;
+  explicit TileOverride(int t) : before(ocr::set_conv_tile_override(t)) {}
+  ~TileOverride() { ocr::set_conv_tile_override(before); }
+};
+}  // namespace
+
+extern "C" {
+
+// one launch_conv_igemm on caller data with the descriptor the engine builds.  form: 0 exact f32, 1 split bf16 (weights through
+// split3_weights_tiled with rows of ks ks cin), 2 bf16 operands (x and the weights rounded on the way in); out_bf16: bf16 results, residual and
+// up_residual.  src_mode SRC_PLAIN: x [batch][n][h][w][cin]; SRC_CAT4: the levels p5 (h / 8), p4 (h / 4), p3 (h / 2), p2 (h) one after the other,
+// 64 channels each.  wgt [batch][cout][ks ks][cin]; store_mode STORE_NHWC: results [batch][n ho wo][cout]; STORE_SHUFFLE2: [n][2 ho][2 wo][64].
+// out_io / out2_io (either may be null): the result and, behind it, guard_rows rows of its row length, f32 on the host: uploaded before the
+// launch and downloaded whole after it.  residual [n ho wo][cout], up_residual [n][ho / 2][wo / 2][cout] are buffers of their own.  tile: 0 =
+// pick_tile's choice, 1 = 128 x 128, 2 = 128 x 64, 3 = 64 x 64, for this launch only.  The source sits inside one allocation with a lead of at
+// least (w + 1) cin elements in front of it and behind it which src_bytes does not cover; the four levels of CAT4 sit in one allocation with
+// such a region in front of, between and behind them, all of it inside src_bytes - zeros, or with poison != 0 quiet NaN.  Which combinations
+// exist is conv_igemm.hip's check(): its refusals come back as errors.  A source or a result of 2^31 bytes or more is handed to the launcher
+// before anything is read or allocated, without operands: it must refuse by the shape
+int ocr_test_igemm_run(ocr_det_t* det, int form, int out_bf16, const float* x, int n, int h, int w, int cin, const float* wgt, int cout, int ks, int stride,
+                       int src_mode, int store_mode, int batch, const float* scale, const float* bias, const float* residual, const float* up_residual,
+                       int relu, int tile, int poison, float* out_io, float* out2_io, int guard_rows) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !x || !wgt) fail(OCR_ERR_INVALID, "null argument");
+    if (form < 0 || form > 2 || n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || guard_rows < 0 || batch < 1 || tile < 0 || tile > 3 ||
+        (ks != 1 && ks != 3) || (stride != 1 && stride != 2) || (src_mode != SRC_PLAIN && src_mode != SRC_CAT4) ||
+        (store_mode != STORE_NHWC && store_mode != STORE_SHUFFLE2))
+      fail(OCR_ERR_INVALID, "igemm hook: bad form, shape, kernel size, stride, mode, batch or tile");
+    if (!out_io && !out2_io) fail(OCR_ERR_INVALID, "igemm hook: no output");
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    const bool in_bf = form == 2, out_bf = out_bf16 != 0, cat4 = src_mode == SRC_CAT4, shuffle = store_mode == STORE_SHUFFLE2;
+    const size_t ies = in_bf ? 2 : 4, oes = out_bf ? 2 : 4;
+    const int pad = (ks - 1) / 2;
+    const int ho = (h + 2 * pad - ks) / stride + 1, wo = (w + 2 * pad - ks) / stride + 1;
+    ConvDesc d{};
+    d.in_bf16 = in_bf ? 1 : 0;
+    d.out_bf16 = out_bf ? 1 : 0;
+    d.x3 = form == 1 ? 1 : 0;
+    d.src_mode = src_mode;
+    d.store_mode = store_mode;
+    d.N = n; d.Hin = h; d.Win = w; d.Cin = cin; d.Ho = ho; d.Wo = wo; d.Cout = cout;
+    d.ks = ks; d.stride = stride; d.pad = pad;
+    d.batch = batch;
+    d.relu = relu ? 1 : 0;
+    d.name = "test_igemm";
+    TileOverride tile_for_this_launch(tile);
+    const size_t w_e = (size_t)batch * cout * ks * ks * cin;
+    const unsigned long long in_bytes = (unsigned long long)batch * n * h * w * cin * ies, res_bytes = (unsigned long long)batch * n * ho * wo * cout * oes;
+    if (in_bytes >= (1ull << 31) || res_bytes >= (1ull << 31)) {
+      d.src_bytes = in_bytes;
+      d.wgt_bytes = w_e * (form == 1 ? 6 : ies);
+      launch_conv_igemm(d, s);
+      fail(OCR_ERR_INTERNAL, "igemm hook: the launcher took a source of %llu and a result of %llu bytes", in_bytes, res_bytes);
+    }
+    HookBuffers b;
+    const float fill = poison ? std::numeric_limits<float>::quiet_NaN() : 0.f;
+    if (cat4) {
+      size_t lv_e[4], lv_at[4], at = 0;
+      auto gap = [&](int lw) { return (((size_t)2 * (lw + 2) * 64 * ies + 4095) / 4096) * 4096; };   // more than two rows of the level behind it
+      for (int l = 0; l < 4; ++l) {
+        lv_e[l] = (size_t)n * (h >> (3 - l)) * (w >> (3 - l)) * 64;
+        at += gap(w >> (3 - l));
+        lv_at[l] = at;
+        at += lv_e[l] * ies;
+      }
+      const size_t total = at + gap(w);
+      std::vector<uint8_t> img(total);
+      fill_elems(img, 0, nullptr, total / ies, in_bf, fill);
+      const float* lv = x;
+      for (int l = 0; l < 4; ++l) {
+        fill_elems(img, lv_at[l], lv, lv_e[l], in_bf, 0.f);
+        lv += lv_e[l];
+      }
+      char* d_src = static_cast<char*>(b.raw(img.data(), img.size()));
+      for (int l = 0; l < 4; ++l) d.src[l] = d_src + lv_at[l];
+      d.src_base = d_src;
+      d.src_bytes = total;
+    } else {
+      const size_t in_e = (size_t)batch * n * h * w * cin;
+      const size_t lead = ((((size_t)(w + 1) * cin * ies) + 4095) / 4096) * 4096;
+      std::vector<uint8_t> img(lead + in_e * ies + lead);
+      fill_elems(img, 0, nullptr, lead / ies, in_bf, fill);
+      fill_elems(img, lead, x, in_e, in_bf, 0.f);
+      fill_elems(img, lead + in_e * ies, nullptr, lead / ies, in_bf, fill);
+      d.src[0] = static_cast<char*>(b.raw(img.data(), img.size())) + lead;
+      d.src_bytes = in_e * ies;
+    }
+    d.wgt = upload_form_weights(b, form, wgt, w_e, ks * ks * cin, &d.wgt_bytes);
+    d.scale = scale ? b.f32(scale, cout) : nullptr;
+    d.bias = bias ? b.f32(bias, cout) : nullptr;
+    const size_t px = (size_t)batch * n * ho * wo;
+    d.residual = residual ? upload_io(b, residual, px * cout, out_bf) : nullptr;
+    d.up_residual = up_residual ? upload_io(b, up_residual, (size_t)n * (ho / 2) * (wo / 2) * cout, out_bf) : nullptr;
+    const size_t rows = shuffle ? 4 * px : px, row_e = shuffle ? 64 : cout, out_e = (rows + guard_rows) * row_e;
+    void* d_out = out_io ? upload_io(b, out_io, out_e, out_bf) : nullptr;
+    void* d_out2 = out2_io ? upload_io(b, out2_io, out_e, out_bf) : nullptr;
+    d.out = d_out;
+    d.out2 = d_out2;
+    launch_conv_igemm(d, s);
+    OCR_HIP(hipStreamSynchronize(s));
+    if (out_io) download_io(out_io, d_out, out_e, out_bf);
+    if (out2_io) download_io(out2_io, d_out2, out_e, out_bf);
+  });
+}
+
+}  // extern "C"

@@ -11,7 +11,8 @@ Per kernel a *Case class im2cols the operands, runs the kernel's epilogue in f32
 output of the same layout (an emulation's or the GPU's) against the same pipeline in f64:
   rms(out) = sqrt(mean(((out - ref) / norm)^2)),  norm = sum |a||b| * |scale| carried through the epilogue.
 `bar(case)` = (rms of six products, smallest rms of five among the drops that change anything, their geometric mean).
-The *_family functions are the inputs of tests/test_gpu_stem_head_kernels.py and tests/test_gpu_phase_kernels.py;
+The *_family functions are the inputs of tests/test_gpu_stem_head_kernels.py, tests/test_gpu_phase_kernels.py and
+tests/test_gpu_igemm_kernels.py;
 tests/test_split_bf16_emul.py and tests/test_phase_conv_oracle.py check on the CPU
 that each of them separates five products from six by at least 5 x."""
 import numpy as np
@@ -229,12 +230,21 @@ class RecCase(_Case):
 
 
 class ConvCase(_Case):
-    """conv_igemm's split-bf16 form through debug_conv_run(variant=2) without epilogue terms: x NHWC, wg [cout][ks*ks][cin],
-    K = tap * cin + ci in groups of 16.  Output [n][ho][wo][cout]."""
-    kgroup = 16
+    """conv_igemm's plain conv (debug_conv_run(variant=2), debug_igemm_run) without epilogue terms: x NHWC, wg [cout][ks*ks][cin],
+    K = tap * cin + ci in groups of `kgroup` - 16, one MFMA, or 32, the kernel's K-step.  Output [n][ho][wo][cout].  x [B][n][h][w][cin]
+    with wg [B][cout][1][cin] is the batched GEMM: B products, each emulated on its own, output [B][n][h][w][cout]."""
 
-    def __init__(self, x, wg, stride):
+    def __init__(self, x, wg, stride, kgroup=16):
         x, wg = np.asarray(x, f32), np.asarray(wg, f32)
+        self.kgroup = kgroup
+        self.batched = x.ndim == 5
+        self.blocks = [self._im2col(xb, wb, stride) for xb, wb in (zip(x, wg) if self.batched else ((x, wg),))]
+        self.A, self.B = self.blocks[0]
+        self.ref = self._place([A.astype(f64) @ B.astype(f64) for A, B in self.blocks], f64)
+        self.mag = self._place([np.abs(A).astype(f64) @ np.abs(B).astype(f64) for A, B in self.blocks], f64)
+        self.norm = self.mag
+
+    def _im2col(self, x, wg, stride):
         n, h, w, cin = x.shape
         cout, kk, _ = wg.shape
         ks = int(round(kk ** 0.5))
@@ -246,14 +256,18 @@ class ConvCase(_Case):
         for t in range(kk):
             ky, kx = divmod(t, ks)
             A[:, :, :, t] = xp[:, ky:ky + stride * (ho - 1) + 1:stride, kx:kx + stride * (wo - 1) + 1:stride]
-        self.A = A.reshape(-1, kk * cin)
-        self.B = np.ascontiguousarray(wg.reshape(cout, kk * cin).T)
         self.shape = (n, ho, wo, cout)
-        self._finish()
-        self.norm = self.mag.reshape(self.shape)
+        return A.reshape(-1, kk * cin), np.ascontiguousarray(wg.reshape(cout, kk * cin).T)
 
-    def epilogue(self, acc, dt):
-        return acc.astype(dt).reshape(self.shape)
+    def _place(self, per_block, dt):
+        out = np.stack([np.asarray(v, dt).reshape(self.shape) for v in per_block])
+        return out if self.batched else out[0]
+
+    def emulated(self, products=PRODUCTS):
+        return self._place([emulate(A, B, products, self.kgroup) for A, B in self.blocks], f32)
+
+    def chain(self):
+        return self._place([f32_chain(A, B) for A, B in self.blocks], f32)
 
 
 class _PhasedCase(_Case):
@@ -368,6 +382,22 @@ def conv_family(case, seed=3):
     rng = np.random.default_rng(seed + cin)
     x = rng.standard_normal((n, h, w, cin)).astype(f32)
     wg = (rng.standard_normal((cout, ks * ks, cin)) / np.sqrt(ks * ks * cin)).astype(f32)
+    return x, wg, stride
+
+
+# (n, h, w, cin, cout, ks, stride, batch): one per (ks, stride), the batched GEMM; K = 32, 64, 576 and 2304
+IGEMM_CASES = ((2, 9, 7, 32, 64, 1, 1, 1), (2, 10, 18, 64, 128, 1, 2, 1), (1, 9, 17, 64, 128, 3, 1, 1), (2, 10, 18, 64, 64, 3, 2, 1),
+               (1, 9, 7, 256, 64, 3, 1, 1), (1, 1, 130, 64, 64, 1, 1, 3))
+
+
+def igemm_family(case, seed=29):
+    """the inputs of tests/test_gpu_igemm_kernels.py (group G5): case = (n, h, w, cin, cout, ks, stride, batch); N(0,1) activations, weights
+    N(0,1) / sqrt(K); batch > 1: the batched GEMM's x [B][n][h][w][cin], wg [B][cout][1][cin]"""
+    n, h, w, cin, cout, ks, stride, batch = case
+    rng = np.random.default_rng(seed + cin + 7 * ks + stride)
+    lead = (batch,) if batch > 1 else ()
+    x = rng.standard_normal(lead + (n, h, w, cin)).astype(f32)
+    wg = (rng.standard_normal(lead + (cout, ks * ks, cin)) / np.sqrt(ks * ks * cin)).astype(f32)
     return x, wg, stride
 
 

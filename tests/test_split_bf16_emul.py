@@ -81,6 +81,13 @@ def test_conv_families_separate_five_products_from_six(case):
     _separated(E.ConvCase(*E.conv_family(case)))
 
 
+@pytest.mark.parametrize("case", E.IGEMM_CASES, ids=str)
+def test_igemm_families_separate_five_products_from_six_at_the_kernels_k_step(case):
+    """the inputs of tests/test_gpu_igemm_kernels.py (G5), K groups of 32 as in conv_igemm's K-step"""
+    x, wg, stride = E.igemm_family(case)
+    _separated(E.ConvCase(x, wg, stride, kgroup=32))
+
+
 def test_rec_pooled_onehot_is_conv1_of_its_weights():
     """The host-side pooled map is what conv1 + bias + 2x2 max pool of the returned weights computes (f64 conv: one non-zero term per sum)."""
     crops, w1, b1, w2, b2, p1 = E.rec_family(3)
