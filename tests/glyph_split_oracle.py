@@ -8,6 +8,9 @@ n = 1: one piece, the box unchanged.  Otherwise cnt[x] = ink of column x over [y
 and cut j is the x in [max(c_j - r, x0 + 1), min(c_j + r, x1 - 1)] that minimises (cnt[x], |x - c_j|, x).  Piece i covers
 [cut_i, cut_(i+1)) with its y range first ink row .. last ink row + 1; a piece without ink is dropped.  A word with more than
 max_word_pieces pieces (after the drops) passes through unsplit and word_info[k][3] gains bit 4.
+
+Cases: drawn_cases and fuzz_case (glyphs up to 60 columns), wide_drawn_cases and wide_fuzz_case (up to 1201 columns, both polarities);
+reach() counts what a case reaches of the sizes at which the kernel's loops over columns take further steps.
 """
 from __future__ import annotations
 
@@ -156,7 +159,10 @@ def drawn_cases():
 def fuzz_case(seed: int = 77):
     """Two 96 x 160 frames of uniform noise (about 40 % of the pixels are ink at t = 120, dark ink), 32 words a frame as rectangles
     of width 3 to 60 (both ends forced) and height 6 to 11, packed first-fit into 8 rows a frame.  The column rule makes nearly every
-    word one glyph as wide as the word, the component rule breaks it into blobs.  -> (frames, polys, adj)"""
+    word one glyph as wide as the word, the component rule breaks it into blobs.  -> (frames, polys, adj)
+    What it does not reach: the widest window is 2 * (60 // 8) + 1 = 15 columns and no piece is 64 columns wide, so neither of the
+    kernel's loops over columns takes a second step of 64; no piece is dropped (at 40 % ink every piece holds some); and every word is
+    polarity 1.  wide_fuzz_case and wide_drawn_cases are there for those; reach() counts what a case reaches."""
     rng = np.random.default_rng(seed)
     frames = rng.uniform(0.0, 300.0, (2, 1, 96, 160)).astype(np.float32)
     polys = []
@@ -171,3 +177,216 @@ def fuzz_case(seed: int = 77):
             used[row] += int(gw) + 2
         polys.append(words)
     return frames, polys, np.ones((2, 2))
+
+
+REACH_KEYS = ("win_gt64", "win_gt128", "cut_ge64", "cut_ge128", "count_ties", "dist_ties", "piece_gt64", "piece_gt128", "dropped", "far_rows")
+
+
+def reach(frames: np.ndarray, glyphs: dict, params=None) -> dict:
+    """What a case reaches, counted from the oracle's own quantities (64 is the kernel's step over columns, one wave):
+      win_gt64, win_gt128      search windows [lo, hi] of more than 64 / 128 columns
+      cut_ge64, cut_ge128      cuts whose index in their window, cut - lo, is >= 64 / >= 128
+      count_ties               cuts whose ink count is held by more than one column of the window
+      dist_ties                of those, cuts whose (count, |x - c|) is held by two columns: the smaller x decided
+      piece_gt64, piece_gt128  pieces [cut_i, cut_(i+1)) of a cut glyph wider than 64 / 128 columns, dropped ones included
+      dropped                  pieces without ink
+      far_rows                 kept pieces wider than 64 whose first or last ink row is not that of their first 64 columns, or whose
+                               first 64 columns hold no ink
+      asked                    {n: glyphs that ask for n pieces}"""
+    p = params_with(params)
+    off = np.asarray(glyphs["word_offsets"], np.int64)
+    info = np.array(glyphs["word_info"], np.int32).reshape(-1, 4)
+    boxes = np.asarray(glyphs["boxes"], np.int32).reshape(-1, 4)
+    out = dict.fromkeys(REACH_KEYS, 0)
+    out["asked"] = {}
+    for k in range(len(off) - 1):
+        g0, g1 = int(off[k]), int(off[k + 1])
+        if g1 == g0:
+            continue
+        fr, t, pol = int(info[k, 0]), int(info[k, 1]), int(info[k, 2])
+        hw = int((boxes[g0:g1, 3] - boxes[g0:g1, 1]).max())
+        for g in range(g0, g1):
+            x0, y0, x1, y1 = (int(v) for v in boxes[g])
+            gw = x1 - x0
+            n = pieces_asked(gw, hw, p)
+            out["asked"][n] = out["asked"].get(n, 0) + 1
+            if n == 1:
+                continue
+            q = GO.quantise(frames[fr, 0, y0:y1, x0:x1])
+            ink = (q <= t) if pol == 1 else (q > t)
+            cnt = ink.sum(axis=0)
+            r = max(1, gw // (4 * n))
+            cuts = cuts_of(cnt, x0, x1, n)
+            for j, cut in zip(range(1, n), cuts):
+                c = x0 + (j * gw) // n
+                lo, hi = max(c - r, x0 + 1), min(c + r, x1 - 1)
+                out["win_gt64"] += hi - lo + 1 > 64
+                out["win_gt128"] += hi - lo + 1 > 128
+                out["cut_ge64"] += cut - lo >= 64
+                out["cut_ge128"] += cut - lo >= 128
+                same = [x for x in range(lo, hi + 1) if cnt[x - x0] == cnt[cut - x0]]
+                out["count_ties"] += len(same) > 1
+                out["dist_ties"] += sum(abs(x - c) == abs(cut - c) for x in same) > 1
+            edges = [x0] + cuts + [x1]
+            for xa, xb in zip(edges, edges[1:]):
+                out["piece_gt64"] += xb - xa > 64
+                out["piece_gt128"] += xb - xa > 128
+                rows = np.nonzero(ink[:, xa - x0:xb - x0].any(axis=1))[0]
+                if len(rows) == 0:
+                    out["dropped"] += 1
+                elif xb - xa > 64:
+                    first = np.nonzero(ink[:, xa - x0:xa - x0 + 64].any(axis=1))[0]
+                    out["far_rows"] += len(first) == 0 or (first[0], first[-1]) != (rows[0], rows[-1])
+    return {k: (v if k == "asked" else int(v)) for k, v in out.items()}
+
+
+def add_reach(a: dict, b: dict) -> dict:
+    """the counters of two cases, added"""
+    out = {k: a[k] + b[k] for k in REACH_KEYS}
+    out["asked"] = {n: a["asked"].get(n, 0) + b["asked"].get(n, 0) for n in sorted(set(a["asked"]) | set(b["asked"]))}
+    return out
+
+
+WIDE_BOX = (10, 2, 610, 14)
+
+
+def _inverted(case):
+    """the same drawing light on dark at polarity 2: 210 <-> 30 (levels mirrored about 120), every expected number unchanged"""
+    name, frames, blk, prm, want, bits = case
+    info = blk["word_info"].copy()
+    info[:, 2] = 2
+    return (name, (PAPER + INK - frames).astype(np.float32), dict(blk, word_info=info), prm, want, bits)
+
+
+def wide_drawn_cases():
+    """-> [(name + "-p1" | "-p2", frames, glyph block, params, expected piece boxes, expected bit 4 per word)]: drawn cases past one
+    wave's 64 columns, each at polarity 1 (dark on light, as drawn below) and as the same drawing inverted at polarity 2; t = 120.
+    All but tall_wide: a 16 x 700 frame per glyph, the glyph [10, 610) x [2, 14) (gw = 600, hw = 12, the rule asks for (120000 + 1200)
+    // 2400 = 50 pieces) and max_pieces = 2: n = 2, r = 600 // 8 = 75, c = 10 + 300 = 310, the window is [235, 385] (151 columns; a lane
+    that starts at 235 + l meets 235 + l, 299 + l, 363 + l: index 64 is column 299, index 128 is column 363).
+      far_min       a solid bar over the glyph with column 380 blank: the only zero count lies in the third step (index 145): the cut
+                    is 380, the pieces [10, 380) and [380, 610), both with all 12 rows.
+      far_tie       frame 0: the bar with columns 250 and 370 blank, both at distance 60 from c, in steps 0 and 2: the smaller x wins,
+                    the cut is 250.  Frame 1: columns 250 and 300 blank: 300 is nearer (10 against 60) and wins although it is the
+                    larger x.
+      far_rows      ink [10, 14) x [6, 9) and [320, 324) x [6, 9), one pixel at (x 200, y 2) and one at (x 290, y 13).  In the window
+                    column 290 counts 1, 320..323 count 3, the rest 0: the cut is c = 310.  Piece 0 = [10, 310) has rows 2 (x 200),
+                    6..8 and 13 (x 290): [10, 2, 310, 14], both extremes beyond its first 64 columns.  Piece 1 = [310, 6, 610, 9].
+      far_only      ink [10, 14) x [6, 9) and one pixel at (x 600, y 7); the window is blank, the cut is 310.  Piece 1 = [310, 610)
+                    holds only that pixel, 290 columns in: [310, 7, 610, 8], kept.
+      far_only3     the same drawing at max_pieces = 3: n = 3, r = 600 // 12 = 50, c = 210 and 410, both windows blank: cuts 210 and
+                    410.  The middle piece [210, 410) has no ink and is dropped: [10, 6, 210, 9] and [410, 7, 610, 8].
+      at_threshold  not an inversion: the two polarities share the drawing and differ in what the levels A = 120.0, B = 120.9 (both
+                    q = 120 = t) and C = 121.0 (q = 121) are.  Rows 6 and 7 are solid ink over [10, 610) (30 at polarity 1, 210 at
+                    polarity 2, the paper the other of the two), except column 305 = A, column 300 = B, column 290 = C in both rows;
+                    single pixels (x 100, y 2) = A, (x 100, y 3) = C, (x 500, y 13) = B, (x 500, y 12) = C.
+                    Polarity 1 (ink is q <= 120: A and B are ink, C is not): column 290 counts 0, every other 2: the cut is 290.
+                    Piece 0 = [10, 290) has rows 2 (A), 6, 7: [10, 2, 290, 8].  Piece 1 has rows 6, 7 and 13 (B): [290, 6, 610, 14].
+                    Polarity 2 (ink is q > 120: C is ink, A and B are not): columns 300 and 305 count 0, 305 is nearer to 310: the cut
+                    is 305.  Piece 0 = [10, 305) has rows 3 (C), 6, 7: [10, 3, 305, 8].  Piece 1 has rows 6, 7 and 12 (C):
+                    [305, 6, 610, 13].  (Were q = t ink at polarity 2 every column would count 2 and the cut would be 310.)
+      tall_wide     a 1006 x 608 frame, one glyph [4, 604) x [3, 1003) (gw = 600, hw = 1000), aspect_pct 25: n = (120000 + 25000) //
+                    50000 = 2, r = 75, c = 304, window [229, 379].  Ink only over the window's columns [229, 380), all 1000 rows, but
+                    for the pixel (x 370, y 500): column 370 counts 999, every other 1000 - four digits in the key's high field -
+                    and the cut is 370 (index 141).  Pieces [4, 3, 370, 1003] and [370, 3, 604, 1003].
+    """
+    two = dict(max_pieces=2)
+    paper = lambda n=1, h=16, w=700: np.full((n, 1, h, w), PAPER, np.float32)
+    x0, y0, x1, y1 = WIDE_BOX
+    one = lambda pol=1: block([0], T_HAND, pol, [[WIDE_BOX]])
+    cases = []
+
+    f = paper()
+    f[0, 0, y0:y1, x0:x1] = INK
+    f[0, 0, :, 380] = PAPER
+    cases.append(("far_min", f, one(), two, [[10, 2, 380, 14], [380, 2, 610, 14]], [0]))
+
+    f = paper(2)
+    f[:, 0, y0:y1, x0:x1] = INK
+    f[0, 0, :, [250, 370]] = PAPER
+    f[1, 0, :, [250, 300]] = PAPER
+    cases.append(("far_tie", f, block([0, 1], T_HAND, 1, [[WIDE_BOX], [WIDE_BOX]]), two,
+                  [[10, 2, 250, 14], [250, 2, 610, 14], [10, 2, 300, 14], [300, 2, 610, 14]], [0, 0]))
+
+    f = paper()
+    f[0, 0, 6:9, 10:14] = INK
+    f[0, 0, 6:9, 320:324] = INK
+    f[0, 0, 2, 200] = INK
+    f[0, 0, 13, 290] = INK
+    cases.append(("far_rows", f, one(), two, [[10, 2, 310, 14], [310, 6, 610, 9]], [0]))
+
+    f = paper()
+    f[0, 0, 6:9, 10:14] = INK
+    f[0, 0, 7, 600] = INK
+    cases.append(("far_only", f, one(), two, [[10, 6, 310, 9], [310, 7, 610, 8]], [0]))
+    cases.append(("far_only3", f, one(), dict(max_pieces=3), [[10, 6, 210, 9], [410, 7, 610, 8]], [0]))
+
+    f = paper(1, 1006, 608)
+    f[0, 0, 3:1003, 229:380] = INK
+    f[0, 0, 500, 370] = PAPER
+    cases.append(("tall_wide", f, block([0], T_HAND, 1, [[(4, 3, 604, 1003)]]), dict(aspect_pct=25),
+                  [[4, 3, 370, 1003], [370, 3, 604, 1003]], [0]))
+
+    out = []
+    for c in cases:
+        out.append((c[0] + "-p1",) + c[1:])
+        out.append((c[0] + "-p2",) + _inverted(c)[1:])
+
+    A, B, Cl = T_HAND + 0.0, T_HAND + 0.9, T_HAND + 1.0
+    for pol, want in ((1, [[10, 2, 290, 8], [290, 6, 610, 14]]), (2, [[10, 3, 305, 8], [305, 6, 610, 13]])):
+        f = np.full((1, 1, 16, 700), PAPER if pol == 1 else INK, np.float32)
+        f[0, 0, 6:8, x0:x1] = INK if pol == 1 else PAPER
+        f[0, 0, 6:8, 305] = A
+        f[0, 0, 6:8, 300] = B
+        f[0, 0, 6:8, 290] = Cl
+        f[0, 0, 2, 100], f[0, 0, 3, 100] = A, Cl
+        f[0, 0, 13, 500], f[0, 0, 12, 500] = B, Cl
+        out.append((f"at_threshold-p{pol}", f, one(pol), two, want, [0]))
+    return out
+
+
+WIDE_H, WIDE_W = 48, 1201
+# the parameter sets of the wide fuzz, on the CPU and on the GPU: max_pieces 1..4, aspect_pct 25 / 100 / 400, min_piece_w 3 / 64, and a
+# max_word_pieces that lets single glyphs through and stops the words of many
+WIDE_PARAMS = (dict(max_pieces=1), dict(max_pieces=2), dict(max_pieces=3), dict(max_pieces=4),
+               dict(max_pieces=2, aspect_pct=25), dict(max_pieces=4, aspect_pct=25), dict(max_pieces=3, aspect_pct=400),
+               dict(max_pieces=4, aspect_pct=400), dict(max_pieces=2, min_piece_w=64), dict(max_pieces=4, aspect_pct=25, min_piece_w=64),
+               dict(max_pieces=4, max_word_pieces=6))
+
+
+def wide_fuzz_case(seed: int = 11, polarity: int = 1):
+    """Two 48 x 1201 frames, eight bands of six rows a frame, a band one word of glyphs side by side (so hw is often a neighbour's
+    height).  Widths 3, 65, 129, 257, 513 and the whole 1201 columns plus random ones up to 1100, heights 3 to 6; the glyphs of width 3
+    ask for one piece whatever the parameters, so waves that return at once share workgroups with waves that cut.  Boxes touch x = 0,
+    x = W, y = 0 and y = H.  Ink is sparse and patchy: a (row, 64-column chunk) cell is blank with probability 1/2 and otherwise 24 %
+    ink, about 12 % overall, so columns without ink are common, pieces lose all their ink, and a piece's first and last ink row often
+    lie past its first 64 columns.  Levels are k + j/10, ink 0..120.9 and paper 121..255.9 at polarity 1, swapped at polarity 2, t = 120:
+    pixels with q = t occur.  -> (frames 2 x 1 x 48 x 1201, glyph block)"""
+    rng = np.random.default_rng([seed, polarity])
+    H, W = WIDE_H, WIDE_W
+    cells = rng.random((2, H, (W + 63) // 64)) < 0.5
+    ink = rng.random((2, H, W)) < np.repeat(cells, 64, axis=2)[:, :, :W] * 0.24
+    low = rng.integers(0, 121, (2, H, W)) + rng.integers(0, 10, (2, H, W)) / 10.0
+    high = rng.integers(121, 256, (2, H, W)) + rng.integers(0, 10, (2, H, W)) / 10.0
+    frames = np.where(ink == (polarity == 1), low, high).astype(np.float32)[:, None]
+    R = lambda a, b: int(rng.integers(a, b + 1))
+    bands = [[[W], [513, 3, 257, 3, 65, 129, 3, R(6, 12)], [R(600, 1100), 3, R(6, 12)], [65, 3, 65, 129, 3, 257, R(3, 60), R(3, 60)],
+              [R(600, 1100)], [R(3, 150) for _ in range(6)], [R(900, 1100), 3], [513, 3, 513]],
+             [[R(600, 1100), 3, 65], [129, 3, R(6, 12), 513, R(6, 12), 257, 3], [R(900, 1100)], [R(3, 150) for _ in range(6)],
+              [257, 3, 129, 65, 3, 513], [R(600, 1100), R(6, 12), 3], [R(3, 300) for _ in range(4)], [W]]]
+    frame_of_word, words = [], []
+    for fr in range(2):
+        for b, widths in enumerate(bands[fr]):
+            gaps = [R(0, 2) for _ in widths]
+            x = 0 if b % 2 == 0 else W - (sum(widths) + sum(gaps[1:]))     # even bands start at x = 0, odd bands end at x = W
+            assert x >= 0 and sum(widths) + sum(gaps[1:]) <= W
+            word = []
+            for i, gw in enumerate(widths):
+                x += gaps[i] if i else 0
+                h = 6 if i == 0 and b in (0, 7) else R(3, 6)
+                y = 6 * b + R(0, 6 - h)
+                word.append((x, y, x + gw, y + h))
+                x += gw
+            frame_of_word.append(fr)
+            words.append(word)
+    return frames, block(frame_of_word, T_HAND, polarity, words)

@@ -1,6 +1,9 @@
 """ocr_split_glyphs on the MI355X (csrc/glyph_split.hip) against tests/glyph_split_oracle.py, array for array: the drawn cases, a
 seeded fuzz over column and component input blocks at max_pieces 1..4, a block in which nothing is wide, both memory kinds and every
-OCR_ERR_INVALID case with the handle used again."""
+OCR_ERR_INVALID case with the handle used again.  Past one wave's 64 columns (tests/test_glyph_split_oracle.py shows which wrong
+kernels these tell from the right one): the wide drawn cases in both polarities, the wide fuzz (48 x 1201 frames, glyphs up to 1201
+columns) over SO.WIDE_PARAMS in both polarities and memory kinds with its reach counters re-asserted, 1 to 257 glyphs around the
+workgroup's four, a probe glyph moved through a batch and across frames, and a frame that starts 2^31 bytes into a device block."""
 import ctypes as C
 import functools
 
@@ -87,6 +90,140 @@ def test_seeded_fuzz(det, rule):
     want = SO.split(frames, _as_dict(blk), dict(max_pieces=4, max_word_pieces=2, aspect_pct=50, min_piece_w=4))
     assert np.any(want["word_info"][:, 3] & 4) and not np.all(want["word_info"][:, 3] & 4)
     _same(*det.split_glyphs(frames, blk, dict(max_pieces=4, max_word_pieces=2, aspect_pct=50, min_piece_w=4)), want)
+
+
+WIDE = {c[0]: c for c in SO.wide_drawn_cases()}
+
+
+@pytest.mark.parametrize("name", sorted(WIDE))
+def test_wide_drawn_case(det, name):
+    import torch
+    _, frames, blk, prm, want_boxes, bits = WIDE[name]
+    want = SO.split(frames, blk, prm)
+    got, pmap = det.split_glyphs(frames, _set(blk), prm)
+    _same(got, pmap, want)
+    assert got.boxes.tolist() == want_boxes and got.word_info[:, 3].tolist() == bits
+    d = torch.from_numpy(frames).cuda()
+    torch.cuda.synchronize()
+    n, _, h, w = frames.shape
+    dev, dmap = det.split_glyphs_device(d.data_ptr(), n, h, w, _set(blk), prm)
+    _same(dev, dmap, want)
+    assert dev.boxes.tolist() == want_boxes
+
+
+@functools.lru_cache(maxsize=None)
+def _wide(pol):
+    return SO.wide_fuzz_case(polarity=pol)
+
+
+@pytest.mark.parametrize("pol", [1, 2])
+def test_wide_fuzz(det, pol):
+    """Windows and pieces of several steps of 64, both polarities, every parameter set of SO.WIDE_PARAMS, both memory kinds; the
+    counters say that the oracle's result holds what the case is for."""
+    import torch
+    frames, blk = _wide(pol)
+    gs = _set(blk)
+    d = torch.from_numpy(frames).cuda()
+    torch.cuda.synchronize()
+    total = None
+    for prm in SO.WIDE_PARAMS:
+        want = SO.split(frames, blk, prm)
+        r = SO.reach(frames, blk, prm)
+        total = r if total is None else SO.add_reach(total, r)
+        if prm == dict(max_pieces=2):
+            assert r["cut_ge128"] >= 1
+        if "max_word_pieces" in prm:
+            bit4 = want["word_info"][:, 3] & 4
+            assert bit4.any() and not bit4.all() and (bit4[np.diff(blk["word_offsets"]) > 1] == 0).any()
+        _same(*det.split_glyphs(frames, gs, prm), want)
+        _same(*det.split_glyphs_device(d.data_ptr(), 2, SO.WIDE_H, SO.WIDE_W, gs, prm), want)
+    assert all(total[k] >= 1 for k in SO.REACH_KEYS), total
+    assert set(total["asked"]) == {1, 2, 3, 4}
+
+
+def _scatter(rng, n_glyphs, n_frames, pol, widths=(200, 3, 70, 3, 400, 5, 130, 3, 1000)):
+    """n_glyphs boxes over the wide frames, glyph i of width widths[i % 9] (nine is prime to the workgroup's four, so a glyph that asks
+    for one piece meets every position of a workgroup), words of 1, 2, 3, 1, ... glyphs, the words spread over the frames in order"""
+    boxes = []
+    for i in range(n_glyphs):
+        w, h = widths[i % len(widths)], int(rng.integers(3, 7))
+        x, y = int(rng.integers(0, SO.WIDE_W - w + 1)), int(rng.integers(0, SO.WIDE_H - h + 1))
+        boxes.append((x, y, x + w, y + h))
+    words, i = [], 0
+    while i < n_glyphs:
+        k = len(words) % 3 + 1
+        words.append(boxes[i:i + k])
+        i += k
+    return _on_frames([len(words) * f // n_frames for f in range(n_frames)] + [len(words)], pol, words, n_frames)
+
+
+def _on_frames(first_word, pol, words, n_frames):
+    """SO.block with the frame of each word from first_word (n_frames + 1 word offsets), img_offsets covering every frame"""
+    frame_of_word = [f for f in range(n_frames) for _ in range(first_word[f + 1] - first_word[f])]
+    return dict(SO.block(frame_of_word, SO.T_HAND, pol, words), img_offsets=np.asarray(first_word, np.int32))
+
+
+@pytest.mark.parametrize("n_glyphs", [1, 3, 4, 5, 8, 9, 257])
+def test_glyph_counts_around_a_workgroup(det, n_glyphs):
+    """kSplitGlyphs = 4 glyphs a workgroup: the last workgroup holds 1, 3, 4, 1, 4, 1 and 1 glyphs, and waves that copy their box sit
+    beside waves that cut."""
+    for pol in (1, 2):
+        frames, _ = _wide(pol)
+        blk = _scatter(np.random.default_rng([n_glyphs, pol]), n_glyphs, 2, pol)
+        prm = dict(max_pieces=4, max_word_pieces=12)
+        want = SO.split(frames, blk, prm)
+        assert len(want["asked"]) == n_glyphs and want["asked"][0] > 1
+        if n_glyphs >= 3:
+            assert set((want["asked"][:4] > 1).tolist()) == {False, True}
+        _same(*det.split_glyphs(frames, _set(blk), prm), want)
+
+
+def test_a_glyph_does_not_depend_on_its_neighbours(det):
+    """One probe glyph (three cuts, windows of 150 columns) as glyph 0, 3 and last of a batch of nine, on frames 0 and 2 of three
+    (frame 2 a copy of frame 0, frame 1 another image): its pieces are the same six times, and the whole block is the oracle's."""
+    two, _ = _wide(1)
+    frames = np.ascontiguousarray(two[[0, 1, 0]])
+    probe, prm = (1, 7, 1201, 12), dict(max_pieces=4)
+    alone = SO.split(frames, SO.block([0], SO.T_HAND, 1, [[probe]]), prm)["boxes"]
+    assert len(alone) == 4
+    fill = _scatter(np.random.default_rng(9), 8, 1, 1, widths=(3, 300, 64, 3, 700, 65, 3, 129))
+    fill = [fill["boxes"][a:e].tolist() for a, e in zip(fill["word_offsets"][:-1], fill["word_offsets"][1:])]
+    assert [len(w) for w in fill] == [1, 2, 3, 1, 1]
+    for fr in (0, 2):
+        for n_before in (0, 2, 5):          # words in front of the probe: it is glyph 0, 3 and 8
+            words = fill[:n_before] + [[probe]] + fill[n_before:]
+            # the words before the probe lie on the frames up to its own, those after it on the frames from its own on
+            first = [0, n_before + 1, n_before + 1 + (5 - n_before) // 2, 6] if fr == 0 else [0, n_before // 2, n_before, 6]
+            blk = _on_frames(first, 1, words, 3)
+            pos = sum(len(w) for w in fill[:n_before])
+            assert pos == {0: 0, 2: 3, 5: 8}[n_before] and blk["word_info"][n_before, 0] == fr and blk["boxes"][pos].tolist() == list(probe)
+            got, pmap = det.split_glyphs(frames, _set(blk), prm)
+            _same(got, pmap, SO.split(frames, blk, prm))
+            assert np.array_equal(got.boxes[pmap[:, 0] == pos], alone), (fr, n_before)
+
+
+def test_frame_past_2_31_bytes(det):
+    """257 frames of 1024 x 2049 f32 on the device: frame 256 starts 2^31 + 2^20 bytes into the block and is the only one drawn and
+    the only one with words; the oracle sees that frame alone, as frame 0."""
+    import torch
+    n, h, w = 257, 1024, 2049
+    rng = np.random.default_rng(31)
+    ink = rng.random((h, w)) < 0.1
+    one = np.where(ink, rng.integers(0, 121, (h, w)), rng.integers(121, 256, (h, w))).astype(np.float32)[None, None]
+    words = [[(0, 0, w, 6)], [(5, 500, 705, 512), (706, 503, 709, 509)], [(1000, h - 5, w, h)]]
+    blk0 = SO.block([0, 0, 0], SO.T_HAND, 1, words)
+    prm = dict(max_pieces=4)
+    want = SO.split(one, blk0, prm)
+    r = SO.reach(one, blk0, prm)
+    assert want["asked"].tolist() == [4, 4, 1, 4] and r["win_gt128"] >= 3 and r["piece_gt128"] >= 9
+    blk = _on_frames([0] * n + [3], 1, words, n)
+    want["word_info"][:, 0] = n - 1
+    want["img_offsets"] = blk["img_offsets"]
+    block = torch.empty((n, 1, h, w), dtype=torch.float32, device="cuda")
+    assert (n - 1) * h * w * 4 >= 1 << 31
+    block[n - 1] = torch.from_numpy(one[0]).cuda()
+    torch.cuda.synchronize()
+    _same(*det.split_glyphs_device(block.data_ptr(), n, h, w, _set(blk), prm), want)
 
 
 def test_nothing_wide_comes_back_array_for_array(det):
