@@ -524,10 +524,14 @@ def test_lib() -> C.CDLL:
         L.ocr_test_winograd_conv.argtypes = ([C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int] +
                                              [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p])
         L.ocr_test_det_stage.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-        L.ocr_test_stem_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4
+        L.ocr_test_stem_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int]
         L.ocr_test_head_run.argtypes = ([C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_float, C.c_float] +
-                                        [C.c_void_p] * 2)
-        L.ocr_test_rec_features.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+                                        [C.c_int, C.c_void_p, C.c_void_p, C.c_int])
+        L.ocr_test_convt2_sigmoid.argtypes = ([C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_int])
+        L.ocr_test_binarize.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_void_p, C.c_int]
+        L.ocr_test_binarize_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_int, C.c_void_p, C.c_int]
+        L.ocr_test_rec_features.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int]
         L.ocr_test_rec_fc1.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.ocr_test_rec_fc2.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
         L.ocr_test_comm_assemble.argtypes = [C.POINTER(C.POINTER(Polygons)), C.c_int, C.POINTER(C.POINTER(Polygons))]
@@ -2195,33 +2199,76 @@ class Detector:
                                                 int(nsrc), p(bi), int(bool(relu)), p(rs), int(launches), int(bool(poison)), _ptr(io), int(guard)))
         return io[:px].reshape(n, 8 * h, 8 * w, 64), io[px:]
 
-    def debug_stem_run(self, form, frames, w64x49, scale64, bias64):
+    def debug_stem_run(self, form, frames, w64x49, scale64, bias64, poison=0, guard=None, sentinel=-7.0):
         """The stem alone on caller data (test hook): form 0 exact f32, 1 bf16 precision, 2 split bf16.  frames: N x H x W, uint8 (raw luma)
-        or f32; w64x49: conv1.weight as [64][49].  Returns N x H/4 x W/4 x 64 f32 (form 1: the bf16 output widened)."""
+        or f32; w64x49: conv1.weight as [64][49].  Returns N x H/4 x W/4 x 64 f32 (form 1: the bf16 output widened).
+        The frames sit between two leads of zeros, of quiet NaN (poison=1; uint8 frames: 255) or of +inf (poison=2; uint8: 255).  With
+        guard=g the result is (out, the g rows of 64 behind it), which went to the device as `sentinel` and come back as the kernel left them."""
         x = np.ascontiguousarray(frames)
         if x.dtype != np.uint8:
             x = np.ascontiguousarray(x, dtype=np.float32)
         n, h, w = x.shape
         f = lambda a, shape: np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
         wg, sc, bi = f(w64x49, (64, 49)), f(scale64, (64,)), f(bias64, (64,))
-        out = np.empty((n, h // 4, w // 4, 64), np.float32)
-        check(test_lib().ocr_test_stem_run(self._h, int(form), _ptr(x), int(x.dtype == np.uint8), n, h, w, _ptr(wg), _ptr(sc), _ptr(bi), _ptr(out)))
-        return out
+        rows, g = n * (h // 4) * (w // 4), int(guard or 0)
+        io = np.full((rows + g, 64), sentinel, np.float32)
+        check(test_lib().ocr_test_stem_run(self._h, int(form), _ptr(x), int(x.dtype == np.uint8), n, h, w, _ptr(wg), _ptr(sc), _ptr(bi), int(poison),
+                                           _ptr(io), g))
+        out = io[:rows].reshape(n, h // 4, w // 4, 64)
+        return out if guard is None else (out, io[rows:])
 
-    def debug_head_run(self, form, y_nhwc, wt1, s4, b4, w2t, bias2=0.0, thresh=0.5, want_bitmap=True):
+    def debug_head_run(self, form, y_nhwc, wt1, s4, b4, w2t, bias2=0.0, thresh=0.5, want_bitmap=True, poison=0, guard=None, sentinel=-7.0,
+                       bitmap_sentinel=9):
         """The fused head alone on caller data (test hook): form 0 f32 MFMA, 1 bf16 operands (y and wt1 rounded inside), 2 split bf16.
         y: N x h4 x w4 x 64; wt1: [4 taps a*2+b][64 co][64 ci]; s4 / b4: [256] (tap * 64 + co); w2t: [64 co][4 u = c'*2+d'].
-        Returns (prob N x 4 h4 x 4 w4 f32, bitmap u8 or None)."""
+        Returns (prob N x 4 h4 x 4 w4 f32, bitmap u8 or None).
+        y sits between two leads of zeros, quiet NaN (poison=1) or +inf (poison=2).  With guard=g the result is (prob, bitmap or None, prob's
+        guard g x 4 w4, bitmap's guard or None): rows that went to the device as the sentinels and come back as the kernel left them."""
         y = np.ascontiguousarray(y_nhwc, dtype=np.float32)
         n, h4, w4, c = y.shape
         assert c == 64
         f = lambda a, shape: np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
         wt, s, b, w2 = f(wt1, (4, 64, 64)), f(s4, (256,)), f(b4, (256,)), f(w2t, (64, 4))
-        prob = np.empty((n, 4 * h4, 4 * w4), np.float32)
-        bm = np.empty((n, 4 * h4, 4 * w4), np.uint8) if want_bitmap else None
+        rows, g = n * 4 * h4, int(guard or 0)
+        pio = np.full((rows + g, 4 * w4), sentinel, np.float32)
+        bio = np.full((rows + g, 4 * w4), bitmap_sentinel, np.uint8) if want_bitmap else None
         check(test_lib().ocr_test_head_run(self._h, int(form), _ptr(y), n, h4, w4, _ptr(wt), _ptr(s), _ptr(b), _ptr(w2), float(bias2), float(thresh),
-                                           _ptr(prob), _ptr(bm) if want_bitmap else None))
-        return prob, bm
+                                           int(poison), _ptr(pio), _ptr(bio) if want_bitmap else None, g))
+        prob = pio[:rows].reshape(n, 4 * h4, 4 * w4)
+        bm = bio[:rows].reshape(n, 4 * h4, 4 * w4) if want_bitmap else None
+        return (prob, bm) if guard is None else (prob, bm, pio[rows:], bio[rows:] if want_bitmap else None)
+
+    def debug_convt2_sigmoid(self, x_nhwc, w4x64, bias=0.0, thresh=0.5, want_bitmap=True, poison=0, guard=8, sentinel=-7.0, bitmap_sentinel=9):
+        """convt2_sigmoid_kernel alone on caller data (test hook): x N x H2 x W2 x 64 f32 between two leads (zeros, NaN or +inf as poison = 0, 1,
+        2); w4x64 [4 taps a*2+b][64].  Returns (prob N x 2 H2 x 2 W2 f32, bitmap u8 or None, prob's guard rows, bitmap's guard rows or None)."""
+        x = np.ascontiguousarray(x_nhwc, dtype=np.float32)
+        n, h2, w2, c = x.shape
+        assert c == 64
+        wt = np.ascontiguousarray(np.asarray(w4x64, dtype=np.float32).reshape(4, 64))
+        rows, g = n * 2 * h2, int(guard)
+        pio = np.full((rows + g, 2 * w2), sentinel, np.float32)
+        bio = np.full((rows + g, 2 * w2), bitmap_sentinel, np.uint8) if want_bitmap else None
+        check(test_lib().ocr_test_convt2_sigmoid(self._h, _ptr(x), n, h2, w2, _ptr(wt), float(bias), float(thresh), int(poison), _ptr(pio),
+                                                 _ptr(bio) if want_bitmap else None, g))
+        return (pio[:rows].reshape(n, 2 * h2, 2 * w2), bio[:rows].reshape(n, 2 * h2, 2 * w2) if want_bitmap else None, pio[rows:],
+                bio[rows:] if want_bitmap else None)
+
+    def debug_binarize(self, prob, thresh, poison=0, guard=64, sentinel=9):
+        """launch_binarize on caller data (test hook): prob, any shape, f32, between two leads.  Returns (bitmap u8 [size], its guard bytes)."""
+        x = np.ascontiguousarray(prob, dtype=np.float32).reshape(-1)
+        io = np.full(x.size + int(guard), sentinel, np.uint8)
+        check(test_lib().ocr_test_binarize(self._h, _ptr(x), x.size, float(thresh), int(poison), _ptr(io), int(guard)))
+        return io[:x.size], io[x.size:]
+
+    def debug_binarize_pack(self, prob, thresh, poison=0, guard=8, sentinel=0xA5A5A5A5):
+        """launch_binarize_pack on caller data (test hook): prob n_images x px_per_image f32 between two leads.  Returns (words u32
+        [n_images][2 ceil(px / 64)], the guard words behind them)."""
+        x = np.ascontiguousarray(prob, dtype=np.float32)
+        n, px = x.shape
+        words = n * ((px + 63) // 64 * 2)
+        io = np.full(words + int(guard), sentinel, np.uint32)
+        check(test_lib().ocr_test_binarize_pack(self._h, _ptr(x), n, px, float(thresh), int(poison), _ptr(io), int(guard)))
+        return io[:words].reshape(n, -1), io[words:]
 
     def debug_bf16_basic_block(self, x_nhwc, w1, w2, scale1=None, bias1=None, scale2=None, bias2=None, fused=True, num_cus=0, iters=1):
         """one BasicBlock 64 -> 64 of the bf16 precision (test hook): fused = basic_block_bf16_c64.hip (one launch), otherwise two
@@ -2526,16 +2573,23 @@ class Recognizer:
     def synchronize(self) -> None:
         check(lib().ocr_rec_synchronize(self._h))
 
-    def debug_rec_features(self, form, crops, w1, b1, w2, b2):
+    def debug_rec_features(self, form, crops, w1, b1, w2, b2, crops_per_block=0, poison=0, guard=None, sentinel=-7.0):
         """conv1 + pool + conv2 + pool on caller weights (test hook): form 0 the exact-f32 kernel, 1 the small-batch split-bf16 one.
-        crops: n x 784; w1 [32][25], b1 [32], w2 [64][32][25], b2 [64].  Returns n x 1024 f32 in the order co * 16 + p."""
+        crops: n x 784; w1 [32][25], b1 [32], w2 [64][32][25], b2 [64].  Returns n x 1024 f32 in the order co * 16 + p.
+        crops_per_block (form 0): 0 = chosen by n as shipped, 1, 2 or 4 = that instantiation of rec_conv_kernel.  The crops sit between two
+        leads of four crops: zeros, quiet NaN (poison=1) or +inf (poison=2).  With guard=g the result is (feat, the rows behind it), rows
+        that went to the device as `sentinel` and come back as the kernel left them: g rows for form 0; for form 1 the pad rows of the last
+        16-crop tile and max(1, ceil(g / 16)) further tiles."""
         f = lambda a, shape: np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
         x = f(crops, (-1, 784))
         n = x.shape[0]
         w1, b1, w2, b2 = f(w1, (32, 25)), f(b1, (32,)), f(w2, (64, 32, 25)), f(b2, (64,))
-        feat = np.empty((n, 1024), np.float32)
-        check(test_lib().ocr_test_rec_features(self._h, int(form), _ptr(x), n, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(feat)))
-        return feat
+        g = int(guard or 0)
+        rows = n + g if int(form) == 0 else 16 * ((n + 15) // 16 + max(1, (g + 15) // 16))
+        io = np.full((rows, 1024), sentinel, np.float32)
+        check(test_lib().ocr_test_rec_features(self._h, int(form), int(crops_per_block), _ptr(x), n, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), int(poison),
+                                               _ptr(io), g))
+        return io[:n] if guard is None else (io[:n], io[n:])
 
     def debug_rec_fc1(self, form, feat, w, bias, poison=False, guard=8, sentinel=-7.0):
         """fc1 + bias + ReLU on caller weights (test hook): form 0 the large-batch conv_igemm GEMM, 1 rec_fc1_ksplit_kernel.  feat: n x 1024;

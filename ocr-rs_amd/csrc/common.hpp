@@ -326,7 +326,8 @@ std::vector<float> rec_fc2_small_fragments(const float* w_62x512);
 void launch_rec_small(const RecWeights& w, const float* crops, int n, float* feat, float* hid, float* logits62, int32_t* labels,
                       double* probs, hipStream_t s, int stage);
 bool rec_small_batch(int n);   // the latency-optimised kernels (16x16x4 MFMA chains) take batches up to 1024 crops
-void launch_rec_conv(const RecWeights& w, const float* crops, int n, float* feat, hipStream_t s);
+// crops_per_block: 0 = rec_crops_per_block(n), what the engine runs; 1, 2 or 4 force that instantiation (kernel-level tests)
+void launch_rec_conv(const RecWeights& w, const float* crops, int n, float* feat, hipStream_t s, int crops_per_block = 0);
 std::vector<float> rec_fc2_fragments(const float* w_62x512);
 // fc1 + bias + ReLU of the large-batch path: feat [n][1024] x f1w -> hid [n][512] as one conv_igemm 1x1 GEMM named "rec_fc1"
 void launch_rec_fc1(const RecWeights& w, const float* feat, int n, float* hid, hipStream_t s);

@@ -578,10 +578,12 @@ bool rec_small_batch(int n) { return n <= kRecSmallBatch; }
 
 int rec_crops_per_block(int n) { return n <= 768 ? 1 : n <= 3072 ? 2 : 4; }
 
-void launch_rec_conv(const RecWeights& w, const float* crops, int n, float* feat, hipStream_t s) {
+void launch_rec_conv(const RecWeights& w, const float* crops, int n, float* feat, hipStream_t s, int crops_per_block) {
+  if (crops_per_block != 0 && crops_per_block != 1 && crops_per_block != 2 && crops_per_block != 4)
+    fail(OCR_ERR_INVALID, "rec conv: %d crops per workgroup (0 = by batch, 1, 2 or 4)", crops_per_block);
   if (n <= 0) return;
   // few crops: one per workgroup so that every CU gets work; many: four, so that a tap's weights serve four row tiles
-  const int t = rec_crops_per_block(n);
+  const int t = crops_per_block ? crops_per_block : rec_crops_per_block(n);
   const dim3 grid((n + t - 1) / t), block(256);
   if (t == 1) hipLaunchKernelGGL(rec_conv_kernel<1>, grid, block, 0, s, crops, n, w.c1f, w.c1b, w.c2f, w.c2b, feat);
   else if (t == 2) hipLaunchKernelGGL(rec_conv_kernel<2>, grid, block, 0, s, crops, n, w.c1f, w.c1b, w.c2f, w.c2b, feat);

@@ -588,6 +588,16 @@ struct HookBuffers {
     else OCR_HIP(hipMemset(d, 0, std::max<size_t>(bytes, 16)));
     return d;
   }
+  // `bytes` of src inside one allocation with at least `lead` bytes (rounded up to whole 256) in front of them and behind them, every
+  // 4-byte word of both leads = fill: what a kernel reads outside the source it was given is then in mapped memory and of a known value
+  void* framed(const void* src, size_t bytes, size_t lead, uint32_t fill) {
+    lead = (lead + 255) / 256 * 256;
+    const size_t total = (lead + bytes + lead + 3) / 4 * 4;
+    std::vector<uint8_t> t(total);
+    for (size_t i = 0; i < total; i += 4) std::memcpy(&t[i], &fill, 4);
+    std::memcpy(&t[lead], src, bytes);
+    return static_cast<uint8_t*>(raw(t.data(), total)) + lead;
+  }
   float* f32(const float* src, size_t elems) { return static_cast<float*>(raw(src, elems * 4)); }
   void* u16(const std::vector<uint16_t>& v) { return raw(v.data(), v.size() * 2); }
   void* as_bf16(const float* src, size_t elems) {
@@ -600,23 +610,41 @@ struct HookBuffers {
 
 extern "C" {
 
+// The hooks below share two habits.  SOURCES sit inside one allocation between two leads (HookBuffers::framed) of zeros, or with
+// poison = 1 of quiet NaN (u8 data: 255), or with poison = 2 of +inf (u8: 255): the sizes handed to the launcher state the real data only,
+// so a read outside them - multiplied by a zero weight or not - shows as a changed bit.  OUTPUTS are *_io arrays with guard rows behind the
+// result: uploaded before the launch and downloaded whole after it, so what the caller put into the guard comes back only if the kernel
+// wrote nothing there.
+static uint32_t hook_lead_fill(int poison, int elem_bytes) {
+  if (!poison) return 0u;
+  if (elem_bytes == 1) return 0xffffffffu;
+  if (elem_bytes == 2) return poison == 2 ? 0x7f807f80u : 0x7fc07fc0u;
+  return poison == 2 ? 0x7f800000u : 0x7fc00000u;
+}
+static void hook_check_poison(int poison, int guard) {
+  if (poison < 0 || poison > 2 || guard < 0) ocr::fail(OCR_ERR_INVALID, "hook: poison is 0, 1 or 2 and the guard not negative");
+}
+
 // the stem alone (stem_tail.hip) on caller data: conv 7x7 s2 p3 (1 -> 64) * scale + bias, ReLU, max pool 3x3 s2 p1.  form 0 = launch_stem
 // (exact f32), 1 = launch_stem_bf16 (bf16 precision; the output is widened to f32), 2 = launch_stem_x3 (split bf16).  x: n x h x w frames, f32
-// or (x_is_u8) u8; w64x49: conv1.weight [64][7][7]; out: [n][h / 4][w / 4][64] f32
+// or (x_is_u8) u8, framed by at least eight frame rows; w64x49: conv1.weight [64][7][7]; out_io: [n * h / 4 * w / 4 + guard_rows][64] f32 -
+// form 1's output is bf16 on the device, guard included (out_io is rounded on the way up and widened on the way back)
 int ocr_test_stem_run(ocr_det_t* det, int form, const void* x, int x_is_u8, int n, int h, int w, const float* w64x49, const float* scale64,
-                      const float* bias64, float* out_nhwc_f32) {
+                      const float* bias64, int poison, float* out_io, int guard_rows) {
   return guard([&] {
     using namespace ocr;
-    if (!det || !x || !w64x49 || !scale64 || !bias64 || !out_nhwc_f32) fail(OCR_ERR_INVALID, "null argument");
+    if (!det || !x || !w64x49 || !scale64 || !bias64 || !out_io) fail(OCR_ERR_INVALID, "null argument");
     if (form < 0 || form > 2 || n <= 0 || h <= 0 || w <= 0) fail(OCR_ERR_INVALID, "stem hook: bad form or shape");
+    hook_check_poison(poison, guard_rows);
     OCR_HIP(hipSetDevice(det->impl.device()));
     hipStream_t s = det->impl.stream();
     HookBuffers b;
-    const size_t in_e = (size_t)n * h * w, out_e = (size_t)n * (h / 4) * (w / 4) * 64;
-    void* d_x = b.raw(x, in_e * (x_is_u8 ? 1 : 4));
+    const size_t eb = x_is_u8 ? 1 : 4;
+    const size_t in_e = (size_t)n * h * w, out_e = ((size_t)n * (h / 4) * (w / 4) + guard_rows) * 64;
+    void* d_x = b.framed(x, in_e * eb, (size_t)8 * w * eb, hook_lead_fill(poison, (int)eb));
     const float* d_sc = b.f32(scale64, 64);
     const float* d_bi = b.f32(bias64, 64);
-    void* d_out = b.raw(nullptr, out_e * (form == 1 ? 2 : 4));
+    void* d_out = form == 1 ? b.as_bf16(out_io, out_e) : b.f32(out_io, out_e);
     if (form == 0) {   // [64][49] -> [49][64], as the engine uploads it
       std::vector<float> t(49 * 64);
       for (int c = 0; c < 64; ++c)
@@ -633,45 +661,120 @@ int ocr_test_stem_run(ocr_det_t* det, int form, const void* x, int x_is_u8, int 
       OCR_HIP(hipMemcpy(t.data(), d_out, out_e * 2, hipMemcpyDeviceToHost));
       for (size_t i = 0; i < out_e; ++i) {
         const uint32_t u = (uint32_t)t[i] << 16;
-        std::memcpy(&out_nhwc_f32[i], &u, 4);
+        std::memcpy(&out_io[i], &u, 4);
       }
     } else {
-      OCR_HIP(hipMemcpy(out_nhwc_f32, d_out, out_e * 4, hipMemcpyDeviceToHost));
+      OCR_HIP(hipMemcpy(out_io, d_out, out_e * 4, hipMemcpyDeviceToHost));
     }
   });
 }
 // the fused head alone (tail_fused.hip) on caller data: form = launch_tail_fused's `bf16` (0 f32 MFMA, 1 bf16 operands - y and wt1 are
-// rounded on the way in -, 2 split bf16: wt1 as split3_weights planes).  y: [n][h4][w4][64]; wt1: [4 taps][64 co][64 ci]; s4 / b4: [256]
-// (tap * 64 + co); w2t: [64 co][4]; prob: [n][4 h4][4 w4] f32, bitmap (optional) the same shape in u8
+// rounded on the way in -, 2 split bf16: wt1 as split3_weights planes).  y: [n][h4][w4][64], framed by at least 128 pixel rows (one
+// workgroup's worth); wt1: [4 taps][64 co][64 ci]; s4 / b4: [256] (tap * 64 + co); w2t: [64 co][4]; prob_io: [n * 4 h4 + guard_rows][4 w4]
+// f32, bitmap_io (optional) the same shape in u8
 int ocr_test_head_run(ocr_det_t* det, int form, const float* y_nhwc, int n, int h4, int w4, const float* wt1, const float* s4, const float* b4,
-                      const float* w2t, float bias2, float thresh, float* prob_out, uint8_t* bitmap_out_or_null) {
+                      const float* w2t, float bias2, float thresh, int poison, float* prob_io, uint8_t* bitmap_io_or_null, int guard_rows) {
   return guard([&] {
     using namespace ocr;
-    if (!det || !y_nhwc || !wt1 || !s4 || !b4 || !w2t || !prob_out) fail(OCR_ERR_INVALID, "null argument");
+    if (!det || !y_nhwc || !wt1 || !s4 || !b4 || !w2t || !prob_io) fail(OCR_ERR_INVALID, "null argument");
     if (form < 0 || form > 2 || n <= 0 || h4 <= 0 || w4 <= 0) fail(OCR_ERR_INVALID, "head hook: bad form or shape");
+    hook_check_poison(poison, guard_rows);
     OCR_HIP(hipSetDevice(det->impl.device()));
     hipStream_t s = det->impl.stream();
     HookBuffers b;
-    const size_t m = (size_t)n * h4 * w4, y_e = m * 64, w_e = (size_t)4 * 64 * 64, px = m * 16;
-    const void* d_y = form == 1 ? b.as_bf16(y_nhwc, y_e) : b.f32(y_nhwc, y_e);
+    const size_t m = (size_t)n * h4 * w4, y_e = m * 64, w_e = (size_t)4 * 64 * 64, px = ((size_t)n * 4 * h4 + guard_rows) * 4 * w4;
+    const void* d_y;
+    if (form == 1) {
+      std::vector<uint16_t> t(y_e);
+      for (size_t i = 0; i < y_e; ++i) t[i] = hook_bf16_bits(y_nhwc[i]);
+      d_y = b.framed(t.data(), y_e * 2, (size_t)128 * 64 * 2, hook_lead_fill(poison, 2));
+    } else {
+      d_y = b.framed(y_nhwc, y_e * 4, (size_t)128 * 64 * 4, hook_lead_fill(poison, 4));
+    }
     const void* d_w = form == 1 ? b.as_bf16(wt1, w_e) : form == 2 ? b.u16(split3_weights(wt1, w_e)) : b.f32(wt1, w_e);
-    float* d_prob = static_cast<float*>(b.raw(nullptr, px * 4));
-    uint8_t* d_bm = bitmap_out_or_null ? static_cast<uint8_t*>(b.raw(nullptr, px)) : nullptr;
+    float* d_prob = b.f32(prob_io, px);
+    uint8_t* d_bm = bitmap_io_or_null ? static_cast<uint8_t*>(b.raw(bitmap_io_or_null, px)) : nullptr;
     launch_tail_fused(d_y, d_w, form, b.f32(s4, 256), b.f32(b4, 256), b.f32(w2t, 256), bias2, d_prob, d_bm, thresh, n, h4, w4, s);
     OCR_HIP(hipStreamSynchronize(s));
-    OCR_HIP(hipMemcpy(prob_out, d_prob, px * 4, hipMemcpyDeviceToHost));
-    if (d_bm) OCR_HIP(hipMemcpy(bitmap_out_or_null, d_bm, px, hipMemcpyDeviceToHost));
+    OCR_HIP(hipMemcpy(prob_io, d_prob, px * 4, hipMemcpyDeviceToHost));
+    if (d_bm) OCR_HIP(hipMemcpy(bitmap_io_or_null, d_bm, px, hipMemcpyDeviceToHost));
   });
 }
-// conv1 + pool + conv2 + pool of the recogniser (rec_net.hip) on caller weights: form 0 = launch_rec_conv (exact f32, crops per workgroup
-// chosen by n as shipped), 1 = launch_rec_small stage 0 (split-bf16 conv2).  crops: [n][784]; w1: [32][25]; w2: [64][32][25]; feat_out:
-// [n][1024] as k = co * 16 + p in both forms - form 1's kernel writes the operand order of the fc1 kernel, undone here
-int ocr_test_rec_features(ocr_rec_t* rec, int form, const float* crops, int n, const float* w1, const float* b1, const float* w2, const float* b2,
-                          float* feat_out) {
+// the two-kernel head's second half (stem_tail.hip's convt2_sigmoid_kernel) on caller data: convT 2x2 s2 (64 -> 1) + bias + sigmoid
+// (+ binarize).  in: [n][H2][W2][64] f32, framed by at least 128 pixels; w4x64: [4 taps a * 2 + b][64]; prob_io: [n * 2 H2 + guard_rows][2 W2]
+// f32, bitmap_io (optional) the same shape in u8
+int ocr_test_convt2_sigmoid(ocr_det_t* det, const float* in, int n, int H2, int W2, const float* w4x64, float bias, float thresh, int poison,
+                            float* prob_io, uint8_t* bitmap_io_or_null, int guard_rows) {
   return guard([&] {
     using namespace ocr;
-    if (!rec || !crops || !w1 || !b1 || !w2 || !b2 || !feat_out) fail(OCR_ERR_INVALID, "null argument");
+    if (!det || !in || !w4x64 || !prob_io) fail(OCR_ERR_INVALID, "null argument");
+    if (n <= 0 || H2 <= 0 || W2 <= 0) fail(OCR_ERR_INVALID, "convt2 hook: bad shape");
+    hook_check_poison(poison, guard_rows);
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    HookBuffers b;
+    const size_t in_e = (size_t)n * H2 * W2 * 64, px = ((size_t)n * 2 * H2 + guard_rows) * 2 * W2;
+    const float* d_in = static_cast<const float*>(b.framed(in, in_e * 4, (size_t)128 * 64 * 4, hook_lead_fill(poison, 4)));
+    float* d_prob = b.f32(prob_io, px);
+    uint8_t* d_bm = bitmap_io_or_null ? static_cast<uint8_t*>(b.raw(bitmap_io_or_null, px)) : nullptr;
+    launch_convt2_sigmoid(d_in, b.f32(w4x64, 256), bias, d_prob, d_bm, thresh, n, H2, W2, s);
+    OCR_HIP(hipStreamSynchronize(s));
+    OCR_HIP(hipMemcpy(prob_io, d_prob, px * 4, hipMemcpyDeviceToHost));
+    if (d_bm) OCR_HIP(hipMemcpy(bitmap_io_or_null, d_bm, px, hipMemcpyDeviceToHost));
+  });
+}
+// launch_binarize on caller data: prob [n] f32, framed by at least 4096 floats; bitmap_io: [n + guard_elems] u8
+int ocr_test_binarize(ocr_det_t* det, const float* prob, size_t n, float thresh, int poison, uint8_t* bitmap_io, int guard_elems) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !prob || !bitmap_io) fail(OCR_ERR_INVALID, "null argument");
+    if (n == 0) fail(OCR_ERR_INVALID, "binarize hook: no pixels");
+    hook_check_poison(poison, guard_elems);
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    HookBuffers b;
+    const float* d_prob = static_cast<const float*>(b.framed(prob, n * 4, (size_t)4096 * 4, hook_lead_fill(poison, 4)));
+    uint8_t* d_bm = static_cast<uint8_t*>(b.raw(bitmap_io, n + guard_elems));
+    launch_binarize(d_prob, d_bm, thresh, n, s);
+    OCR_HIP(hipStreamSynchronize(s));
+    OCR_HIP(hipMemcpy(bitmap_io, d_bm, n + guard_elems, hipMemcpyDeviceToHost));
+  });
+}
+// launch_binarize_pack on caller data: prob [n_images][px_per_image] f32, framed by at least 4096 floats; words_io: [n_images *
+// binarize_pack_words(px_per_image) + guard_words] 32-bit words
+int ocr_test_binarize_pack(ocr_det_t* det, const float* prob, int n_images, size_t px_per_image, float thresh, int poison, uint32_t* words_io,
+                           int guard_words) {
+  return guard([&] {
+    using namespace ocr;
+    if (!det || !prob || !words_io) fail(OCR_ERR_INVALID, "null argument");
+    if (n_images <= 0 || px_per_image == 0) fail(OCR_ERR_INVALID, "binarize_pack hook: no pixels");
+    hook_check_poison(poison, guard_words);
+    OCR_HIP(hipSetDevice(det->impl.device()));
+    hipStream_t s = det->impl.stream();
+    HookBuffers b;
+    const size_t words = (size_t)n_images * binarize_pack_words(px_per_image) + guard_words;
+    const float* d_prob =
+        static_cast<const float*>(b.framed(prob, (size_t)n_images * px_per_image * 4, (size_t)4096 * 4, hook_lead_fill(poison, 4)));
+    uint32_t* d_w = static_cast<uint32_t*>(b.raw(words_io, words * 4));
+    launch_binarize_pack(d_prob, d_w, thresh, n_images, px_per_image, s);
+    OCR_HIP(hipStreamSynchronize(s));
+    OCR_HIP(hipMemcpy(words_io, d_w, words * 4, hipMemcpyDeviceToHost));
+  });
+}
+// conv1 + pool + conv2 + pool of the recogniser (rec_net.hip) on caller weights: form 0 = launch_rec_conv (exact f32; crops_per_block 0 =
+// chosen by n as shipped, 1 / 2 / 4 = that instantiation of rec_conv_kernel), 1 = launch_rec_small stage 0 (split-bf16 conv2;
+// crops_per_block must be 0).  crops: [n][784], framed by at least four crops; w1: [32][25]; w2: [64][32][25].  feat_io: rows of 1024 as
+// k = co * 16 + p in both forms.  Form 0: n + guard_rows rows.  Form 1: 16 (ceil(n / 16) + max(1, ceil(guard_rows / 16))) rows - the kernel
+// writes the operand order of the fc1 kernel, whole 16-crop tiles: the hook permutes every row on the way up and back, so the pad rows
+// of the last tile and the tiles behind it reach the caller as well
+int ocr_test_rec_features(ocr_rec_t* rec, int form, int crops_per_block, const float* crops, int n, const float* w1, const float* b1,
+                          const float* w2, const float* b2, int poison, float* feat_io, int guard_rows) {
+  return guard([&] {
+    using namespace ocr;
+    if (!rec || !crops || !w1 || !b1 || !w2 || !b2 || !feat_io) fail(OCR_ERR_INVALID, "null argument");
     if (form < 0 || form > 1 || n <= 0) fail(OCR_ERR_INVALID, "rec hook: bad form or batch");
+    if (form == 1 && crops_per_block != 0) fail(OCR_ERR_INVALID, "rec hook: crops_per_block belongs to form 0");
+    hook_check_poison(poison, guard_rows);
     OCR_HIP(hipSetDevice(rec->impl.device()));
     hipStream_t s = rec->impl.stream();
     HookBuffers b;
@@ -679,33 +782,39 @@ int ocr_test_rec_features(ocr_rec_t* rec, int form, const float* crops, int n, c
     rw.c1f = b.f32(rec_conv1_fragments(w1).data(), 13 * 64);
     rw.c1b = b.f32(b1, 32);
     rw.c2b = b.f32(b2, 64);
-    const float* d_crops = b.f32(crops, (size_t)n * 784);
-    const size_t tiles = ((size_t)n + 15) / 16;
-    std::vector<float> t(tiles * 16 * 1024);
-    float* d_feat = static_cast<float*>(b.raw(nullptr, t.size() * 4));   // whole 16-crop tiles: the operand order interleaves a tile's crops
+    const float* d_crops = static_cast<const float*>(b.framed(crops, (size_t)n * 784 * 4, (size_t)4 * 784 * 4, hook_lead_fill(poison, 4)));
     if (form == 0) {
+      const size_t e = ((size_t)n + guard_rows) * 1024;
+      float* d_feat = b.f32(feat_io, e);
       const std::vector<float> f2 = rec_conv2_fragments(w2);
       rw.c2f = b.f32(f2.data(), f2.size());
-      launch_rec_conv(rw, d_crops, n, d_feat, s);
-    } else {
-      rw.c2x = b.u16(rec_conv2_small_x3_fragments(w2));
-      launch_rec_small(rw, d_crops, n, d_feat, nullptr, nullptr, nullptr, nullptr, s, 0);
-    }
-    OCR_HIP(hipStreamSynchronize(s));
-    OCR_HIP(hipMemcpy(t.data(), d_feat, t.size() * 4, hipMemcpyDeviceToHost));
-    if (form == 0) {
-      std::copy(t.begin(), t.begin() + (size_t)n * 1024, feat_out);
+      launch_rec_conv(rw, d_crops, n, d_feat, s, crops_per_block);
+      OCR_HIP(hipStreamSynchronize(s));
+      OCR_HIP(hipMemcpy(feat_io, d_feat, e * 4, hipMemcpyDeviceToHost));
       return;
     }
     // operand order [tile of 16 crops][g: sixteen k][q][r: crop of the tile][e] holds k = 16 g + 4 q + e of crop 16 tile + r
-    for (size_t tile = 0; tile < tiles; ++tile)
-      for (int g = 0; g < 64; ++g)
-        for (int q = 0; q < 4; ++q)
-          for (int r = 0; r < 16; ++r)
-            for (int e = 0; e < 4; ++e) {
-              const size_t crop = tile * 16 + r;
-              if (crop < (size_t)n) feat_out[crop * 1024 + 16 * g + 4 * q + e] = t[((((tile * 64 + g) * 4 + q) * 16 + r) * 4) + e];
-            }
+    const size_t tiles = ((size_t)n + 15) / 16 + std::max<size_t>(1, ((size_t)guard_rows + 15) / 16);
+    std::vector<float> t(tiles * 16 * 1024);
+    auto permute = [&](bool up) {
+      for (size_t tile = 0; tile < tiles; ++tile)
+        for (int g = 0; g < 64; ++g)
+          for (int q = 0; q < 4; ++q)
+            for (int r = 0; r < 16; ++r)
+              for (int e = 0; e < 4; ++e) {
+                float& dev = t[((((tile * 64 + g) * 4 + q) * 16 + r) * 4) + e];
+                float& host = feat_io[(tile * 16 + r) * 1024 + 16 * g + 4 * q + e];
+                if (up) dev = host;
+                else host = dev;
+              }
+    };
+    permute(true);
+    float* d_feat = b.f32(t.data(), t.size());
+    rw.c2x = b.u16(rec_conv2_small_x3_fragments(w2));
+    launch_rec_small(rw, d_crops, n, d_feat, nullptr, nullptr, nullptr, nullptr, s, 0);
+    OCR_HIP(hipStreamSynchronize(s));
+    OCR_HIP(hipMemcpy(t.data(), d_feat, t.size() * 4, hipMemcpyDeviceToHost));
+    permute(false);
   });
 }
 

@@ -10,6 +10,10 @@ C3  the dropped-product bar: normalised rms error against f64 <= sqrt(rms of six
     separation of 5 x).  A kernel that loses lo.hi, hi.lo or mid.mid fails here and nowhere else.  docs/split_bf16_error.md
     records the measured values (run with -s to print them).
 C4  the bf16-precision forms against f64 on the rounded operands.
+C5  memory discipline of the stem and the head (the recogniser's conv stage: tests/test_gpu_rec_conv_kernels.py): the hooks put the
+    frames / y between two leads and guard rows behind every output.  Nothing is written behind an output; leads of NaN (u8 frames: 255)
+    change no bit of the result - the padded MFMA rows and the zero-weight pad taps read zeros or nothing, M = 1 leaves 127 padded rows of
+    a head workgroup -; a frame or image of NaN (u8: 255 among frames of 0) leaves its neighbours' bits alone.
 """
 import functools
 import itertools
@@ -274,3 +278,74 @@ def test_head_bf16_matches_f64_on_rounded_operands(det, shape):
     ref = E.HeadCase(E.bf16_round(y), E.bf16_round(wt1), s4, b4, w2t, bias2).ref
     prob, _ = det.debug_head_run(1, y, wt1, s4, b4, w2t, bias2)
     assert float(np.abs(prob - ref).max()) <= 1e-5
+
+
+# ---- C5: guards, poisoned leads, isolation of the items of a batch ---------------------------------------------------------------
+
+GUARD = 8
+STEM_GUARD_SHAPES = [(3, 32, 32), (2, 64, 32), (1, 96, 224)]     # one-tile frames with a neighbour on both sides; two tile rows; a ragged tile column
+HEAD_GUARD_SHAPES = [(1, 1, 1), (1, 1, 127), (1, 3, 43), (3, 5, 7)]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else a.dtype)
+
+
+def _stem_guarded(det, form, frames, ops, poison):
+    out, guard = det.debug_stem_run(form, frames, *ops, poison=poison, guard=GUARD)
+    assert guard.shape == (GUARD, 64) and np.array_equal(guard, np.full_like(guard, -7.0)), ("rows behind the stem's output were written", poison)
+    return out
+
+
+@pytest.mark.parametrize("entry", ["u8", "f32"])
+@pytest.mark.parametrize("form", [0, 1, 2], ids=FORM_NAMES.get)
+@pytest.mark.parametrize("shape", STEM_GUARD_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_stem_stays_inside_its_frames_and_its_output(det, shape, form, entry):
+    ops = E.stem_weights(1)
+    frames = E.stem_family("luma_u8" if entry == "u8" else "fraction", *shape, seed=sum(shape))
+    clean = _stem_guarded(det, form, frames, ops, 0)
+    assert not np.isnan(clean).any() and clean.any()
+    for poison in (1, 2):      # f32: quiet NaN, +inf; u8: 255 both times
+        got = _stem_guarded(det, form, frames, ops, poison)
+        assert np.array_equal(_bits(got), _bits(clean)), (poison, np.argwhere(_bits(got) != _bits(clean))[:4])
+    if shape[0] == 3:
+        if entry == "u8":      # no NaN in u8: the loudest frame among silent ones
+            base = np.zeros(shape, np.uint8)
+            clean = _stem_guarded(det, form, base, ops, 0)
+            bad = base.copy()
+            bad[1] = 255
+        else:
+            bad = frames.copy()
+            bad[1] = np.nan
+        got = _stem_guarded(det, form, bad, ops, 0)
+        assert np.array_equal(_bits(got[[0, 2]]), _bits(clean[[0, 2]])), np.argwhere(_bits(got[[0, 2]]) != _bits(clean[[0, 2]]))[:4]
+
+
+def _head_guarded(det, form, ops, poison, want_bitmap=True):
+    prob, bm, gp, gb = det.debug_head_run(form, *ops, want_bitmap=want_bitmap, poison=poison, guard=GUARD)
+    w = prob.shape[2]
+    assert gp.shape == (GUARD, w) and np.array_equal(gp, np.full_like(gp, -7.0)), ("rows behind prob were written", poison)
+    if want_bitmap:
+        assert gb.shape == (GUARD, w) and np.array_equal(gb, np.full_like(gb, 9)), ("rows behind the bitmap were written", poison)
+        assert np.isin(bm, (0, 1)).all()
+    else:
+        assert bm is None and gb is None
+    return prob, bm
+
+
+@pytest.mark.parametrize("form", [0, 1, 2], ids=FORM_NAMES.get)
+@pytest.mark.parametrize("shape", HEAD_GUARD_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_head_stays_inside_its_pixels_and_its_outputs(det, shape, form):
+    ops = E.head_family(*shape, seed=sum(shape))
+    prob, bm = _head_guarded(det, form, ops, 0)
+    assert not np.isnan(prob).any()
+    for poison in (1, 2):      # rows past M read as zeros: not as what lies behind y
+        p2, b2 = _head_guarded(det, form, ops, poison)
+        assert np.array_equal(_bits(p2), _bits(prob)) and np.array_equal(b2, bm), (poison, np.argwhere(_bits(p2) != _bits(prob))[:4])
+    p3, none = _head_guarded(det, form, ops, 1, want_bitmap=False)
+    assert none is None and np.array_equal(_bits(p3), _bits(prob))
+    if shape[0] == 3:
+        y = ops[0].copy()
+        y[1] = np.nan
+        p4, b4 = _head_guarded(det, form, (y,) + tuple(ops[1:]), 0)
+        assert np.array_equal(_bits(p4[[0, 2]]), _bits(prob[[0, 2]])) and np.array_equal(b4[[0, 2]], bm[[0, 2]])
